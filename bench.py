@@ -18,13 +18,18 @@ Workloads:
 
   python bench.py --gpus N --steps K --warmup W      (N > 1: under torch.distributed.run, or started directly — it then
                                                       spawns the N ranks itself, spawn_ranks below)
+  python bench.py ... --full                         (also the CPU baseline, the spot checks and every extra leg)
+  python bench.py ... --dump-outputs DIR             (the last timed step's outputs as DIR/<name>.npy)
 
-Inputs are resident in HBM before the timed region.  Prints ONE JSON line (rank 0) whose `roofline`
-is the VALU instruction-issue roof (the path is integer-only: no MFMA, HBM three orders of
-magnitude away) with the HBM figures as a sub-block, plus `cpu_baseline` (the
-reference's gmpy2 engine on the host cores) and, on one GPU, the legs `single_batch`, `latency`,
-`end_to_end`, `end_to_end_keygen`, `extra.biprime_k2048`, `extra.biprime_k1024_c256/_c8192` and
-`extra.c5_k4096[_b1024/_b16384]`.  DESIGN.md §6 defines every field.
+Inputs are resident in HBM before the timed region and are the same in every run with the same
+arguments.  Prints ONE JSON line (rank 0) whose `roofline` is the VALU instruction-issue roof (the
+path is integer-only: no MFMA, HBM three orders of magnitude away) with the HBM
+figures as a sub-block.  A plain run does only that: set-up, warm-up, the K timed steps, the line.
+With --full the line also carries `cpu_baseline` (the reference's gmpy2 engine on the host cores),
+the elements of the batch are spot-checked against CPython pow, and on one GPU the legs
+`single_batch`, `latency`, `end_to_end`, `end_to_end_keygen`, `extra.biprime_k2048`,
+`extra.biprime_k1024_c256/_c8192` and `extra.c5_k4096[_b1024/_b16384]` run after the headline.
+DESIGN.md §6 defines every field.
 """
 
 from __future__ import annotations
@@ -73,6 +78,7 @@ def _latest_profile(name: str) -> Path:
 
 
 HBM_MEASURED = _latest_profile("hbm_traffic.json")             # tools/hbm_traffic.py (FETCH_SIZE / WRITE_SIZE passes)
+DUMP_LIMIT, DUMP_SEED = 64 << 20, 0xD15C0                       # --dump-outputs: bytes in all, seed of the row sample
 
 
 def parse() -> argparse.Namespace:
@@ -89,8 +95,14 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="biprime workload on N GPUs: strong = --batch (default 4096) candidates sharded over the ranks (configs[3]), "
                          "weak = that many per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single_batch / end_to_end / extra legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the spot check against CPython pow, the stage timings of the "
+                         "biprime workload and every extra leg; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64; past "
+                         f"{DUMP_LIMIT >> 20} MB in all a fixed, seeded sample of rows, listed in DIR/<name>_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the single_batch / end_to_end / extra legs")
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--check", type=int, default=6, help="elements verified against CPython pow after timing")
     ap.add_argument("--streams", type=int, default=0,
@@ -363,6 +375,7 @@ class DecryptWorkload:
         ln = self.lanes[k % len(self.lanes)]
         buf = ln["bufs"][ln["turn"]]
         ln["turn"] ^= 1
+        self.last_buf = buf                      # what the latest step wrote (--dump-outputs)
         eng, torch = self.eng, self.torch
         with torch.cuda.stream(ln["stream"]):
             if buf["done"] is not None:          # the recombination that read this set two steps ago
@@ -410,6 +423,12 @@ class DecryptWorkload:
                 x = x * allp[k][j] % n2
             assert (x - 1) % n == 0 and msgs[j] == (x - 1) // n * self.theta_inv % n, f"plaintext {e} differs"
         return f"{len(idx)} elements bit-exact vs CPython pow; all {batch} combines divisible by N"
+
+    def outputs(self) -> dict:
+        """What a caller of the timed path receives from its last step: this party's partial decryptions c^exp mod N^2,
+        the recombined plaintexts (both as u32 words, least significant first) and the status byte of every ciphertext."""
+        buf = self.last_buf
+        return {"partial_decryptions": buf["partials"][self.own_slot], "plaintexts": buf["msg"], "status": buf["status"]}
 
 
 def pick_decrypt_shape(eng, args, n_bits: int, batch: int, nstreams: int):
@@ -557,7 +576,8 @@ def run_decrypt_main(args, eng, torch, dist, rank: int, world: int, key_length: 
     wl.make_lanes(nstreams, dist, world, cu_slices=cu_slices)
     elapsed, kernel_ms, launches = time_steps(eng, torch, dist, lambda k: wl.step(k, dist), args.steps, args.warmup, nstreams)
     assert launches == args.steps, (launches, args.steps)
-    note = wl.verify(args.check if rank == 0 else 0, rank, dist)
+    # (a plain run keeps the status flags of every recombination; the spot check against CPython pow is --full's)
+    note = wl.verify(args.check if rank == 0 and args.full else 0, rank, dist)
     if rank != 0:
         return {}
     geo = eng.geometry(wl.n2.bit_length(), batch, 1) if args.generic_modulus else eng.nsquare_launch_shape(wl.n.bit_length(), batch)
@@ -817,6 +837,7 @@ class BiprimeWorkload:
 
     def step(self, k: int, dist) -> None:
         ln = self.lanes[k % len(self.lanes)]
+        self.last_lane = ln                      # what the latest step wrote (--dump-outputs)
         eng = self.eng
         with self.torch.cuda.stream(ln["stream"]):
             for w in ln.pop("works", []):        # the gathers of this lane's previous step must have read its buffers
@@ -854,6 +875,12 @@ class BiprimeWorkload:
         got = [int(x) for x in self.lanes[0]["verdict"][0].cpu().numpy()]
         assert got == want, "verdict bytes differ from DK:1147-1158 on the host"
         return f"candidate 0: {len(keep)} v values bit-exact vs CPython pow, Jacobi selection vs sympy, {self.KEEP} verdict bytes vs host"
+
+    def outputs(self) -> dict:
+        """What a caller of the timed path receives from its last step: this party's v values (candidate x test slot x
+        u32 words, least significant first) and the verdict byte of every (candidate, test slot)."""
+        ln = self.last_lane
+        return {"v_values": ln["v_all"][self.index - 1], "verdicts": ln["verdict"]}
 
 
 def biprime_roofline(eng, wl: BiprimeWorkload, steps: int, elapsed: float, kernel_ms: float, nstreams: int) -> dict:
@@ -940,13 +967,38 @@ def run_biprime(args, eng, torch, dist, rank: int, world: int, key_length: int, 
     wl.make_lanes(nstreams, dist, world)
     elapsed, kernel_ms, launches = time_steps(eng, torch, dist, lambda k: wl.step(k, dist), steps, warmup, nstreams)
     assert launches == steps
-    note = wl.verify(args.check) if rank == 0 else ""
+    note = (wl.verify(args.check) if args.full else "skipped") if rank == 0 else ""
     if dist is not None:
         assert torch.equal(wl.lanes[0]["vote_gather"][rank], wl.lanes[0]["verdict"]), "vote all-gather shard mismatch"
     if rank != 0:
         return {}
     geo = eng.geometry(wl.mod_bits, cands * wl.KEEP, cands)
-    # the stages on their own (one launch each, untimed region above excluded)
+    out = {
+        "metric": f"biprimality-test modexps/sec ({key_length}-bit N)",
+        "value": world * cands * wl.KEEP * steps / elapsed,
+        "unit": "modexps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "distributed": dist_info(torch, dist, world, steps),
+        "config": {
+            "workload": f"C4: {n_parties}-party key_length={key_length} t=2, {total_cands} sieve-surviving candidate moduli "
+                        f"sharded over {world} GPU(s) ({cands}/GPU/step): 160 Jacobi symbols + first-40 selection + 40 modexps "
+                        "g^e mod N per candidate (party 1's exponent (N-p1-q1+1)/4), verdict of all parties' v values"
+                        + ("; all-gather of v rows and verdict bytes" if dist is not None else ""),
+            "candidates_per_gpu": cands, "mod_bits": wl.mod_bits, "exp_bits": wl.exp_bits, "limbs_u32": wl.limbs,
+            "parallelism": f"dp{world}", "steps_in_flight": nstreams, "geometry_K_L_W_blocks": list(geo),
+            "verified": note,
+        },
+        "roofline": biprime_roofline(eng, wl, steps, elapsed, kernel_ms, nstreams),
+        "_wl": wl,
+    }
+    if args.full:
+        out["stages"] = biprime_stages(eng, torch, wl, cands)
+    return out
+
+
+def biprime_stages(eng, torch, wl: BiprimeWorkload, cands: int) -> dict:
+    """The stages on their own (one launch each, untimed region above excluded)."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     j_t = eng.jacobi_t(wl.g_t, wl.mods_op, wl.GENS)
@@ -965,29 +1017,10 @@ def run_biprime(args, eng, torch, dist, rank: int, world: int, key_length: int, 
     verdict_s = time.perf_counter() - t0
     del j_t, big
     return {
-        "metric": f"biprimality-test modexps/sec ({key_length}-bit N)",
-        "value": world * cands * wl.KEEP * steps / elapsed,
-        "unit": "modexps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": elapsed / steps * 1e3,
-        "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "distributed": dist_info(torch, dist, world, steps),
-        "config": {
-            "workload": f"C4: {n_parties}-party key_length={key_length} t=2, {total_cands} sieve-surviving candidate moduli "
-                        f"sharded over {world} GPU(s) ({cands}/GPU/step): 160 Jacobi symbols + first-40 selection + 40 modexps "
-                        "g^e mod N per candidate (party 1's exponent (N-p1-q1+1)/4), verdict of all parties' v values"
-                        + ("; all-gather of v rows and verdict bytes" if dist is not None else ""),
-            "candidates_per_gpu": cands, "mod_bits": wl.mod_bits, "exp_bits": wl.exp_bits, "limbs_u32": wl.limbs,
-            "parallelism": f"dp{world}", "steps_in_flight": nstreams, "geometry_K_L_W_blocks": list(geo),
-            "verified": note,
-        },
-        "stages": {
-            "jacobi_symbols_per_s": cands * wl.GENS / jac_s, "jacobi_ms": jac_s * 1e3,
-            "sieve_candidates_per_s": 65536 / sieve_s, "sieve_ms_65536": sieve_s * 1e3, "sieve_primes": len(wl.primes),
-            "verdict_slots_per_s": cands * wl.KEEP / verdict_s, "verdict_ms": verdict_s * 1e3,
-            "sieve_survival": cands / wl.sieved,
-        },
-        "roofline": biprime_roofline(eng, wl, steps, elapsed, kernel_ms, nstreams),
-        "_wl": wl,
+        "jacobi_symbols_per_s": cands * wl.GENS / jac_s, "jacobi_ms": jac_s * 1e3,
+        "sieve_candidates_per_s": 65536 / sieve_s, "sieve_ms_65536": sieve_s * 1e3, "sieve_primes": len(wl.primes),
+        "verdict_slots_per_s": cands * wl.KEEP / verdict_s, "verdict_ms": verdict_s * 1e3,
+        "sieve_survival": cands / wl.sieved,
     }
 
 
@@ -1217,6 +1250,31 @@ def leg_short_kernels(eng, torch, reps: int = 8) -> dict:
 # ---------------------------------------------------------------------------------------------------
 EXTRAS_FILE = ROOT / "bench_extras.json"
 LINE_TARGET, LINE_LIMIT = 4096, 8192
+
+
+def dump_outputs(directory, arrays: dict, limit: int = DUMP_LIMIT, seed: int = DUMP_SEED) -> dict:
+    """--dump-outputs: every array (a device tensor of u32 words or bytes, first axis = the element of the batch) as
+    DIR/<name>.npy in float64, which holds every u32 exactly.  When the set would exceed `limit` bytes, each array keeps
+    the same seeded, sorted sample of its elements, and DIR/<name>_rows.npy records which ones.  Returns name -> shape."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.view(np.uint32) if a.dtype == np.int32 else a          # the words are unsigned
+    total = sum(a.size * 8 for a in host.values())
+    shapes = {}
+    for name, a in host.items():
+        if total > limit:
+            keep = max(1, int(a.shape[0] * 0.95 * limit / total))            # 5 % left for the row lists
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))
+            np.save(out / f"{name}_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out / f"{name}.npy", a.astype(np.float64))
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def _num(x, digits: int = 5):
@@ -1516,14 +1574,17 @@ def main() -> None:
     for kv in args.knob:
         name, _, value = kv.partition("=")
         eng.debug_knob(name, int(value))
-    extras = world == 1 and not args.no_extras and not args.generic_modulus
+    # a plain run measures the headline alone; the CPU baseline and every extra leg are --full's
+    extras = world == 1 and args.full and not args.no_extras and not args.generic_modulus
     if args.workload in ("c3", "c5"):
         key_length = args.key_length or (2048 if args.workload == "c3" else 4096)
         batch = args.batch or (10000 if args.workload == "c3" else 4096)
         label = "C3 (BASELINE.json configs[2])" if args.workload == "c3" else "C5 (BASELINE.json configs[4])"
         out = run_decrypt_main(args, eng, torch, dist, rank, world, key_length, batch, label)
+        if args.dump_outputs and rank == 0:
+            out["dumped"] = dump_outputs(args.dump_outputs, out["_wl"].outputs())
         cb = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             def _cpu():
                 w_ = out["_wl"]
                 bases = [c if w_.exps[w_.own] >= 0 else pow(c, -1, w_.n2) for c in w_.cts[:64]]
@@ -1608,7 +1669,7 @@ def main() -> None:
                     out["extra"]["c5_k4096_b1024"] = guarded("c5_k4096_b1024", lambda: c5_leg(1024, 24, 8, False))
                     out["extra"]["c5_k4096_b16384"] = guarded("c5_k4096_b16384", lambda: c5_leg(16384, 4, 2, False))
                     out["short_kernels"] = guarded("short_kernels", lambda: leg_short_kernels(eng, torch))
-        if world > 1 and not args.no_extras and args.workload == "c3" and not args.generic_modulus:
+        if world > 1 and args.full and not args.no_extras and args.workload == "c3" and not args.generic_modulus:
             # configs[3] on N GPUs inside the driver's scaling run: 4096 candidates sharded over the ranks,
             # all-gather of the v rows and of the verdict bytes (the biprimality vote, DK:1331-1360)
             if rank == 0:
@@ -1626,8 +1687,10 @@ def main() -> None:
         total = (args.batch or 4096) if weak else (args.batch * world if args.batch else 4096)
         nstreams = args.streams if args.streams > 0 else biprime_lanes(total if weak else -(-total // world), args.steps)
         out = run_biprime(args, eng, torch, dist, rank, world, key_length, total, args.steps, args.warmup, nstreams, weak=weak)
+        if args.dump_outputs and rank == 0:
+            out["dumped"] = dump_outputs(args.dump_outputs, out["_wl"].outputs())
         cb = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             def _cpu_bp():
                 w_ = out["_wl"]
                 secs = args.cpu_seconds if world == 1 else min(args.cpu_seconds, 5.0)

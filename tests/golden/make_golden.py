@@ -45,7 +45,7 @@ import msgpack
 import sympy
 
 HERE = Path(__file__).resolve().parent
-REF_PKG = Path("/root/reference/src/tno/mpc/protocols/distributed_keygen")
+REF_PKG = HERE.parent.parent / "oracle" / "_ref" / "distributed_keygen"       # the unmodified reference modules (oracle/ref_build.py)
 SEED = 0xD15C0
 
 

@@ -1,4 +1,4 @@
-"""Drop-in check against the REAL reference modules (build container only: needs /root/reference).
+"""Drop-in check against the REAL reference modules (where build() has copied them into oracle/_ref).
 
 The unmodified reference ``paillier_shared_key.py`` / ``distributed_keygen.py`` are imported with
 stand-ins for their un-vendored dependencies (the recipe of tests/golden/make_golden.py), three
@@ -17,8 +17,8 @@ from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference/src/tno/mpc/protocols/distributed_keygen")
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="reference sources only exist in the build container")
+REF = Path(__file__).resolve().parent.parent / "oracle" / "_ref" / "distributed_keygen"      # oracle/ref_build.py, run by build()
+NO_REF = "the reference modules are not in oracle/_ref (build() copies them where a checkout of the reference exists)"
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
 
@@ -52,6 +52,8 @@ class FakePool:
 
 @pytest.fixture(scope="module")
 def ref():
+    if not REF.exists():
+        pytest.skip(NO_REF)
     import make_golden
 
     psk, dk = make_golden.load_reference()

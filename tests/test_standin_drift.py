@@ -1,7 +1,7 @@
 """Drift guard: the HIP engine is only ever composed with the builder-written stand-in package
 (tests/standin/keygen_standin, on the GPU box) and the real reference only with the test double of the engine (here).
 What ties the two together is that patch.py touches the SAME names with the SAME call signatures in both.  This test
-imports the unmodified reference (the recipe of tests/golden/make_golden.py; build container only) and asserts that
+imports the unmodified reference (the recipe of tests/golden/make_golden.py; where build() has copied it into oracle/_ref) and asserts that
 every callable patch.py rebinds, calls or instantiates has an identical signature in the stand-in, and that every
 attribute it reads exists on both.
 
@@ -18,8 +18,9 @@ from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference/src/tno/mpc/protocols/distributed_keygen")
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="reference sources only exist in the build container")
+REF = Path(__file__).resolve().parent.parent / "oracle" / "_ref" / "distributed_keygen"      # oracle/ref_build.py, run by build()
+pytestmark = pytest.mark.skipif(not REF.exists(), reason="the reference modules are not in oracle/_ref (build() copies them "
+                                                         "where a checkout of the reference exists)")
 
 sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
 ROOT = Path(__file__).resolve().parent.parent

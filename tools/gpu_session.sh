@@ -78,9 +78,9 @@ for step in "$@"; do
     ;;
   dist_paths)
     # the N > 1 code paths on one GPU: two ranks over gloo (slices, gathers, the distributed biprime leg), one rank over RCCL
-    MX_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 8 --warmup 2 > $O/bench_two_ranks_gloo_one_gpu.json 2> $O/bench_two_ranks_gloo_one_gpu.err; tail -c 1200 $O/bench_two_ranks_gloo_one_gpu.json; echo
-    MX_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 > $O/bench_rccl_single_rank.json 2> $O/bench_rccl_single_rank.err; tail -c 600 $O/bench_rccl_single_rank.json; echo
-    MX_BENCH_FORCE_DIST=1 python bench.py --workload biprime --batch 512 --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_biprime_c512_rccl_single_rank.json 2>/dev/null; tail -c 500 $O/bench_biprime_c512_rccl_single_rank.json; echo
+    MX_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 --steps 8 --warmup 2 > $O/bench_two_ranks_gloo_one_gpu.json 2> $O/bench_two_ranks_gloo_one_gpu.err; tail -c 1200 $O/bench_two_ranks_gloo_one_gpu.json; echo
+    MX_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 > $O/bench_rccl_single_rank.json 2> $O/bench_rccl_single_rank.err; tail -c 600 $O/bench_rccl_single_rank.json; echo
+    MX_BENCH_FORCE_DIST=1 python bench.py --full --workload biprime --batch 512 --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_biprime_c512_rccl_single_rank.json 2>/dev/null; tail -c 500 $O/bench_biprime_c512_rccl_single_rank.json; echo
     ;;
   smoke)
     ( time python -c "import __graft_entry__ as g; g.build(); g.smoke()" ) > $O/smoke.log 2>&1; tail -4 $O/smoke.log
@@ -91,7 +91,7 @@ for step in "$@"; do
   biprime_lanes)
     for spec in "2048 512" "2048 1024" "1024 256"; do set -- $spec
       for st in 1 2 3 4 6; do
-        python bench.py --workload biprime --key-length $1 --batch $2 --streams $st --steps 12 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('biprime k$1 c$2 streams $st:', round(d['value']), 'modexps/s', round(d['ms_per_step'],2), 'ms/step frac', d['roofline'].get('frac'), 'kernel_ms', d['roofline'].get('kernel_ms'), d['config'].get('geometry_K_L_W_blocks'))"
+        python bench.py --full --workload biprime --key-length $1 --batch $2 --streams $st --steps 12 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('biprime k$1 c$2 streams $st:', round(d['value']), 'modexps/s', round(d['ms_per_step'],2), 'ms/step frac', d['roofline'].get('frac'), 'kernel_ms', d['roofline'].get('kernel_ms'), d['config'].get('geometry_K_L_W_blocks'))"
       done
     done | tee $O/biprime_lanes.txt
     ;;
@@ -119,8 +119,8 @@ for step in "$@"; do
   bench_ab)
     for rep in 1 2; do
       for kn in "" "--knob n2_friendly_1w=1"; do
-        python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 5 $kn 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c3 driver flags [$kn]', round(d['value']), 'modexps/s', round(d['ms_per_step'],3), 'ms/step kernel_ms', round(d['roofline']['kernel_ms'],2), 'clock', d['roofline'].get('shader_clock_mhz_measured'))"
-        python bench.py --workload c5 --batch 16384 --streams 2 --steps 4 --warmup 2 --no-extras --no-cpu-baseline $kn 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c5 16384 x 2 in flight [$kn]', round(d['value']), 'modexps/s', round(d['ms_per_step'],2), 'ms/step')"
+        python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 5 $kn 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c3 driver flags [$kn]', round(d['value']), 'modexps/s', round(d['ms_per_step'],3), 'ms/step kernel_ms', round(d['roofline']['kernel_ms'],2), 'clock', d['roofline'].get('shader_clock_mhz_measured'))"
+        python bench.py --full --workload c5 --batch 16384 --streams 2 --steps 4 --warmup 2 --no-extras --no-cpu-baseline $kn 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c5 16384 x 2 in flight [$kn]', round(d['value']), 'modexps/s', round(d['ms_per_step'],2), 'ms/step')"
       done
     done | tee $O/bench_ab.txt
     ;;
@@ -134,13 +134,13 @@ for step in "$@"; do
     ( time python -m pytest tests/test_gpu_stress.py -m gpu -x -q -k "four_streams" --durations=8 ) > $O/pytest_stress.log 2>&1; tail -15 $O/pytest_stress.log
     ;;
   bench)
-    python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err; cp bench_extras.json $O/bench_driver_flags_extras.json
+    python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err; cp bench_extras.json $O/bench_driver_flags_extras.json
     tail -c 2500 $O/bench_driver_flags.json; wc -c $O/bench_driver_flags.json
     ;;
   biprime_small)
     for spec in "1024 256" "2048 512" "2048 100" "2048 25" "2048 1024" "2048 2048" "2048 4096"; do set -- $spec
       steps=16; [ "$2" -le 256 ] && steps=48
-      python bench.py --workload biprime --key-length $1 --batch $2 --steps $steps --warmup 4 --no-cpu-baseline > $O/bench_biprime_k$1_c$2.json 2>/dev/null
+      python bench.py --full --workload biprime --key-length $1 --batch $2 --steps $steps --warmup 4 --no-cpu-baseline > $O/bench_biprime_k$1_c$2.json 2>/dev/null
       python -c "import json,sys; d=json.loads(open('$O/bench_biprime_k$1_c$2.json').read().strip().splitlines()[-1]); print('biprime k$1 c$2', round(d['value']), 'modexps/s', round(d['ms_per_step'],2), 'ms/step frac', d['roofline'].get('frac'), 'kernel_ms', d['roofline'].get('kernel_ms'))"
     done
     ;;
@@ -149,11 +149,11 @@ for step in "$@"; do
     line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value']), d['unit'], round(d['ms_per_step'],3), 'ms/step frac', d['roofline'].get('frac'), 'kernel_ms', d['roofline'].get('kernel_ms'))"; }
     for rep in 1 2; do for lib in shipped $V/noprio.so; do
       [ $lib = shipped ] && unset MX_LIBRARY || export MX_LIBRARY=$R/$lib
-      for st in 6 8 12; do python bench.py --workload biprime --key-length 1024 --batch 256 --streams $st --steps 48 --warmup 12 --no-cpu-baseline 2>/dev/null | line "$lib k1024 c256 lanes $st:"; done
-      for st in 4 8; do python bench.py --workload biprime --key-length 2048 --batch 512 --streams $st --steps 16 --warmup 8 --no-cpu-baseline 2>/dev/null | line "$lib k2048 c512 lanes $st:"; done
-      python bench.py --workload biprime --key-length 2048 --batch 100 --streams 6 --steps 24 --warmup 6 --no-cpu-baseline 2>/dev/null | line "$lib k2048 c100 lanes 6:"
-      python bench.py --workload biprime --no-cpu-baseline 2>/dev/null | line "$lib k2048 c4096:"
-      python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | line "$lib c3 driver flags:"
+      for st in 6 8 12; do python bench.py --full --workload biprime --key-length 1024 --batch 256 --streams $st --steps 48 --warmup 12 --no-cpu-baseline 2>/dev/null | line "$lib k1024 c256 lanes $st:"; done
+      for st in 4 8; do python bench.py --full --workload biprime --key-length 2048 --batch 512 --streams $st --steps 16 --warmup 8 --no-cpu-baseline 2>/dev/null | line "$lib k2048 c512 lanes $st:"; done
+      python bench.py --full --workload biprime --key-length 2048 --batch 100 --streams 6 --steps 24 --warmup 6 --no-cpu-baseline 2>/dev/null | line "$lib k2048 c100 lanes 6:"
+      python bench.py --full --workload biprime --no-cpu-baseline 2>/dev/null | line "$lib k2048 c4096:"
+      python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | line "$lib c3 driver flags:"
     done; done | tee $O/prio_ab.txt
     unset MX_LIBRARY
     ;;
@@ -163,7 +163,7 @@ for step in "$@"; do
     for spec in "1024 256 48" "2048 100 48" "2048 25 48" "2048 256 48" "2048 512 48" "2048 1024 24"; do set -- $spec
       for lpl in -1 9 18; do for st in 4 6 8 12 16 24; do
         [ $((${3} % st)) -ne 0 ] && continue
-        python bench.py --workload biprime --key-length $1 --batch $2 --streams $st --limbs-per-lane $lpl --steps $3 --warmup $st --no-cpu-baseline 2>/dev/null | line "k$1 c$2 lpl $lpl lanes $st:"
+        python bench.py --full --workload biprime --key-length $1 --batch $2 --streams $st --limbs-per-lane $lpl --steps $3 --warmup $st --no-cpu-baseline 2>/dev/null | line "k$1 c$2 lpl $lpl lanes $st:"
       done; done
     done | tee $O/lanes_fine.txt
     ;;
@@ -173,7 +173,7 @@ for step in "$@"; do
     line() { python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value']), d['unit'], round(d['ms_per_step'],3), 'ms/step frac', d['roofline'].get('frac'), 'kernel_ms', d['roofline'].get('kernel_ms'), d['config'].get('geometry_K_L_W_blocks'))"; }
     for spec in "1024 256 9" "2048 100 18" "2048 25 9" "2048 512 18"; do set -- $spec
       for q in 16 24 32; do for aux in 1 0; do for st in 4 8 12 16; do
-        python bench.py --workload biprime --key-length $1 --batch $2 --streams $st --limbs-per-lane $3 --hw-queues $q --priority-aux $aux --steps 48 --warmup $st --no-cpu-baseline 2>/dev/null | line "k$1 c$2 lpl $3 queues $q aux $aux lanes $st:"
+        python bench.py --full --workload biprime --key-length $1 --batch $2 --streams $st --limbs-per-lane $3 --hw-queues $q --priority-aux $aux --steps 48 --warmup $st --no-cpu-baseline 2>/dev/null | line "k$1 c$2 lpl $3 queues $q aux $aux lanes $st:"
       done; done; done
     done | tee $O/lanes_queues.txt
     ;;
@@ -188,14 +188,14 @@ for step in "$@"; do
     for spec in "c5 1024 48" "c5 2048 48" "c5 4096 24" "c3 2048 48" "c3 4096 48" "c3 10000 24"; do set -- $spec
       for st in 4 6 8 12 16; do
         [ $((${3} % st)) -ne 0 ] && continue
-        python bench.py --workload $1 --batch $2 --streams $st --steps $3 --warmup $st --no-cpu-baseline --no-extras 2>/dev/null | line "$1 b$2 lanes $st:"
+        python bench.py --full --workload $1 --batch $2 --streams $st --steps $3 --warmup $st --no-cpu-baseline --no-extras 2>/dev/null | line "$1 b$2 lanes $st:"
       done
     done | tee $O/decrypt_lanes.txt
     ;;
   bench_queues)
     # the whole default bench (all legs in one process) with 16 / 24 / 32 hardware queues
     for q in 16 24 32; do
-      python bench.py --steps 20 --warmup 5 --hw-queues $q --cpu-seconds 1 > $O/bench_q$q.json 2> $O/bench_q$q.err; cp bench_extras.json $O/bench_q${q}_extras.json
+      python bench.py --full --steps 20 --warmup 5 --hw-queues $q --cpu-seconds 1 > $O/bench_q$q.json 2> $O/bench_q$q.err; cp bench_extras.json $O/bench_q${q}_extras.json
       python - $O/bench_q${q}_extras.json $q <<'PY'
 import json, sys
 e = json.load(open(sys.argv[1]))

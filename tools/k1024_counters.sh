@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/$out; mkdir -p $O
 cd /tmp
 for lpl in 9 18; do
-  B="python3 $R/bench.py --workload biprime --key-length 1024 --batch 8192 --no-cpu-baseline --streams 1 --steps 3 --warmup 1 --limbs-per-lane $lpl"
+  B="python3 $R/bench.py --full --workload biprime --key-length 1024 --batch 8192 --no-cpu-baseline --streams 1 --steps 3 --warmup 1 --limbs-per-lane $lpl"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_l$lpl -- $B > $O/bench_l$lpl.json 2>/dev/null
   rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/pmc_a_l$lpl -- $B > /dev/null 2>&1
   rocprofv3 --pmc SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $O/pmc_b_l$lpl -- $B > /dev/null 2>&1
