@@ -410,6 +410,30 @@ int mx_powmod_launch_form(int mod_bits, int64_t batch, int64_t groups, int limbs
 int mx_powmod_geometry_for(int mod_bits, int64_t batch, int64_t groups, int limbs_per_lane, int* lanes_per_element,
                            int* limbs_per_lane_out, int* limb_bits, int* blocks);
 
+/* ---- homomorphic linear maps: multi-exponentiation modulo N^2 (ABI 4.4, additions) --------------------------------
+ *   d_out[r] = prod_{t < terms} d_inputs[d_index[r][t]] ^ w[r][t]  mod N^2,   w[r][t] >= 0
+ * with the modulus of a plan of mx_powmod_nsquare_prepare (its constants; the plan's exponent is not used).  Interleaved
+ * fixed-window (Straus) form on the pair arithmetic (csrc/mx_multiexp_n2.hpp): a table pass writes 2^window powers of
+ * every input into the workspace, then one group of lanes per output squares once per window bit and multiplies once
+ * per term and window.  Rows of the same launch execute the same number of terms and windows: pad with weight 0.
+ *   d_inputs: [n_inputs][limbs2] residues < N^2; NULL = the tables already in the workspace (an earlier run with the
+ *             same inputs, window and workspace on the same stream)
+ *   d_index:  [n_outputs][terms] int32 in [0, n_inputs);  d_weights: [n_outputs][terms][(weight_bits + 31) / 32] words
+ *   weight_bits <= 2 * bits(N) + 64 (weights below 2^(bits(N^2) + 64)); window 1 .. 8 (mx_multiexp_nsquare_shape).
+ * limbs_per_lane: 9 (the narrow geometry: every modulus of the pair kernel with groups of up to 32 lanes) or 0.
+ * Results are canonical residues in [0, N^2), NOT fresh ciphertexts: re-randomise before they leave the party. */
+int mx_multiexp_nsquare_shape(int n_bits, int64_t n_inputs, int64_t n_outputs, int64_t terms, int weight_bits,
+                              int limbs_per_lane, int window, int* lanes, int* limbs_per_lane_out, int* window_out,
+                              int64_t* chunk_terms);
+int64_t mx_multiexp_nsquare_workspace_bytes(int n_bits, int64_t n_inputs, int limbs_per_lane, int window);
+int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_inputs, int limbs2,
+                            const int32_t* d_index, const uint32_t* d_weights, int terms, int weight_bits,
+                            uint32_t* d_out, int64_t n_outputs, int limbs_per_lane, int window, void* d_workspace,
+                            int64_t workspace_bytes, void* stream);
+/* The kernel instances mx_multiexp_nsquare_run can select: (lanes per element, limbs per lane) pairs, at most
+ * max_entries written; returns their number. */
+int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 #include "mx_upload.hpp"
 #include "mx_powmod_n2_split.hpp"
 #include "mx_bipair.hpp"
+#include "mx_multiexp_n2.hpp"
 
 // ---- modexp modulo N^2 through pairs modulo N --------------------------------------------------
 namespace {
@@ -783,4 +784,108 @@ extern "C" int mx_powmod_nsquare(const uint32_t* d_bases, uint32_t* d_out, const
   MX_TRY(mx_powmod_nsquare_prepare(&plan, h_n, h_exp, limbs_n, exp_limbs, d_ws, pb, stream));
   return mx_powmod_nsquare_run(&plan, d_bases, d_out, limbs2, batch, 0, 0, 0,
                                (char*)d_ws + pb, ws_bytes - pb, stream);
+}
+
+// ---- multi-exponentiation modulo N^2 (mx_multiexp_n2.hpp): homomorphic linear maps of ciphertexts -----------------
+namespace mxm { int launch_multiexp(int K, bool table, const mx::MultiexpN2Args& a, int64_t nblocks, hipStream_t s); }
+namespace {
+constexpr int MX_MULTIEXP_MAX_WINDOW = 8;
+constexpr int MX_MULTIEXP_MODEL_MAX_WINDOW = 6;         // the cost model's range (the caller may ask for up to 8)
+// the narrow geometry of the pair kernel: groups of 1 .. 32 lanes
+bool multiexp_geometry(int n_bits, int limbs_per_lane, Geometry& g) {
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return false;
+  return choose_geometry(n_bits, g, LIMBS_PER_LANE) && g.K <= 32;
+}
+// Window of the interleaved fixed-window schedule, from pair products: 2^w - 2 per input to build its table (plus the two
+// of its conversion, the same for every w), ceil(bits / w) multiplications per term and output, (ceil(bits / w) - 1) w
+// squarings per output.
+int multiexp_window(int64_t n_inputs, int64_t n_outputs, int64_t terms, int weight_bits) {
+  if (weight_bits <= 1) return 1;
+  int best = 1;
+  double bestc = -1.0;
+  for (int w = 1; w <= MX_MULTIEXP_MODEL_MAX_WINDOW; ++w) {
+    const double nwin = (double)((weight_bits + w - 1) / w);
+    const double c = (double)n_inputs * (double)((1 << w) - 2) + (double)n_outputs * ((double)terms * nwin + (nwin - 1.0) * w);
+    if (bestc < 0 || c < bestc) { bestc = c; best = w; }
+  }
+  return best;
+}
+}  // namespace
+
+extern "C" int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  static const int ks[] = {1, 2, 4, 8, 16, 32};
+  const int n = (int)(sizeof(ks) / sizeof(ks[0]));
+  if (max_entries < 0 || (max_entries > 0 && (!lanes || !limbs_per_lane))) return MX_ERR_ARG;
+  for (int i = 0; i < n && i < max_entries; ++i) { lanes[i] = ks[i]; limbs_per_lane[i] = LIMBS_PER_LANE; }
+  return n;
+}
+
+extern "C" int mx_multiexp_nsquare_shape(int n_bits, int64_t n_inputs, int64_t n_outputs, int64_t terms, int weight_bits,
+                                         int limbs_per_lane, int window, int* lanes, int* limbs_per_lane_out,
+                                         int* window_out, int64_t* chunk_terms) {
+  if (!lanes || !limbs_per_lane_out || !window_out || !chunk_terms) return MX_ERR_ARG;
+  if (n_inputs < 0 || n_outputs < 0 || terms < 0 || weight_bits < 0 || window < 0 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  Geometry g;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  *lanes = g.K;
+  *limbs_per_lane_out = g.L;
+  *window_out = window > 0 ? window : multiexp_window(n_inputs, n_outputs, terms, weight_bits);
+  // split-K: outputs too few to give every SIMD of the device a wavefront have their terms cut into chunks that run on
+  // groups of their own (a second launch multiplies the partial products together)
+  const int64_t target = (int64_t)device_cus() * 4 * (64 / g.K);
+  int64_t chunk = terms;
+  if (n_outputs > 0 && n_outputs < target && terms > 64) {
+    chunk = (terms * n_outputs + target - 1) / target;
+    if (chunk < 64) chunk = 64;
+  }
+  *chunk_terms = chunk < 1 ? 1 : chunk;
+  return MX_OK;
+}
+
+extern "C" int64_t mx_multiexp_nsquare_workspace_bytes(int n_bits, int64_t n_inputs, int limbs_per_lane, int window) {
+  Geometry g;
+  if (n_inputs < 0 || window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  return align256((n_inputs > 0 ? n_inputs : 1) * ((int64_t)2 * g.K * g.L * 4 << window));
+}
+
+extern "C" int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_inputs, int limbs2,
+                                       const int32_t* d_index, const uint32_t* d_weights, int terms, int weight_bits,
+                                       uint32_t* d_out, int64_t n_outputs, int limbs_per_lane, int window, void* d_ws,
+                                       int64_t ws_bytes, void* stream) {
+  if (!plan || !plan->d_plan || !d_out || !d_ws || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_inputs <= 0 || n_outputs <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
+  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
+  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  const int64_t need = mx_multiexp_nsquare_workspace_bytes(bits, n_inputs, LIMBS_PER_LANE, window);
+  if (need < 0) return (int)need;
+  if (need > ws_bytes) return MX_ERR_WORKSPACE;
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  mx::MultiexpN2Args a;
+  a.inputs = d_inputs;
+  a.tables = (u32*)d_ws;
+  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.index = d_index;
+  a.weights = d_weights;
+  a.out = d_out;
+  a.n_inputs = n_inputs; a.rows = n_outputs;
+  a.terms = terms;
+  a.wwords = (weight_bits + 31) / 32;
+  a.window = window;
+  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  const int gpw = 64 / g.K;
+  MxKernelTimer timer(s);
+  // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
+  if (d_inputs) MX_TRY(mxm::launch_multiexp(g.K, true, a, (n_inputs + gpw - 1) / gpw, s));
+  return mxm::launch_multiexp(g.K, false, a, (n_outputs + gpw - 1) / gpw, s);
 }

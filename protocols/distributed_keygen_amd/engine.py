@@ -15,6 +15,7 @@ Engine without a GPU or without the built library raises.
 
 from __future__ import annotations
 
+import ctypes as _ctypes
 from collections import OrderedDict
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -963,6 +964,74 @@ class Engine:
         return [vals[g * gsize : g * gsize + len(bases[g])] for g in range(groups)]
 
 
+    # ------------------------------------------------------------------ homomorphic linear maps modulo N^2
+    def multiexp_nsquare_shape(self, n: int, n_inputs: int, n_outputs: int, terms: int, weight_bits: int,
+                               window: int = 0) -> Tuple[int, int, int]:
+        """(window, split-K chunk in terms, table bytes per input and entry) of mx_multiexp_nsquare_shape."""
+        k, l, w = _ctypes_ints(3)
+        chunk = _ctypes.c_int64()
+        _lib.check(self.lib.mx_multiexp_nsquare_shape(int(n).bit_length(), n_inputs, n_outputs, terms, weight_bits, 0, int(window),
+                                                      k, l, w, chunk), "mx_multiexp_nsquare_shape")
+        return w.value, int(chunk.value), 2 * k.value * l.value * 4
+
+    def multiexp_nsquare_t(self, inputs_t, weights, n: int, bias: Optional[Sequence[int]] = None, window: int = 0):
+        """y_j = (1 + (b_j mod n) n) * prod_i inputs[i]^W[j][i]  mod n^2 on the device (csrc/mx_multiexp_n2.hpp).
+
+        ``inputs_t``: ``[n_inputs, limbs2]`` rows of residues below n^2; ``weights``: one row per output, a dense sequence
+        of ``n_inputs`` signed ints or a sparse ``{input: weight}``; ``bias``: one plaintext per output or None.  A negative
+        weight uses the input's inverse (computed once on the device; ValueError like ``pow`` if it has none), a zero
+        weight gives 1 even for a zero input.  ``window`` > 0 overrides the library's window.  Returns ``[n_outputs,
+        limbs2]`` canonical residues — not fresh ciphertexts (re-randomise before they leave the party).  The planning
+        (sign split, bias, split-K, buckets, stages) is multiexp_plan.py."""
+        from . import multiexp_plan as mp
+
+        n = int(n)
+        _check_modulus(n)
+        n_inputs, limbs2 = inputs_t.shape
+        if _limbs.limbs_for(n * n) > limbs2:
+            raise ValueError("rows narrower than N^2")
+        nb = n.bit_length()
+        plan = mp.plan_call(weights, n_inputs, n, bias, lambda a, b, c, d: self.multiexp_nsquare_shape(n, a, b, c, d),
+                            window=int(window))
+        return mp.execute(plan, _MultiexpBackend(self, n, limbs2, nb), inputs_t)
+
+    def _linear_map_ints(self, cts: Sequence[int], weights, n: int, bias=None) -> List[int]:
+        if not weights:
+            return []
+        _check_modulus(n)
+        n2 = n * n
+        limbs2 = _limbs.limbs_for(n2)
+        if not len(cts):
+            from . import multiexp_plan as mp
+
+            mp.normalize_rows(weights, 0, n)          # (a map of no inputs: every row must be empty)
+        vals = list(cts) if len(cts) else [0]
+        x_t = self.to_device(_limbs.pack_reduced(vals, limbs2, n2))
+        return _limbs.unpack(self.to_host(self.multiexp_nsquare_t(x_t, weights, n, bias)))
+
+    @_int_args
+    def ciphertext_scale_batch(self, cts: Sequence[int], scalars: Sequence[int], n: int) -> List[int]:
+        """[pow(c, k, n^2) for c, k in zip(cts, scalars)] — ``ciphertext *= k`` with a scalar per ciphertext (any sign)."""
+        if len(cts) != len(scalars):
+            raise ValueError("one scalar per ciphertext")
+        return self._linear_map_ints(cts, [{k: s} for k, s in enumerate(scalars)], n)
+
+    @_int_args
+    def ciphertext_sum_batch(self, groups: Sequence[Sequence[int]], n: int) -> List[int]:
+        """[prod(g) mod n^2 for g in groups] — the homomorphic sum of every group (an empty group gives 1)."""
+        flat: List[int] = []
+        rows = []
+        for g in groups:
+            g = list(g)
+            rows.append({len(flat) + t: 1 for t in range(len(g))})
+            flat.extend(g)
+        return self._linear_map_ints(flat, rows, n)
+
+    @_int_args
+    def ciphertext_linear_map_batch(self, cts: Sequence[int], weights, n: int, bias: Optional[Sequence[int]] = None) -> List[int]:
+        """The encrypted W x + b: [(1 + (b_j mod n) n) prod_i cts[i]^W[j][i] mod n^2 for j] (rows dense or {index: weight})."""
+        return self._linear_map_ints(cts, list(weights), n, bias)
+
     # ------------------------------------------------------------------ modular multiplication / inversion / encryption
     @_int_args
     def mulmod_t(self, a_t, b_t, mod: int, out_t=None):
@@ -1511,6 +1580,88 @@ class Engine:
         pass_t = self.biprime_verdict_t(self.to_device(rows), list(mods))
         arr = pass_t.cpu().numpy().astype(bool)
         return [list(map(bool, arr[g])) for g in range(groups)]
+
+
+def _ctypes_ints(k: int):
+    return tuple(_ctypes.c_int() for _ in range(k))
+
+
+class _MultiexpBackend:
+    """multiexp_plan.execute over device rows of one Engine and modulus."""
+
+    def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
+        self.eng, self.n, self.limbs2, self.n_bits = eng, n, limbs2, n_bits
+        self.torch = eng.torch
+        self.plan = eng.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+
+    def _index(self, positions):
+        return self.torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.eng.device)
+
+    def take(self, rows_t, positions):
+        return rows_t.index_select(0, self._index(positions)).contiguous()
+
+    def invert(self, rows_t):
+        return self.eng.modinv_t(rows_t, self.n * self.n)
+
+    def bias_rows(self, residues):
+        return self.eng.to_device(_limbs.pack_reduced([1 + b * self.n for b in residues], self.limbs2, self.n * self.n))
+
+    def gather(self, inputs_t, inv_t, bias_t, parts):
+        pools = [inputs_t] + [t for t in (inv_t, bias_t) if t is not None]
+        base = {"x": 0}
+        off = inputs_t.shape[0]
+        if inv_t is not None:
+            base["inv"] = off
+            off += inv_t.shape[0]
+        if bias_t is not None:
+            base["bias"] = off
+        pool = self.torch.cat(pools, dim=0) if len(pools) > 1 else inputs_t
+        return self.take(pool, [base[kind] + k for kind, k in parts])
+
+    def run(self, tables_t, n_tables, launch, window):
+        eng, torch = self.eng, self.torch
+        rows, terms = launch.index.shape
+        out_t = torch.empty((rows, self.limbs2), dtype=torch.int32, device=eng.device)
+        idx_t = eng.to_device(launch.index.view(np.uint32))
+        w_t = eng.to_device(launch.weights.reshape(rows, -1))
+        with torch.cuda.device(eng.device):
+            eng._use_plan(self.plan)
+            ws = eng._workspace(eng.lib.mx_multiexp_nsquare_workspace_bytes(self.n_bits, n_tables, 0, window))
+            rc = eng.lib.mx_multiexp_nsquare_run(
+                self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_tables, self.limbs2,
+                idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, out_t.data_ptr(), rows, 0, window,
+                ws.data_ptr(), ws.numel(), eng._stream_ptr())
+        _lib.check(rc, "mx_multiexp_nsquare_run")
+        return out_t
+
+    def _pick(self, picks, with_one: bool):
+        torch = self.torch
+        outs, first, index = [], {}, []
+        one = None
+        for pk in picks:
+            if pk is None:
+                if one is None:
+                    one = torch.zeros((1, self.limbs2), dtype=torch.int32, device=self.eng.device)
+                    one[0, 0] = 1
+                    first[id(one)] = sum(t.shape[0] for t in outs)
+                    outs.append(one)
+                index.append(first[id(one)])
+                continue
+            t, r = pk
+            if id(t) not in first:
+                first[id(t)] = sum(u.shape[0] for u in outs)
+                outs.append(t)
+            index.append(first[id(t)] + r)
+        if not index:
+            return torch.empty((0, self.limbs2), dtype=torch.int32, device=self.eng.device)
+        pool = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
+        return self.take(pool, index)
+
+    def rows_of(self, picks):
+        return self._pick(picks, False)
+
+    def assemble(self, picks):
+        return self._pick(picks, True)
 
 
 def _check_modulus(mod: int) -> None:

@@ -1,0 +1,92 @@
+"""Homomorphic operations on Paillier ciphertexts, batched on the GPU engine.
+
+With g = N + 1 a ciphertext c of m satisfies  c1 * c2 = Enc(m1 + m2),  c^k = Enc(k m)  and  (1 + b N) c = Enc(m + b)
+(mod N^2).  The reference's README shows them as ``ciphertext += 100`` and ``ciphertext *= 3``; this module applies
+them to many ciphertexts at once:
+
+  * ``scale``: c_i^(k_i) — a scalar of any sign per ciphertext;
+  * ``add`` / ``neg``: c_i * d_i and c_i^-1;
+  * ``sum_groups``: the product of every group (ragged groups, any size);
+  * ``linear_map``: the encrypted W x + b (dense rows or sparse ``{index: weight}`` rows, optional plaintext bias).
+
+Ciphertexts are ints or objects with ``get_value()`` (the reference's ``PaillierCiphertext``); for objects the modulus
+comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` is called once per distinct object.  The
+results are ints: canonical residues in [0, N^2), NOT fresh ciphertexts — re-randomise them
+(``Engine.randomize_batch``) before they leave the party.  ``engine`` is injected for tests; the default is the
+process-wide HIP engine.
+"""
+
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence
+
+
+def _engine(engine: Any) -> Any:
+    if engine is not None:
+        return engine
+    from .engine import default_engine
+
+    return default_engine()
+
+
+def _values(cts: Sequence[Any], n: Optional[int]):
+    """(ints, n): get_value() once per distinct object."""
+    cache: Dict[int, int] = {}
+    out: List[int] = []
+    for c in cts:
+        if isinstance(c, int):
+            out.append(c)
+            continue
+        key = id(c)
+        if key not in cache:
+            cache[key] = int(c.get_value())
+            if n is None:
+                n = int(c.scheme.public_key.n)
+        out.append(cache[key])
+    if n is None:
+        raise ValueError("the modulus n is needed when the ciphertexts are plain ints")
+    return out, int(n)
+
+
+def scale(cts: Sequence[Any], scalars: Sequence[int], n: Optional[int] = None, engine: Any = None) -> List[int]:
+    """[c^k mod N^2] for every (c, k) — the plaintexts multiplied by k."""
+    vals, n = _values(cts, n)
+    return _engine(engine).ciphertext_scale_batch(vals, [int(k) for k in scalars], n)
+
+
+def add(a: Sequence[Any], b: Sequence[Any], n: Optional[int] = None, engine: Any = None) -> List[int]:
+    """[c * d mod N^2] for every pair — the plaintexts added."""
+    if len(a) != len(b):
+        raise ValueError("operands must have the same length")
+    va, n = _values(list(a) + list(b), n)
+    k = len(a)
+    if k == 0:
+        return []
+    n2 = n * n
+    return _engine(engine).mulmod_batch([v % n2 for v in va[:k]], [v % n2 for v in va[k:]], n2)
+
+
+def neg(cts: Sequence[Any], n: Optional[int] = None, engine: Any = None) -> List[int]:
+    """[c^-1 mod N^2] — the plaintexts negated (ValueError, as pow, for a ciphertext without an inverse)."""
+    vals, n = _values(cts, n)
+    if not vals:
+        return []
+    return _engine(engine).modinv_batch(vals, n * n)
+
+
+def sum_groups(groups: Sequence[Sequence[Any]], n: Optional[int] = None, engine: Any = None) -> List[int]:
+    """[prod(g) mod N^2] for every group — the sum of its plaintexts (an empty group gives 1, an encryption of 0)."""
+    groups = [list(g) for g in groups]
+    flat, n = _values([c for g in groups for c in g], n)
+    out, pos = [], 0
+    for g in groups:
+        out.append(flat[pos : pos + len(g)])
+        pos += len(g)
+    return _engine(engine).ciphertext_sum_batch(out, n)
+
+
+def linear_map(cts: Sequence[Any], weights: Sequence[Any], n: Optional[int] = None, bias: Optional[Sequence[int]] = None,
+               engine: Any = None) -> List[int]:
+    """The encrypted W x + b: [(1 + (b_j mod N) N) prod_i c_i^(W_ji) mod N^2 for every row j of W]."""
+    vals, n = _values(cts, n)
+    return _engine(engine).ciphertext_linear_map_batch(vals, list(weights), n, bias=bias)
