@@ -434,6 +434,24 @@ int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_input
  * max_entries written; returns their number. */
 int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
+ *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
+ * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of
+ * d_out[j] returns `slots` plaintexts of slot_bits bits.  Rows at index count or above count as 1 (the last output may
+ * hold fewer slots).  Horner on the pair arithmetic with the constants of a plan of mx_powmod_nsquare_prepare (its
+ * exponent is not used): (slots - 1) * slot_bits pair squarings per output (csrc/mx_pack_n2.hpp).  Enqueues only, on
+ * `stream`, no workspace; writes ceil(count / slots) rows of limbs2 words.
+ *   d_cts: [count][limbs2] residues < N^2 (any residue: 0 and multiples of N included, nothing is inverted)
+ *   MX_ERR_ARG for a null pointer, count / slots / slot_bits < 1, slot_bits * slots > bits(N) - 2 (the bound under
+ *   which a signed or unsigned packed plaintext decrypts unambiguously) or rows too narrow for N^2;
+ *   MX_ERR_SIZE outside the narrow geometry (limbs_per_lane 9 or 0, groups of up to 32 lanes).
+ * Results are canonical residues in [0, N^2), NOT fresh ciphertexts. */
+int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_cts, int64_t count, int limbs2, int slot_bits,
+                        int slots, uint32_t* d_out, int limbs_per_lane, void* stream);
+/* The kernel instances mx_pack_nsquare_run can select: (lanes per element, limbs per lane) pairs, at most max_entries
+ * written; returns their number. */
+int mx_pack_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ def configure_hw_queues(queues: int = 16) -> bool:
     return True
 
 
-from . import homomorphic, limbs  # noqa: F401
+from . import homomorphic, limbs, packing  # noqa: F401
 from .engine import Engine, default_engine  # noqa: F401
 from .operators import mod_inv, mod_inv_batch, pow_mod, pow_mod_batch, pow_mod_batch_multi  # noqa: F401
 

@@ -4,6 +4,7 @@
 #include "mx_powmod_n2_split.hpp"
 #include "mx_bipair.hpp"
 #include "mx_multiexp_n2.hpp"
+#include "mx_pack_n2.hpp"
 
 // ---- modexp modulo N^2 through pairs modulo N --------------------------------------------------
 namespace {
@@ -888,4 +889,36 @@ extern "C" int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32
   // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
   if (d_inputs) MX_TRY(mxm::launch_multiexp(g.K, true, a, (n_inputs + gpw - 1) / gpw, s));
   return mxm::launch_multiexp(g.K, false, a, (n_outputs + gpw - 1) / gpw, s);
+}
+
+// ---- packing modulo N^2 (mx_pack_n2.hpp): many small plaintexts per ciphertext ---------------------------------------
+namespace mxp { int launch_pack(int K, const mx::PackN2Args& a, int64_t nblocks, hipStream_t s); }
+
+extern "C" int mx_pack_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_cts, int64_t count, int limbs2,
+                                   int slot_bits, int slots, uint32_t* d_out, int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_cts || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (count < 1 || slots < 1 || slot_bits < 1 || limbs2 <= 0 || limbs_per_lane < 0) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if ((int64_t)slot_bits * slots > bits - 2) return MX_ERR_ARG;     // a packed plaintext must decrypt unambiguously
+  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  mx::PackN2Args a;
+  a.cts = d_cts;
+  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.out = d_out;
+  a.count = count;
+  a.outputs = (count + slots - 1) / slots;
+  a.slots = slots; a.slot_bits = slot_bits;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  const int gpw = 64 / g.K;
+  MxKernelTimer timer(s);
+  return mxp::launch_pack(g.K, a, (a.outputs + gpw - 1) / gpw, s);
 }

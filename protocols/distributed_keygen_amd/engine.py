@@ -1032,6 +1032,47 @@ class Engine:
         """The encrypted W x + b: [(1 + (b_j mod n) n) prod_i cts[i]^W[j][i] mod n^2 for j] (rows dense or {index: weight})."""
         return self._linear_map_ints(cts, list(weights), n, bias)
 
+    # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
+    def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
+        """out[j] = prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 on the device (csrc/mx_pack_n2.hpp):
+        one ciphertext of sum_i m_i 2^(slot_bits i) per ``slots`` inputs, the last one holding the rest.
+
+        ``cts_t``: ``[count, limbs2]`` rows of residues below n^2; returns ``[ceil(count / slots), limbs2]`` canonical
+        residues — not fresh ciphertexts.  ``slot_bits * slots`` must not exceed bits(n) - 2 (ValueError); the slot
+        layout of a protocol is packing.py's."""
+        n, slot_bits, slots = int(n), int(slot_bits), int(slots)
+        _check_modulus(n)
+        count, limbs2 = cts_t.shape
+        if _limbs.limbs_for(n * n) > limbs2:
+            raise ValueError("rows narrower than N^2")
+        if slot_bits < 1 or slots < 1 or slot_bits * slots > n.bit_length() - 2:
+            raise ValueError(f"{slots} slots of {slot_bits} bits do not fit a plaintext of {n.bit_length()} bits")
+        torch = self.torch
+        out_t = torch.empty((-(-count // slots), limbs2), dtype=torch.int32, device=self.device)
+        if count == 0:
+            return out_t
+        cts_t = cts_t.contiguous()
+        plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+        with torch.cuda.device(self.device):
+            self._use_plan(plan)
+            rc = self.lib.mx_pack_nsquare_run(plan.desc, cts_t.data_ptr(), count, limbs2, slot_bits, slots, out_t.data_ptr(),
+                                              0, self._stream_ptr())
+        _lib.check(rc, "mx_pack_nsquare_run")
+        return out_t
+
+    @_int_args
+    def ciphertext_pack_batch(self, cts: Sequence[int], n: int, slot_bits: int, slots: int) -> List[int]:
+        """[prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 for j < ceil(len(cts) / slots)]
+        (pack_nsquare_t).  Inputs are reduced modulo n^2; any residue is valid, 0 and multiples of n included (nothing
+        is inverted)."""
+        _check_modulus(n)
+        if not len(cts):
+            return []
+        n2 = n * n
+        limbs2 = _limbs.limbs_for(n2)
+        x_t = self.to_device(_limbs.pack_reduced(cts if isinstance(cts, list) else list(cts), limbs2, n2))
+        return _limbs.unpack(self.to_host(self.pack_nsquare_t(x_t, n, slot_bits, slots)))
+
     # ------------------------------------------------------------------ modular multiplication / inversion / encryption
     @_int_args
     def mulmod_t(self, a_t, b_t, mod: int, out_t=None):
