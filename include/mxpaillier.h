@@ -452,6 +452,41 @@ int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_cts, int6
  * written; returns their number. */
 int mx_pack_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- fixed-base exponentiation: encryption and re-randomisation (ABI 4.4, additions) -------------------------------
+ *   d_out[r] = f_r * g^(e_r)  mod N^2,   r < count,   ONE base g per table, exponents e_r < 2^exp_bits
+ * with the constants of a plan of mx_powmod_nsquare_prepare (its exponent is not used).  mx_fixedbase_nsquare_prepare
+ * tabulates g^(d 2^(window i)) for every window i < ceil(exp_bits / window) and digit d < 2^window in pair form
+ * (csrc/mx_fixedbase_n2.hpp: a chain of exp_bits squarings on one group, then every further entry on a group of its
+ * own) into caller-owned device memory; mx_fixedbase_nsquare_run then costs ceil(exp_bits / window) pair products per
+ * output and NO squaring.  A table serves any number of runs, on any stream ordered after the prepare.
+ *   mode MX_FIXEDBASE_POWER      f_r = 1                        d_operand NULL
+ *        MX_FIXEDBASE_ENCRYPT    f_r = 1 + m_r N                d_operand [count][operand_limbs] messages m_r < N
+ *        MX_FIXEDBASE_RANDOMIZE  f_r = c_r                      d_operand [count][operand_limbs] residues c_r < N^2
+ *   d_base:  [limbs2] any residue < N^2 (0 and multiples of N included: nothing is inverted)
+ *   d_exps:  [count][(exp_bits + 31) / 32] little-endian words; bits at exp_bits and above are ignored
+ *   exp_bits 1 .. 2 * bits(N) + 64; window 1 .. 8 (mx_fixedbase_nsquare_shape: the window that minimises the run's
+ *   products for `count` outputs plus a sixteenth of the table pass — a table is built once per key and serves many
+ *   calls — among the tables of at most table_budget_bytes, 0 = 256 MiB; an explicit window is taken as given;
+ *   *windows = ceil(exp_bits / *window)).
+ *   MX_ERR_ARG for a null pointer, count < 1, exp_bits or window out of range, a table buffer smaller than
+ *   mx_fixedbase_nsquare_table_bytes, a missing operand, rows too narrow for N^2 (for N: ENCRYPT's operand);
+ *   MX_ERR_SIZE outside the narrow geometry (limbs_per_lane 9 or 0, groups of up to 32 lanes).  A refused call launches
+ *   nothing.  Enqueue only, on `stream`, no workspace.  Results are canonical residues in [0, N^2). */
+#define MX_FIXEDBASE_POWER 0
+#define MX_FIXEDBASE_ENCRYPT 1
+#define MX_FIXEDBASE_RANDOMIZE 2
+int mx_fixedbase_nsquare_shape(int n_bits, int exp_bits, int64_t count, int64_t table_budget_bytes, int limbs_per_lane,
+                               int window, int* lanes, int* limbs_per_lane_out, int* window_out, int* windows);
+int64_t mx_fixedbase_nsquare_table_bytes(int n_bits, int exp_bits, int limbs_per_lane, int window);
+int mx_fixedbase_nsquare_prepare(const mx_nsquare_plan* plan, const uint32_t* d_base, int limbs2, int exp_bits,
+                                 int limbs_per_lane, int window, void* d_table, int64_t table_bytes, void* stream);
+int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void* d_table, int exp_bits, int window, int mode,
+                             const uint32_t* d_exps, const uint32_t* d_operand, int operand_limbs, uint32_t* d_out,
+                             int64_t count, int limbs2, int limbs_per_lane, void* stream);
+/* The kernel instances the fixed-base entries can select: (lanes per element, limbs per lane) pairs, at most
+ * max_entries written; returns their number. */
+int mx_fixedbase_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 #ifdef __cplusplus
 }
 #endif

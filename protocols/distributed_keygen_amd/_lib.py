@@ -34,6 +34,7 @@ class CombinePlan(ctypes.Structure):
 
 
 MX_PLAN_FIXED_WINDOW = 1      # include/mxpaillier.h
+MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
 
 _P4 = [POINTER(c_int)] * 4
 
@@ -101,6 +102,11 @@ SYMBOLS = {
     "mx_multiexp_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_fixedbase_nsquare_shape": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, *_P4]),
+    "mx_fixedbase_nsquare_table_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "mx_fixedbase_nsquare_prepare": (c_int, [POINTER(NsquarePlan), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_fixedbase_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "mx_fixedbase_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
 }
 
 

@@ -1,10 +1,12 @@
 // extern "C" entry points of the N^2-modulus modexp (second translation unit of libmxpaillier.so:
 // compiled in parallel with mx_capi.hip, the pair kernels are the most expensive to build).
+#include <cmath>
 #include "mx_upload.hpp"
 #include "mx_powmod_n2_split.hpp"
 #include "mx_bipair.hpp"
 #include "mx_multiexp_n2.hpp"
 #include "mx_pack_n2.hpp"
+#include "mx_fixedbase_n2.hpp"
 
 // ---- modexp modulo N^2 through pairs modulo N --------------------------------------------------
 namespace {
@@ -921,4 +923,133 @@ extern "C" int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
   const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
   return mxp::launch_pack(g.K, a, (a.outputs + gpw - 1) / gpw, s);
+}
+
+// ---- fixed-base exponentiation modulo N^2 (mx_fixedbase_n2.hpp): encryption and re-randomisation ------------------------
+namespace mxf { int launch_fixedbase(int K, int pass, const mx::FixedBaseN2Args& a, int64_t nblocks, hipStream_t s); }
+namespace {
+constexpr int MX_FIXEDBASE_MAX_WINDOW = 8;
+constexpr int64_t MX_FIXEDBASE_TABLE_BUDGET = (int64_t)256 << 20;      // default budget of the window model
+constexpr double MX_FIXEDBASE_TABLE_USES = 16.0;                       // calls a table is expected to serve (it is cached per key)
+int64_t fixedbase_table_bytes(const Geometry& g, int exp_bits, int window) {
+  const int64_t windows = (exp_bits + window - 1) / window;
+  return align256(windows * ((int64_t)2 * g.K * g.L * 4 << window));
+}
+// Window of the fixed-base schedule, in pair products ONE GROUP executes one after the other.  Both passes spread over
+// the machine, so what a pass costs is its products per group times the rounds of groups it needs (two wavefronts per
+// SIMD resident): ceil(exp_bits / w) per round of outputs; for the table, built once, exp_bits squarings of the chain (the
+// same for every w) plus 2 (w - 1) products per round of entries from digit 2 on.  (A first model summed the table's
+// products as if one group built them all and chose w = 5 / 7 for 10^3 / 10^4 outputs, where w = 8 measured 1.6x / 1.15x
+// faster and every table of a key took the same 8-9 ms.)  The table is kept per key, so a call is charged
+// 1 / MX_FIXEDBASE_TABLE_USES of its pass: charged in full to one call of 10^3 outputs at key_length 4096 the model
+// chose w = 7 (5.53 ms a call) where w = 8 takes 4.90 ms a call and 2 ms longer to build, once
+// (profiles/r09_fixed_base_probe.txt).
+int fixedbase_window(const Geometry& g, int exp_bits, int64_t count, int64_t budget) {
+  const double resident = (double)device_cus() * 4 * 2 * (64 / g.K);
+  auto rounds = [&](double groups) { return std::ceil(groups / resident); };
+  int best = 1;
+  double bestc = -1.0;
+  for (int w = 1; w <= MX_FIXEDBASE_MAX_WINDOW; ++w) {
+    if (w > 1 && fixedbase_table_bytes(g, exp_bits, w) > budget) break;
+    const double nwin = (double)((exp_bits + w - 1) / w);
+    const double table = (double)exp_bits + rounds(nwin * (double)((1 << w) - 2)) * 2.0 * (w - 1);
+    const double c = rounds((double)count) * nwin + table / MX_FIXEDBASE_TABLE_USES;
+    if (bestc < 0 || c < bestc) { bestc = c; best = w; }
+  }
+  return best;
+}
+bool fixedbase_args_ok(int bits, int exp_bits, int window) {
+  return exp_bits >= 1 && exp_bits <= 2 * bits + 64 && window >= 1 && window <= MX_FIXEDBASE_MAX_WINDOW;
+}
+}  // namespace
+
+extern "C" int mx_fixedbase_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int mx_fixedbase_nsquare_shape(int n_bits, int exp_bits, int64_t count, int64_t table_budget_bytes,
+                                          int limbs_per_lane, int window, int* lanes, int* limbs_per_lane_out,
+                                          int* window_out, int* windows_out) {
+  if (!lanes || !limbs_per_lane_out || !window_out || !windows_out) return MX_ERR_ARG;
+  if (count < 1 || table_budget_bytes < 0 || window < 0 || limbs_per_lane < 0) return MX_ERR_ARG;
+  if (!fixedbase_args_ok(n_bits, exp_bits, window ? window : 1)) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  const int w = window > 0 ? window
+                           : fixedbase_window(g, exp_bits, count, table_budget_bytes ? table_budget_bytes : MX_FIXEDBASE_TABLE_BUDGET);
+  *lanes = g.K;
+  *limbs_per_lane_out = g.L;
+  *window_out = w;
+  *windows_out = (exp_bits + w - 1) / w;
+  return MX_OK;
+}
+
+extern "C" int64_t mx_fixedbase_nsquare_table_bytes(int n_bits, int exp_bits, int limbs_per_lane, int window) {
+  if (!fixedbase_args_ok(n_bits, exp_bits, window)) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  return fixedbase_table_bytes(g, exp_bits, window);
+}
+
+extern "C" int mx_fixedbase_nsquare_prepare(const mx_nsquare_plan* plan, const uint32_t* d_base, int limbs2, int exp_bits,
+                                            int limbs_per_lane, int window, void* d_table, int64_t table_bytes,
+                                            void* stream) {
+  if (!plan || !plan->d_plan || !d_base || !d_table || plan->limbs_n <= 0 || limbs2 <= 0 || limbs_per_lane < 0) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if (!fixedbase_args_ok(bits, exp_bits, window)) return MX_ERR_ARG;
+  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  if (table_bytes < fixedbase_table_bytes(g, exp_bits, window)) return MX_ERR_ARG;
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  mx::FixedBaseN2Args a{};
+  a.base = d_base;
+  a.table = (u32*)d_table;
+  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.exp_bits = exp_bits; a.window = window; a.windows = (exp_bits + window - 1) / window;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  const int gpw = 64 / g.K;
+  MxKernelTimer timer(s);
+  MX_TRY(mxf::launch_fixedbase(g.K, 0, a, 1, s));
+  const int64_t fill = (int64_t)a.windows * ((1 << window) - 2);
+  if (fill > 0) return mxf::launch_fixedbase(g.K, 1, a, (fill + gpw - 1) / gpw, s);
+  return MX_OK;
+}
+
+extern "C" int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void* d_table, int exp_bits, int window, int mode,
+                                        const uint32_t* d_exps, const uint32_t* d_operand, int operand_limbs,
+                                        uint32_t* d_out, int64_t count, int limbs2, int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_table || !d_exps || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (count < 1 || limbs2 <= 0 || limbs_per_lane < 0) return MX_ERR_ARG;
+  if (mode != mx::FIXEDBASE_POWER && mode != mx::FIXEDBASE_ENCRYPT && mode != mx::FIXEDBASE_RANDOMIZE) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if (!fixedbase_args_ok(bits, exp_bits, window)) return MX_ERR_ARG;
+  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
+  if (mode != mx::FIXEDBASE_POWER) {
+    if (!d_operand || operand_limbs <= 0) return MX_ERR_ARG;
+    const int64_t need = mode == mx::FIXEDBASE_ENCRYPT ? bits : 2 * bits;
+    if (32 * (int64_t)operand_limbs < need) return MX_ERR_ARG;       // rows too narrow for N (ENCRYPT) or N^2
+  }
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  if (mode != mx::FIXEDBASE_POWER && 2 * g.K * g.L + 8 < operand_limbs + 2) return MX_ERR_ARG;
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  mx::FixedBaseN2Args a{};
+  a.table = (u32*)d_table;
+  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.exps = d_exps;
+  a.operand = d_operand;
+  a.out = d_out;
+  a.count = count;
+  a.exp_bits = exp_bits; a.ewords = (exp_bits + 31) / 32; a.window = window; a.windows = (exp_bits + window - 1) / window;
+  a.mode = mode; a.oplimbs = mode == mx::FIXEDBASE_POWER ? 0 : operand_limbs;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  const int gpw = 64 / g.K;
+  MxKernelTimer timer(s);
+  return mxf::launch_fixedbase(g.K, 2, a, (count + gpw - 1) / gpw, s);
 }

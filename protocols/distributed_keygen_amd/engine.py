@@ -65,6 +65,17 @@ class _Plan:
         self.desc, self.block, self.stream_ptr, self.ready = desc, block, stream_ptr, ready
 
 
+class FixedBaseTable(_Plan):
+    """Handle of a fixed-base table (Engine.fixed_base_table): the device block of mx_fixedbase_nsquare_prepare with
+    what a launch needs to read it.  ``desc`` is the N^2 plan whose constants the table was built with (kept alive here)."""
+
+    __slots__ = ("n", "base", "exp_bits", "window", "windows", "nbytes", "plan")
+
+    def __init__(self, plan, block, stream_ptr, ready, n, base, exp_bits, window, windows, nbytes) -> None:
+        super().__init__(plan.desc, block, stream_ptr, ready)
+        self.plan, self.n, self.base, self.exp_bits, self.window, self.windows, self.nbytes = plan, n, base, exp_bits, window, windows, nbytes
+
+
 class _ModulusRows:
     """Moduli of a key-generation round kept on the device between its steps (survivors of the sieve, in order):
     device rows of the width they were produced in, and the largest bit length."""
@@ -148,6 +159,7 @@ class Engine:
         self._fixed_window = False             # tapes of new N^2 plans: fixed windows (secret-independent schedule) instead of sliding ones
         self._n2_plans: "OrderedDict[Tuple[int, int, bool], _Plan]" = OrderedDict()
         self._combine_plans: "OrderedDict[Tuple[int, int, int], _Plan]" = OrderedDict()
+        self._fixed_base_tables: "OrderedDict[Tuple[int, int, int, int], FixedBaseTable]" = OrderedDict()
         self._side_streams: List[Any] = []     # chunked int-level batches (_pipelined): streams verified concurrent
         self._side_streams_capped = False      # the process has fewer concurrent queues than chunks were wanted
         self._pin: Dict[str, Any] = {}         # pinned staging buffers of _pipelined
@@ -995,7 +1007,7 @@ class Engine:
                             window=int(window))
         return mp.execute(plan, _MultiexpBackend(self, n, limbs2, nb), inputs_t)
 
-    def _linear_map_ints(self, cts: Sequence[int], weights, n: int, bias=None) -> List[int]:
+    def _linear_map_ints(self, cts: Sequence[int], weights, n: int, bias=None, fixed_base=None) -> List[int]:
         if not weights:
             return []
         _check_modulus(n)
@@ -1007,17 +1019,18 @@ class Engine:
             mp.normalize_rows(weights, 0, n)          # (a map of no inputs: every row must be empty)
         vals = list(cts) if len(cts) else [0]
         x_t = self.to_device(_limbs.pack_reduced(vals, limbs2, n2))
-        return _limbs.unpack(self.to_host(self.multiexp_nsquare_t(x_t, weights, n, bias)))
+        return _limbs.unpack(self.to_host(self._freshened(self.multiexp_nsquare_t(x_t, weights, n, bias), fixed_base)))
 
     @_int_args
-    def ciphertext_scale_batch(self, cts: Sequence[int], scalars: Sequence[int], n: int) -> List[int]:
-        """[pow(c, k, n^2) for c, k in zip(cts, scalars)] — ``ciphertext *= k`` with a scalar per ciphertext (any sign)."""
+    def ciphertext_scale_batch(self, cts: Sequence[int], scalars: Sequence[int], n: int, fixed_base=None) -> List[int]:
+        """[pow(c, k, n^2) for c, k in zip(cts, scalars)] — ``ciphertext *= k`` with a scalar per ciphertext (any sign).
+        ``fixed_base`` (here and in the functions below): see _freshened."""
         if len(cts) != len(scalars):
             raise ValueError("one scalar per ciphertext")
-        return self._linear_map_ints(cts, [{k: s} for k, s in enumerate(scalars)], n)
+        return self._linear_map_ints(cts, [{k: s} for k, s in enumerate(scalars)], n, fixed_base=fixed_base)
 
     @_int_args
-    def ciphertext_sum_batch(self, groups: Sequence[Sequence[int]], n: int) -> List[int]:
+    def ciphertext_sum_batch(self, groups: Sequence[Sequence[int]], n: int, fixed_base=None) -> List[int]:
         """[prod(g) mod n^2 for g in groups] — the homomorphic sum of every group (an empty group gives 1)."""
         flat: List[int] = []
         rows = []
@@ -1025,12 +1038,13 @@ class Engine:
             g = list(g)
             rows.append({len(flat) + t: 1 for t in range(len(g))})
             flat.extend(g)
-        return self._linear_map_ints(flat, rows, n)
+        return self._linear_map_ints(flat, rows, n, fixed_base=fixed_base)
 
     @_int_args
-    def ciphertext_linear_map_batch(self, cts: Sequence[int], weights, n: int, bias: Optional[Sequence[int]] = None) -> List[int]:
+    def ciphertext_linear_map_batch(self, cts: Sequence[int], weights, n: int, bias: Optional[Sequence[int]] = None,
+                                    fixed_base=None) -> List[int]:
         """The encrypted W x + b: [(1 + (b_j mod n) n) prod_i cts[i]^W[j][i] mod n^2 for j] (rows dense or {index: weight})."""
-        return self._linear_map_ints(cts, list(weights), n, bias)
+        return self._linear_map_ints(cts, list(weights), n, bias, fixed_base=fixed_base)
 
     # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
     def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
@@ -1061,7 +1075,7 @@ class Engine:
         return out_t
 
     @_int_args
-    def ciphertext_pack_batch(self, cts: Sequence[int], n: int, slot_bits: int, slots: int) -> List[int]:
+    def ciphertext_pack_batch(self, cts: Sequence[int], n: int, slot_bits: int, slots: int, fixed_base=None) -> List[int]:
         """[prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 for j < ceil(len(cts) / slots)]
         (pack_nsquare_t).  Inputs are reduced modulo n^2; any residue is valid, 0 and multiples of n included (nothing
         is inverted)."""
@@ -1071,7 +1085,150 @@ class Engine:
         n2 = n * n
         limbs2 = _limbs.limbs_for(n2)
         x_t = self.to_device(_limbs.pack_reduced(cts if isinstance(cts, list) else list(cts), limbs2, n2))
-        return _limbs.unpack(self.to_host(self.pack_nsquare_t(x_t, n, slot_bits, slots)))
+        return _limbs.unpack(self.to_host(self._freshened(self.pack_nsquare_t(x_t, n, slot_bits, slots), fixed_base)))
+
+    # ------------------------------------------------------------------ fixed base: encryption and re-randomisation
+    def fixed_base_shape(self, n: int, exp_bits: int, count: int, window: int = 0, table_budget_bytes: int = 0) -> Tuple[int, int, int]:
+        """(window, windows, table bytes) of mx_fixedbase_nsquare_shape for `count` outputs per call."""
+        k, l, w, nw = _ctypes_ints(4)
+        nb = int(n).bit_length()
+        _lib.check(self.lib.mx_fixedbase_nsquare_shape(nb, int(exp_bits), int(count), int(table_budget_bytes), 0, int(window),
+                                                       k, l, w, nw), "mx_fixedbase_nsquare_shape")
+        nbytes = _lib.check(self.lib.mx_fixedbase_nsquare_table_bytes(nb, int(exp_bits), 0, w.value), "mx_fixedbase_nsquare_table_bytes")
+        return w.value, nw.value, int(nbytes)
+
+    FIXED_BASE_MODEL_COUNT = 100000      # outputs per call the automatic window is chosen for (the table is per key)
+
+    @_int_args
+    def fixed_base_table(self, n: int, base: int, exp_bits: int, window: int = 0) -> FixedBaseTable:
+        """The table of ``base^(d 2^(w i)) mod n^2`` (csrc/mx_fixedbase_n2.hpp) for exponents below ``2^exp_bits``,
+        built on first use and cached per (n, base, exp_bits, window) beside the N^2 plans, with _cache_plan's eviction
+        discipline.  ``window`` = 0: the library's choice for FIXED_BASE_MODEL_COUNT outputs per call.  ``base`` is
+        reduced modulo n^2; any residue is valid."""
+        key = (n, base, exp_bits, window)
+        tab = self._fixed_base_tables.get(key)
+        if tab is not None:
+            self._fixed_base_tables.move_to_end(key)
+            return tab
+        _check_modulus(n)
+        if exp_bits < 1 or exp_bits > 2 * n.bit_length() + 64:
+            raise ValueError(f"exp_bits must lie in 1 .. 2 bits(n) + 64 = {2 * n.bit_length() + 64}")
+        if not 0 <= window <= 8:
+            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
+        n2 = n * n
+        limbs2 = _limbs.limbs_for(n2)
+        w, windows, nbytes = self.fixed_base_shape(n, exp_bits, self.FIXED_BASE_MODEL_COUNT, window)
+        plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            self._use_plan(plan)
+            base_t = self.to_device(_limbs.pack_reduced([base], limbs2, n2))
+            block = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            rc = self.lib.mx_fixedbase_nsquare_prepare(plan.desc, base_t.data_ptr(), limbs2, exp_bits, 0, w,
+                                                       block.data_ptr(), nbytes, self._stream_ptr())
+            _lib.check(rc, "mx_fixedbase_nsquare_prepare")
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(self.device))
+        tab = FixedBaseTable(plan, block, self._stream_ptr(), ready, n, base % n2, exp_bits, w, windows, nbytes)
+        return self._cache_plan(self._fixed_base_tables, key, tab)
+
+    def _freshened(self, rows_t, fixed_base):
+        """``rows_t`` (ciphertext rows modulo n^2, on the device) re-randomised there before they are fetched:
+        ``fixed_base`` = (n, base, exp_bits, window, exponents) multiplies row r by base^(e_r) mod n^2 through the
+        table of fixed_base_table (exponents as fixed_base_exponent_rows takes them); None returns the rows as they are."""
+        if fixed_base is None:
+            return rows_t
+        n, base, exp_bits, window, exps = fixed_base
+        table = self.fixed_base_table(n, base, exp_bits, window)
+        if rows_t.shape[1] != _limbs.limbs_for(table.n * table.n):
+            raise ValueError("the rows are not residues modulo the randomiser's N^2")
+        return self.fixed_base_randomize_t(table, self.fixed_base_exponent_rows(exps, exp_bits), rows_t)
+
+    def _fixed_base_run(self, table: FixedBaseTable, mode: int, exps_t, operand_t):
+        torch = self.torch
+        count, ewords = exps_t.shape
+        if ewords != (table.exp_bits + 31) // 32:
+            raise ValueError(f"exponent rows of {(table.exp_bits + 31) // 32} words expected for {table.exp_bits} bits")
+        limbs2 = _limbs.limbs_for(table.n * table.n)
+        op_limbs = 0
+        if operand_t is not None:
+            if operand_t.shape[0] != count:
+                raise ValueError("one operand row per exponent row expected")
+            op_limbs = operand_t.shape[1]
+            need = _limbs.limbs_for(table.n) if mode == _lib.MX_FIXEDBASE_ENCRYPT else limbs2
+            if op_limbs < need:
+                raise ValueError("operand rows narrower than N" if mode == _lib.MX_FIXEDBASE_ENCRYPT else "rows narrower than N^2")
+            operand_t = operand_t.contiguous()
+        out_t = torch.empty((count, limbs2), dtype=torch.int32, device=self.device)
+        if count == 0:
+            return out_t
+        exps_t = exps_t.contiguous()
+        with torch.cuda.device(self.device):
+            self._use_plan(table.plan)
+            self._use_plan(table)
+            rc = self.lib.mx_fixedbase_nsquare_run(table.desc, table.block.data_ptr(), table.exp_bits, table.window, mode,
+                                                   exps_t.data_ptr(), operand_t.data_ptr() if operand_t is not None else None,
+                                                   op_limbs, out_t.data_ptr(), count, limbs2, 0, self._stream_ptr())
+        _lib.check(rc, "mx_fixedbase_nsquare_run")
+        return out_t
+
+    def fixed_base_power_t(self, table: FixedBaseTable, exps_t):
+        """out[r] = base^(e_r) mod n^2 — a batch of randomisers.  ``exps_t``: ``[count, ceil(exp_bits / 32)]`` little-endian
+        words on the device; bits at ``exp_bits`` and above are ignored.  No squaring: one pair product per window."""
+        return self._fixed_base_run(table, _lib.MX_FIXEDBASE_POWER, exps_t, None)
+
+    def fixed_base_encrypt_t(self, table: FixedBaseTable, exps_t, messages_t):
+        """out[r] = (1 + m_r n) * base^(e_r) mod n^2; ``messages_t``: ``[count, limbs(n)]`` (or wider) rows below n."""
+        return self._fixed_base_run(table, _lib.MX_FIXEDBASE_ENCRYPT, exps_t, messages_t)
+
+    def fixed_base_randomize_t(self, table: FixedBaseTable, exps_t, cts_t):
+        """out[r] = c_r * base^(e_r) mod n^2; ``cts_t``: ``[count, limbs(n^2)]`` rows of any residues below n^2."""
+        return self._fixed_base_run(table, _lib.MX_FIXEDBASE_RANDOMIZE, exps_t, cts_t)
+
+    def fixed_base_exponent_rows(self, exponents, exp_bits: int):
+        """Exponents -> device rows ``[count, ceil(exp_bits / 32)]``: a sequence of ints below ``2^exp_bits`` (ValueError
+        otherwise), or a uint32 numpy array of that shape taken as it is (drawn bytes; the kernel masks the top bits)."""
+        ewords = (int(exp_bits) + 31) // 32
+        if isinstance(exponents, np.ndarray):
+            if exponents.ndim != 2 or exponents.shape[1] != ewords:
+                raise ValueError(f"exponent rows of {ewords} words expected")
+            return self.to_device(exponents)
+        vals = [int(e) for e in exponents]
+        if any(e < 0 or e >> exp_bits for e in vals):
+            raise ValueError(f"exponents must lie in [0, 2^{exp_bits})")
+        return self.to_device(_limbs.pack(vals, ewords))
+
+    def _fixed_base_ints(self, mode: int, exponents, operands, n: int, base: int, exp_bits: int, window: int) -> List[int]:
+        if operands is not None and len(operands) != len(exponents):
+            raise ValueError("one exponent per operand expected")
+        if len(exponents) == 0:
+            return []
+        _check_modulus(n)
+        table = self.fixed_base_table(n, base, exp_bits, window)
+        e_t = self.fixed_base_exponent_rows(exponents, exp_bits)
+        op_t = None
+        if mode == _lib.MX_FIXEDBASE_ENCRYPT:
+            op_t = self.to_device(_limbs.pack_reduced(operands if isinstance(operands, list) else list(operands), _limbs.limbs_for(n), n))
+        elif mode == _lib.MX_FIXEDBASE_RANDOMIZE:
+            n2 = n * n
+            op_t = self.to_device(_limbs.pack_reduced(operands if isinstance(operands, list) else list(operands), _limbs.limbs_for(n2), n2))
+        return _limbs.unpack(self.to_host(self._fixed_base_run(table, mode, e_t, op_t)))
+
+    @_int_args
+    def fixed_base_power_batch(self, exponents, n: int, base: int, exp_bits: int, window: int = 0) -> List[int]:
+        """[pow(base, e, n^2) for e in exponents] through the table of (n, base, exp_bits, window)."""
+        return self._fixed_base_ints(_lib.MX_FIXEDBASE_POWER, exponents, None, n, base, exp_bits, window)
+
+    @_int_args
+    def fixed_base_encrypt_batch(self, messages: Sequence[int], exponents, n: int, base: int, exp_bits: int, window: int = 0) -> List[int]:
+        """[(1 + (m mod n) n) * pow(base, e, n^2) mod n^2 for m, e] — Paillier encryption with g = n + 1 and the
+        randomiser base^e (randomizer.py says what that randomiser is and is not).  Negative messages work as in encrypt_batch."""
+        return self._fixed_base_ints(_lib.MX_FIXEDBASE_ENCRYPT, exponents, messages, n, base, exp_bits, window)
+
+    @_int_args
+    def fixed_base_randomize_batch(self, ciphertexts: Sequence[int], exponents, n: int, base: int, exp_bits: int, window: int = 0) -> List[int]:
+        """[(c mod n^2) * pow(base, e, n^2) mod n^2 for c, e] — re-randomisation with the randomiser base^e."""
+        return self._fixed_base_ints(_lib.MX_FIXEDBASE_RANDOMIZE, exponents, ciphertexts, n, base, exp_bits, window)
 
     # ------------------------------------------------------------------ modular multiplication / inversion / encryption
     @_int_args
@@ -1093,7 +1250,7 @@ class Engine:
         return out_t
 
     @_int_args
-    def mulmod_batch(self, a: Sequence[int], b: Sequence[int], mod: int) -> List[int]:
+    def mulmod_batch(self, a: Sequence[int], b: Sequence[int], mod: int, fixed_base=None) -> List[int]:
         if len(a) != len(b):
             raise ValueError("operands must have the same length")
         if len(a) == 0:
@@ -1102,7 +1259,7 @@ class Engine:
         limbs = _limbs.limbs_for(mod)
         at = self.to_device(_limbs.pack_reduced(a, limbs, mod))
         bt = self.to_device(_limbs.pack_reduced(b, limbs, mod))
-        return _limbs.unpack(self.to_host(self.mulmod_t(at, bt, mod)))
+        return _limbs.unpack(self.to_host(self._freshened(self.mulmod_t(at, bt, mod), fixed_base)))
 
     DIRECT_MODINV_MAX = 4      # elements inverted directly (one wavefront each); longer batches use the product tree
 
@@ -1156,14 +1313,14 @@ class Engine:
         return inv
 
     @_int_args
-    def modinv_batch(self, values: Sequence[int], mod: int) -> List[int]:
+    def modinv_batch(self, values: Sequence[int], mod: int, fixed_base=None) -> List[int]:
         """[mod_inv(v, mod) for v in values] (PSK:90 over a batch)."""
         if len(values) == 0:
             return []
         _check_modulus(mod)
         limbs = _limbs.limbs_for(mod)
         x_t = self.to_device(_limbs.pack_reduced(values, limbs, mod))
-        return _limbs.unpack(self.to_host(self.modinv_t(x_t, mod)))
+        return _limbs.unpack(self.to_host(self._freshened(self.modinv_t(x_t, mod), fixed_base)))
 
     @_int_args
     def encrypt_batch(self, messages: Sequence[int], randomness: Sequence[int], n: int) -> List[int]:

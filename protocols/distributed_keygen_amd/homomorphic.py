@@ -14,6 +14,10 @@ comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` i
 results are ints: canonical residues in [0, N^2), NOT fresh ciphertexts — re-randomise them
 (``Engine.randomize_batch``) before they leave the party.  ``engine`` is injected for tests; the default is the
 process-wide HIP engine.
+
+Every function takes ``randomizer=None``: given a ``randomizer.FastRandomizer`` of the same N, every result is
+multiplied by a power h_s^a of the randomiser's fixed base on the device, before the rows are fetched — see that
+module for what this randomiser is and is not.  Without one, behaviour and results are unchanged.
 """
 
 from __future__ import annotations
@@ -48,13 +52,21 @@ def _values(cts: Sequence[Any], n: Optional[int]):
     return out, int(n)
 
 
-def scale(cts: Sequence[Any], scalars: Sequence[int], n: Optional[int] = None, engine: Any = None) -> List[int]:
+def _fresh(randomizer: Any, n: int, count: int) -> Dict[str, Any]:
+    """The engine keyword that re-randomises `count` results with `randomizer` (nothing without one)."""
+    if randomizer is None:
+        return {}
+    return {"fixed_base": randomizer.spec(n, count)}
+
+
+def scale(cts: Sequence[Any], scalars: Sequence[int], n: Optional[int] = None, engine: Any = None,
+          randomizer: Any = None) -> List[int]:
     """[c^k mod N^2] for every (c, k) — the plaintexts multiplied by k."""
     vals, n = _values(cts, n)
-    return _engine(engine).ciphertext_scale_batch(vals, [int(k) for k in scalars], n)
+    return _engine(engine).ciphertext_scale_batch(vals, [int(k) for k in scalars], n, **_fresh(randomizer, n, len(vals)))
 
 
-def add(a: Sequence[Any], b: Sequence[Any], n: Optional[int] = None, engine: Any = None) -> List[int]:
+def add(a: Sequence[Any], b: Sequence[Any], n: Optional[int] = None, engine: Any = None, randomizer: Any = None) -> List[int]:
     """[c * d mod N^2] for every pair — the plaintexts added."""
     if len(a) != len(b):
         raise ValueError("operands must have the same length")
@@ -63,18 +75,18 @@ def add(a: Sequence[Any], b: Sequence[Any], n: Optional[int] = None, engine: Any
     if k == 0:
         return []
     n2 = n * n
-    return _engine(engine).mulmod_batch([v % n2 for v in va[:k]], [v % n2 for v in va[k:]], n2)
+    return _engine(engine).mulmod_batch([v % n2 for v in va[:k]], [v % n2 for v in va[k:]], n2, **_fresh(randomizer, n, k))
 
 
-def neg(cts: Sequence[Any], n: Optional[int] = None, engine: Any = None) -> List[int]:
+def neg(cts: Sequence[Any], n: Optional[int] = None, engine: Any = None, randomizer: Any = None) -> List[int]:
     """[c^-1 mod N^2] — the plaintexts negated (ValueError, as pow, for a ciphertext without an inverse)."""
     vals, n = _values(cts, n)
     if not vals:
         return []
-    return _engine(engine).modinv_batch(vals, n * n)
+    return _engine(engine).modinv_batch(vals, n * n, **_fresh(randomizer, n, len(vals)))
 
 
-def sum_groups(groups: Sequence[Sequence[Any]], n: Optional[int] = None, engine: Any = None) -> List[int]:
+def sum_groups(groups: Sequence[Sequence[Any]], n: Optional[int] = None, engine: Any = None, randomizer: Any = None) -> List[int]:
     """[prod(g) mod N^2] for every group — the sum of its plaintexts (an empty group gives 1, an encryption of 0)."""
     groups = [list(g) for g in groups]
     flat, n = _values([c for g in groups for c in g], n)
@@ -82,11 +94,12 @@ def sum_groups(groups: Sequence[Sequence[Any]], n: Optional[int] = None, engine:
     for g in groups:
         out.append(flat[pos : pos + len(g)])
         pos += len(g)
-    return _engine(engine).ciphertext_sum_batch(out, n)
+    return _engine(engine).ciphertext_sum_batch(out, n, **_fresh(randomizer, n, len(out)))
 
 
 def linear_map(cts: Sequence[Any], weights: Sequence[Any], n: Optional[int] = None, bias: Optional[Sequence[int]] = None,
-               engine: Any = None) -> List[int]:
+               engine: Any = None, randomizer: Any = None) -> List[int]:
     """The encrypted W x + b: [(1 + (b_j mod N) N) prod_i c_i^(W_ji) mod N^2 for every row j of W]."""
     vals, n = _values(cts, n)
-    return _engine(engine).ciphertext_linear_map_batch(vals, list(weights), n, bias=bias)
+    weights = list(weights)
+    return _engine(engine).ciphertext_linear_map_batch(vals, weights, n, bias=bias, **_fresh(randomizer, n, len(weights)))

@@ -51,15 +51,20 @@ def slots_per_ciphertext(n: int, slot_bits: int) -> int:
     return k
 
 
-def pack(cts: Sequence[Any], slot_bits: int, n: Optional[int] = None, engine: Any = None) -> List[int]:
+def pack(cts: Sequence[Any], slot_bits: int, n: Optional[int] = None, engine: Any = None, randomizer: Any = None) -> List[int]:
     """[prod_{i < k} c_(j k + i)^(2^(b i)) mod N^2 for every output j]: ceil(len(cts) / k) ciphertexts, k =
     ``slots_per_ciphertext(n, slot_bits)``.  Ciphertexts are ints or objects with ``get_value()`` (read once per distinct
-    object; ``n`` then defaults to ``.scheme.public_key.n``).  Returns canonical residues, not fresh ciphertexts."""
+    object; ``n`` then defaults to ``.scheme.public_key.n``).  Returns canonical residues, not fresh ciphertexts — unless
+    a ``randomizer`` (randomizer.FastRandomizer of the same N) is given: the packed rows are then multiplied by powers of
+    its fixed base on the device before they are fetched.  Parties that must agree on the packed ciphertexts bit for bit
+    (``decrypt_sequence_packed``) pack WITHOUT one."""
     vals, n = _values(list(cts), n)
     k = slots_per_ciphertext(n, slot_bits)
     if not vals:
         return []
-    return _engine(engine).ciphertext_pack_batch(vals, n, int(slot_bits), k)
+    from .homomorphic import _fresh
+
+    return _engine(engine).ciphertext_pack_batch(vals, n, int(slot_bits), k, **_fresh(randomizer, n, -(-len(vals) // k)))
 
 
 def _offset(slot_bits: int, k: int) -> int:
