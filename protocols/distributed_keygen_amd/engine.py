@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib, limbs as _limbs
 
+_INTS = (_ctypes.c_int,) * 5       # out-parameter types of the shape queries (Engine._query), sliced to the count
 
 def _int_args(fn):
     """Coerce the integer operands of an entry point once: parameters annotated ``int`` become Python ints and the
@@ -167,6 +168,11 @@ class Engine:
         self._priority_aux = False             # small kernels on a high-priority companion stream (set_priority_aux)
         self._aux: Dict[int, Any] = {}         # stream -> its companion
         self._split_streams: Dict[int, Any] = {}   # stream -> the companion that runs the second part of a split launch
+        self._cu_streams: Dict[int, List[Any]] = {}    # cu_slice_streams: n -> its streams
+        self._side_stream_pool: List[Any] = []     # every chunk stream ever created (_chunk_streams probes them again)
+        self._capped_calls = 0                     # requests since _side_streams_capped was set (RECHECK_CAPPED_EVERY)
+        self._capped_warned = False
+        self._probe_stream: Any = None             # clock_probe_start
 
     # ------------------------------------------------------------------ plumbing
     def _stream_ptr(self) -> int:
@@ -185,6 +191,30 @@ class Engine:
                 ws = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
             self._ws[key] = ws
         return ws
+
+    def _call(self, symbol: str, *args, workspace: Optional[Tuple[Any, ...]] = None, plans: Sequence[_Plan] = ()) -> int:
+        """The one way to a C entry point that enqueues work.  Inside the device context: orders the current stream behind
+        `plans`, sizes the current stream's workspace by the query `workspace` = (symbol, arguments ...) if the entry point
+        takes one, calls `symbol` with `args` followed by (workspace pointer, workspace bytes, stream) or by (stream) —
+        every such entry point of include/mxpaillier.h ends in one of the two — and checks the status under its name."""
+        with self.torch.cuda.device(self.device):
+            for plan in plans:
+                self._use_plan(plan)
+            if workspace is not None:
+                ws = self._workspace(getattr(self.lib, workspace[0])(*workspace[1:]))
+                args += (ws.data_ptr(), ws.numel())
+            rc = getattr(self.lib, symbol)(*args, self._stream_ptr())
+        return _lib.check(rc, symbol)
+
+    def _query(self, symbol: str, *args, outs: Sequence[Any], allow: Any = ()) -> Optional[Tuple[Any, ...]]:
+        """The values a C query writes through its trailing out-parameters (`outs`: their ctypes types).  A status in
+        `allow` gives None instead of raising."""
+        cells = tuple(t() for t in outs)
+        rc = getattr(self.lib, symbol)(*args, *cells)
+        if rc in allow:
+            return None
+        _lib.check(rc, symbol)
+        return tuple(c.value for c in cells)
 
     def _use_plan(self, plan: _Plan) -> None:
         """Order the current stream after the plan's uploads if they were enqueued on another stream."""
@@ -212,6 +242,25 @@ class Engine:
             cache.popitem(last=False)
         return plan
 
+    def _cached(self, cache: "OrderedDict[Any, _Plan]", key: Any) -> Optional[_Plan]:
+        """The plan kept under `key`, now the most recently used one, or None."""
+        plan = cache.get(key)
+        if plan is not None:
+            cache.move_to_end(key)
+        return plan
+
+    def _prepare(self, cache: "OrderedDict[Any, _Plan]", key: Any, nbytes: int, symbol: str, args: Tuple[Any, ...], wrap) -> _Plan:
+        """A new per-key device block: `nbytes` allocated on the current stream, filled by the prepare entry point `symbol`
+        (`args`, then the block and the stream), with the event that marks the end of its uploads;
+        ``wrap(block, stream pointer, event)`` makes the plan, which is kept under `key` (_cache_plan)."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            block = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            self._call(symbol, *args, block.data_ptr(), block.numel())
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(self.device))
+        return self._cache_plan(cache, key, wrap(block, self._stream_ptr(), ready))
+
     def to_device(self, rows: np.ndarray):
         """uint32 rows -> int32 device tensor (bit pattern preserved)."""
         t = self.torch.from_numpy(np.ascontiguousarray(rows, dtype="<u4").view(np.int32))
@@ -220,6 +269,14 @@ class Engine:
     @staticmethod
     def to_host(t) -> np.ndarray:
         return t.detach().cpu().numpy().view(np.uint32)
+
+    def _upload_ints(self, values, limbs: int, moduli):
+        """ints -> device rows of their residues (limbs.pack_reduced), through a pageable copy."""
+        return self.to_device(_limbs.pack_reduced(values, limbs, moduli))
+
+    def _download_ints(self, rows_t) -> List[int]:
+        """Device rows -> ints, through a pageable copy."""
+        return _limbs.unpack(self.to_host(rows_t))
 
     def synchronize(self) -> None:
         self.torch.cuda.current_stream(self.device).synchronize()
@@ -244,6 +301,7 @@ class Engine:
         self._wpg = int(wavefronts)
 
     GENERIC_LATENCY_MAX_BITS = 29 * 3 * 64 - 4 - 31      # 5533: widest modulus with a 3-limb generic instance (mx_host.hpp: choose_geometry)
+    GENERIC_BIPARTITE_MAX_BITS = 29 * 3 * 62 - 35        # 5359: wavefront H needs Pd / 3 + 2 <= 64 lanes (mx_host.hpp)
 
     def _lpl_generic(self, mod_bits: int = 0) -> int:
         """The engine's lane geometry as the generic-modulus kernels take it.  The latency geometry (3) exists for the
@@ -256,8 +314,6 @@ class Engine:
             return 0
         return self._lpl if self._lpl in (3, 6, 9, 18) else 0
 
-    GENERIC_BIPARTITE_MAX_BITS = 29 * 3 * 62 - 35        # 5359: wavefront H needs Pd / 3 + 2 <= 64 lanes (mx_host.hpp)
-
     def _lpl_n2(self) -> int:
         """... as the N^2 pair kernel takes it: 6 (the generic kernel's bipartite latency form) is its latency geometry 3."""
         return 3 if self._lpl == 6 else self._lpl
@@ -265,11 +321,7 @@ class Engine:
     def generic_launch_form(self, mod_bits: int, batch: int = 1, groups: int = 1) -> Tuple[int, int]:
         """(wavefronts per group of elements, pivot) of a generic-modulus modexp launch with this engine's settings:
         (2, hL) for the bipartite latency form (include/mxpaillier.h: mx_powmod_launch_form), else (1, 0)."""
-        import ctypes
-
-        waves, pivot = ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.lib.mx_powmod_launch_form(mod_bits, batch, groups, self._lpl_generic(mod_bits), waves, pivot), "mx_powmod_launch_form")
-        return waves.value, pivot.value
+        return self._query("mx_powmod_launch_form", mod_bits, batch, groups, self._lpl_generic(mod_bits), outs=_INTS[:2])
 
     def set_segments(self, segments: int) -> None:
         """Launches one mx_powmod_nsquare_run exponentiation is cut into (0 = automatic, 1..64)."""
@@ -315,16 +367,11 @@ class Engine:
         return out
 
     def selftest_lanes(self) -> int:
-        with self.torch.cuda.device(self.device):
-            return _lib.check(self.lib.mx_selftest_lanes(self._stream_ptr()), "mx_selftest_lanes")
+        return self._call("mx_selftest_lanes")
 
     def geometry(self, mod_bits: int, batch: int = 1, groups: int = 1) -> Tuple[int, int, int, int]:
         """(lanes per element, limbs per lane, limb bits, blocks) of a generic-modulus modexp launch."""
-        import ctypes
-
-        k, l, w, b = (ctypes.c_int() for _ in range(4))
-        _lib.check(self.lib.mx_powmod_geometry_for(mod_bits, batch, groups, self._lpl_generic(mod_bits), k, l, w, b), "mx_powmod_geometry_for")
-        return k.value, l.value, w.value, b.value
+        return self._query("mx_powmod_geometry_for", mod_bits, batch, groups, self._lpl_generic(mod_bits), outs=_INTS[:4])
 
     def debug_knob(self, knob: str, value: int) -> None:
         """Developer overrides of the library (include/mxpaillier.h: mx_debug_knob; process-wide, 0 restores
@@ -337,24 +384,17 @@ class Engine:
         in every XCD (mx_stream_create_cu_slice) — as torch streams.  For callers that keep several SMALL launches in
         flight (each fitting its slice at about one wavefront per SIMD): on ordinary streams the dispatcher stacks
         them on the same CUs.  Created once per engine and n; they live as long as the engine."""
-        import ctypes
-
-        cache = self.__dict__.setdefault("_cu_streams", {})
-        if n not in cache:
-            out = []
+        if n not in self._cu_streams:
             with self.torch.cuda.device(self.device):
-                for k in range(n):
-                    ptr = ctypes.c_void_p()
-                    _lib.check(self.lib.mx_stream_create_cu_slice(k, n, 0, ctypes.byref(ptr)), "mx_stream_create_cu_slice")
-                    out.append(self.torch.cuda.ExternalStream(ptr.value, device=self.device))
-            cache[n] = out
-        return cache[n]
+                ptrs = [self._query("mx_stream_create_cu_slice", k, n, 0, outs=(_ctypes.c_void_p,))[0] for k in range(n)]
+                self._cu_streams[n] = [self.torch.cuda.ExternalStream(ptr, device=self.device) for ptr in ptrs]
+        return self._cu_streams[n]
 
     def clock_probe_start(self, microseconds: int = 300):
         """Enqueue a shader-clock probe (mx_clock_probe) on a high-priority stream of its own, so that it runs
         beside whatever the other streams have in flight; returns a handle for clock_probe_mhz."""
         torch = self.torch
-        if getattr(self, "_probe_stream", None) is None:
+        if self._probe_stream is None:
             with torch.cuda.device(self.device):
                 self._probe_stream = torch.cuda.Stream(device=self.device, priority=-1)
         with torch.cuda.device(self.device), torch.cuda.stream(self._probe_stream):
@@ -376,38 +416,21 @@ class Engine:
 
     def profile_collect(self) -> Tuple[float, int]:
         """(sum of kernel durations in ms, launches) since the last collect; waits for the launches."""
-        import ctypes
-
-        total, n = ctypes.c_double(), ctypes.c_int()
-        _lib.check(self.lib.mx_profile_collect(total, n), "mx_profile_collect")
-        return total.value, n.value
+        return self._query("mx_profile_collect", outs=(_ctypes.c_double, _ctypes.c_int))
 
     def nsquare_geometry(self, n_bits: int, batch: int) -> Tuple[int, int, int, int]:
         """(lanes per element, limbs per lane, limb bits, blocks) of a powmod_nsquare launch."""
-        import ctypes
-
         return self.nsquare_launch_shape(n_bits, batch)[:4]
 
     def nsquare_launch_shape(self, n_bits: int, batch: int) -> Tuple[int, int, int, int, int]:
         """(lanes per element, limbs per lane, limb bits, blocks, wavefronts per group) of a
         powmod_nsquare launch of `batch` elements with this engine's settings."""
-        import ctypes
-
-        k, l, w, b, wv = (ctypes.c_int() for _ in range(5))
-        _lib.check(self.lib.mx_nsquare_launch_shape(n_bits, batch, self._lpl_n2(), self._wpg, k, l, w, b, wv), "mx_nsquare_launch_shape")
-        return k.value, l.value, w.value, b.value, wv.value
+        return self._query("mx_nsquare_launch_shape", n_bits, batch, self._lpl_n2(), self._wpg, outs=_INTS[:5])
 
     def nsquare_latency_form(self, n_bits: int) -> Optional[Tuple[int, int, int, int]]:
         """(lanes per element, data positions, pivot, largest batch the library takes the form for by itself) of the
         five-wavefront latency form of powmod_nsquare for moduli of n_bits bits, or None where it has no instance."""
-        import ctypes
-
-        k, pd, pivot, most = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
-        rc = self.lib.mx_nsquare_latency_form(n_bits, k, pd, pivot, most)
-        if rc == -2:                                  # MX_ERR_SIZE
-            return None
-        _lib.check(rc, "mx_nsquare_latency_form")
-        return k.value, pd.value, pivot.value, most.value
+        return self._query("mx_nsquare_latency_form", n_bits, outs=_INTS[:3] + (_ctypes.c_int64,), allow=(-2,))     # MX_ERR_SIZE
 
     def saturating_shape(self, n_bits: int, total: int) -> Tuple[int, int]:
         """(limbs per lane, wavefronts per group) for powmod_nsquare launches that run SIDE BY SIDE on several
@@ -416,25 +439,25 @@ class Engine:
         (include/mxpaillier.h: "callers that keep several launches in flight ... should pass 18 / 1").  Otherwise
         the library's choice for ONE launch of the total, which is what the launches then resemble.  The engine's
         explicit settings win."""
-        import ctypes
-
-        k, l, w, b, wv = (ctypes.c_int() for _ in range(5))
-        if not (self._lpl and self._wpg) and self.lib.mx_nsquare_launch_shape(n_bits, total, self._lpl_n2() or 18, self._wpg or 1, k, l, w, b, wv) == 0:
-            simds = 4 * self.torch.cuda.get_device_properties(self.device).multi_processor_count
-            if wv.value == 1 and l.value == 18 and total * k.value // 64 >= 15 * simds // 8:
-                return (18, 1)
+        if not (self._lpl and self._wpg):
+            # (a size the library has no such shape for is no error here: it falls through to the pieces' shape)
+            wide = self._query("mx_nsquare_launch_shape", n_bits, total, self._lpl_n2() or 18, self._wpg or 1, outs=_INTS[:5], allow=_lib.ERRORS)
+            if wide is not None:
+                k, l, _, _, wv = wide
+                simds = 4 * self.torch.cuda.get_device_properties(self.device).multi_processor_count
+                if wv == 1 and l == 18 and total * k // 64 >= 15 * simds // 8:
+                    return (18, 1)
         # otherwise what one PLAIN launch of the total would run (a time-sliced form is a lone launch's: 4 x 2500 ciphertexts
         # at key_length 2048 reach 214 k/s at 9 limbs per lane, 179 k/s in the shape of the time-sliced choice for 10 000)
-        lo, wo = ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.lib.mx_nsquare_pieces_shape(n_bits, total, self._lpl_n2(), self._wpg, lo, wo), "mx_nsquare_pieces_shape")
-        l_, w_ = lo.value, wo.value
+        l_, w_ = self._query("mx_nsquare_pieces_shape", n_bits, total, self._lpl_n2(), self._wpg, outs=_INTS[:2])
         if w_ == 1 and not self._wpg:
             # One launch of the total would run one wavefront per group (a few per cent ahead of two once it has a
             # wavefront for every SIMD), but the launches are `total` in PIECES: a piece with fewer wavefronts than SIMDs
             # is stacked on the CUs of its neighbours, and the two-wavefront form has twice the wavefronts to spread
             # (key_length 4096, 8 x 1024 in flight: 28.7 ms per step on two wavefronts per group, 42.2 on one)
-            if self.lib.mx_nsquare_pieces_shape(n_bits, total, self._lpl_n2(), 2, lo, wo) == 0:
-                return (self._lpl_n2() or lo.value, 2)
+            two = self._query("mx_nsquare_pieces_shape", n_bits, total, self._lpl_n2(), 2, outs=_INTS[:2], allow=_lib.ERRORS)
+            if two is not None:
+                return (self._lpl_n2() or two[0], 2)
         return (self._lpl_n2() or l_, self._wpg or w_)
 
     def nsquare_launch_split(self, n_bits: int, batch: int) -> Optional[Tuple[int, Tuple[int, int], Tuple[int, int]]]:
@@ -442,28 +465,20 @@ class Engine:
         better run as two launches side by side (mx_nsquare_launch_split) and this engine's settings leave the choice to
         the library; None otherwise.  powmod_nsquare_t follows the hint unless the caller fixed the shape or asked for
         more than one segment (both parts run as single launches); with profile() on, the two launches count as two."""
-        import ctypes
-
         if self._lpl or self._wpg:
             return None
-        first = ctypes.c_int64()
-        a, b, c, d = (ctypes.c_int() for _ in range(4))
-        _lib.check(self.lib.mx_nsquare_launch_split(n_bits, batch, first, a, b, c, d), "mx_nsquare_launch_split")
-        return (int(first.value), (a.value, b.value), (c.value, d.value)) if first.value else None
+        first, a, b, c, d = self._query("mx_nsquare_launch_split", n_bits, batch, outs=(_ctypes.c_int64,) + _INTS[:4])
+        return (int(first), (a, b), (c, d)) if first else None
 
     def nsquare_launch_timesliced(self, n_bits: int, batch: int) -> Tuple[int, int]:
         """(resident workgroups per CU, units per group) when a powmod_nsquare launch of `batch` elements with this
         engine's settings runs in the time-sliced form (mx_nsquare_launch_timesliced), (0, 0) for a plain launch."""
-        import ctypes
-
-        r, u = ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.lib.mx_nsquare_launch_timesliced(n_bits, batch, self._lpl_n2(), self._wpg, r, u), "mx_nsquare_launch_timesliced")
-        return r.value, u.value
+        return self._query("mx_nsquare_launch_timesliced", n_bits, batch, self._lpl_n2(), self._wpg, outs=_INTS[:2])
 
     def _mods_operand(self, mods, limbs: int, odd_only: bool = True):
         """Moduli of a per-group launch as (device rows [groups, limbs], max bits).  `mods` is a sequence
         of Python ints (validated and uploaded here) or an already device-resident pair (rows, bits)."""
-        if isinstance(mods, tuple) and len(mods) == 2 and hasattr(mods[0], "data_ptr"):
+        if _is_device_pair(mods):
             rows_t, bits = mods
             if rows_t.shape[1] != limbs:
                 raise ValueError("device moduli must have the row width of the operands")
@@ -490,13 +505,9 @@ class Engine:
         h_exp = _limbs.pack_one(exp, elimbs)
         if out_t is None:
             out_t = self.torch.empty_like(bases_t)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_powmod_workspace_bytes(limbs, elimbs, batch, 1))
-            rc = self.lib.mx_powmod_shared_lpl(
-                bases_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, h_exp.ctypes.data,
-                limbs, elimbs, batch, self._lpl_generic(mod.bit_length()), ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_powmod_shared_lpl")
+        self._call("mx_powmod_shared_lpl", bases_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, h_exp.ctypes.data,
+                   limbs, elimbs, batch, self._lpl_generic(mod.bit_length()),
+                   workspace=("mx_powmod_workspace_bytes", limbs, elimbs, batch, 1))
         return out_t
 
     def powmod_multi_t(self, bases_t, mods, exps, group_size: int, out_t=None):
@@ -506,7 +517,7 @@ class Engine:
         batch, limbs = bases_t.shape
         mods_t, mod_bits = self._mods_operand(mods, limbs)
         groups = mods_t.shape[0]
-        if isinstance(exps, tuple) and len(exps) == 2 and hasattr(exps[0], "data_ptr"):
+        if _is_device_pair(exps):
             exps_t, exp_bits = exps[0], int(exps[1])
         else:
             if len(exps) != groups:
@@ -522,14 +533,9 @@ class Engine:
             raise ValueError("bases must hold groups*group_size rows")
         if out_t is None:
             out_t = self.torch.empty_like(bases_t)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_powmod_workspace_bytes(limbs, elimbs, batch, groups))
-            rc = self.lib.mx_powmod_multi_dev(
-                bases_t.data_ptr(), out_t.data_ptr(), mods_t.data_ptr(), exps_t.data_ptr(),
-                limbs, elimbs, mod_bits, exp_bits, groups, group_size, self._lpl_generic(mod_bits), ws.data_ptr(), ws.numel(),
-                self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_powmod_multi_dev")
+        self._call("mx_powmod_multi_dev", bases_t.data_ptr(), out_t.data_ptr(), mods_t.data_ptr(), exps_t.data_ptr(),
+                   limbs, elimbs, mod_bits, exp_bits, groups, group_size, self._lpl_generic(mod_bits),
+                   workspace=("mx_powmod_workspace_bytes", limbs, elimbs, batch, groups))
         return out_t
 
     # ------------------------------------------------------------------ per-key plans
@@ -538,9 +544,8 @@ class Engine:
         """The plan of `x -> x^exp mod n^2` (constants and tape of mx_powmod_nsquare_prepare), cached:
         (n, exp) is a key's public modulus and the party's Lagrange-folded share (PSK:46, PSK:79-85)."""
         key = (n, exp, self._fixed_window)
-        plan = self._n2_plans.get(key)
+        plan = self._cached(self._n2_plans, key)
         if plan is not None:
-            self._n2_plans.move_to_end(key)
             return plan
         if exp < 0:
             raise ValueError("negative exponent: invert the base first (paillier_shared_key.py:89-91)")
@@ -550,26 +555,17 @@ class Engine:
         h_n = _limbs.pack_one(n, limbs_n)
         h_exp = _limbs.pack_one(exp, elimbs)
         desc = _lib.NsquarePlan()
-        with self.torch.cuda.device(self.device):
-            nbytes = _lib.check(self.lib.mx_nsquare_plan_bytes(limbs_n, elimbs), "mx_nsquare_plan_bytes")
-            block = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
-            rc = self.lib.mx_powmod_nsquare_prepare_ex(
-                desc, h_n.ctypes.data, h_exp.ctypes.data, limbs_n, elimbs, _lib.MX_PLAN_FIXED_WINDOW if self._fixed_window else 0,
-                block.data_ptr(), block.numel(), self._stream_ptr(),
-            )
-            _lib.check(rc, "mx_powmod_nsquare_prepare_ex")
-            ready = self.torch.cuda.Event()
-            ready.record(self.torch.cuda.current_stream(self.device))
-        plan = _Plan(desc, block, self._stream_ptr(), ready)
-        return self._cache_plan(self._n2_plans, key, plan)
+        nbytes = _lib.check(self.lib.mx_nsquare_plan_bytes(limbs_n, elimbs), "mx_nsquare_plan_bytes")
+        flags = _lib.MX_PLAN_FIXED_WINDOW if self._fixed_window else 0
+        return self._prepare(self._n2_plans, key, nbytes, "mx_powmod_nsquare_prepare_ex",
+                             (desc, h_n.ctypes.data, h_exp.ctypes.data, limbs_n, elimbs, flags), lambda *made: _Plan(desc, *made))
 
     @_int_args
     def combine_plan(self, n: int, theta_inv: int, limbs2: int) -> _Plan:
         """The plan of the share recombination for a key (mx_combine_prepare), cached."""
         key = (n, theta_inv, limbs2)
-        plan = self._combine_plans.get(key)
+        plan = self._cached(self._combine_plans, key)
         if plan is not None:
-            self._combine_plans.move_to_end(key)
             return plan
         _check_modulus(n)
         limbs = _limbs.limbs_for(n)
@@ -580,17 +576,9 @@ class Engine:
         h_n = _limbs.pack_one(n, limbs)
         h_t = _limbs.pack_one(theta_inv, limbs)
         desc = _lib.CombinePlan()
-        with self.torch.cuda.device(self.device):
-            nbytes = _lib.check(self.lib.mx_combine_plan_bytes(limbs, limbs2), "mx_combine_plan_bytes")
-            block = self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.device)
-            rc = self.lib.mx_combine_prepare(
-                desc, h_n.ctypes.data, h_t.ctypes.data, limbs, limbs2, block.data_ptr(), block.numel(), self._stream_ptr()
-            )
-            _lib.check(rc, "mx_combine_prepare")
-            ready = self.torch.cuda.Event()
-            ready.record(self.torch.cuda.current_stream(self.device))
-        plan = _Plan(desc, block, self._stream_ptr(), ready)
-        return self._cache_plan(self._combine_plans, key, plan)
+        nbytes = _lib.check(self.lib.mx_combine_plan_bytes(limbs, limbs2), "mx_combine_plan_bytes")
+        return self._prepare(self._combine_plans, key, nbytes, "mx_combine_prepare",
+                             (desc, h_n.ctypes.data, h_t.ctypes.data, limbs, limbs2), lambda *made: _Plan(desc, *made))
 
     @_int_args
     def powmod_nsquare_t(self, bases_t, n: int, exp: int, out_t=None, segments: Optional[int] = None,
@@ -604,8 +592,7 @@ class Engine:
             raise ValueError("negative exponent: invert the base first (paillier_shared_key.py:89-91)")
         batch, limbs2 = bases_t.shape
         _check_modulus(n)
-        if _limbs.limbs_for(n * n) > limbs2:
-            raise ValueError("rows narrower than N^2")
+        _check_rows_n2(n, limbs2)
         plan = self.nsquare_plan(n, exp)
         if out_t is None:
             out_t = self.torch.empty_like(bases_t)
@@ -630,15 +617,10 @@ class Engine:
             self.powmod_nsquare_t(bases_t[:first], n, exp, out_t=out_t[:first], segments=1, shape=shape_a)
             cur.wait_stream(side)
             return out_t
-        with self.torch.cuda.device(self.device):
-            self._use_plan(plan)
-            ws = self._workspace(self.lib.mx_powmod_nsquare_run_workspace_bytes(plan.desc, batch))
-            rc = self.lib.mx_powmod_nsquare_run(
-                plan.desc, bases_t.data_ptr(), out_t.data_ptr(), limbs2, batch,
-                self._lpl_n2() if shape is None else int(shape[0]), self._wpg if shape is None else int(shape[1]),
-                self._segments if segments is None else int(segments), ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_powmod_nsquare_run")
+        self._call("mx_powmod_nsquare_run", plan.desc, bases_t.data_ptr(), out_t.data_ptr(), limbs2, batch,
+                   self._lpl_n2() if shape is None else int(shape[0]), self._wpg if shape is None else int(shape[1]),
+                   self._segments if segments is None else int(segments),
+                   workspace=("mx_powmod_nsquare_run_workspace_bytes", plan.desc, batch), plans=(plan,))
         return out_t
 
     @_int_args
@@ -652,25 +634,17 @@ class Engine:
         into the recombination without being packed a second time)."""
         if len(bases) == 0:
             return ([], None) if keep_rows else []
-        _check_modulus(n)
-        n2 = n * n
-        limbs2 = _limbs.limbs_for(n2)
+        n2, limbs2 = _nsquare(n)
         vals = bases if isinstance(bases, list) else list(bases)
         if len(vals) < self.PIPELINE_MIN:
             import time as _t
 
             # rows are packed straight into a page-locked buffer and come back through one (a pageable copy of the 5.7 MB
             # of 10 000 ciphertexts costs ~1 ms each way: 2 of the 46 ms of such a call)
-            torch = self.torch
             count = len(vals)
             t0 = _t.perf_counter()
-            in_pin, out_pin = self._pinned("in", count, limbs2), self._pinned("out", count, limbs2)
-            in_np = in_pin.numpy().view(np.uint32)
-            try:
-                _limbs.pack_into(vals, limbs2, in_np, 0)
-                _limbs.reduce_rows(in_np, n2)
-            except ValueError:                        # a value that does not fit the rows, or a negative one
-                in_np[:] = _limbs.pack_reduced(vals, limbs2, n2)
+            in_pin = self._packed_rows("in", vals, limbs2, n2)
+            self._pinned("out", count, limbs2)          # (a first call's page-locked allocations both count as packing)
             t1 = _t.perf_counter()
             # a lone launch that is waited for right away: nothing else is in flight whose drain segments
             # could shorten, and the three extra segment boundaries would cost ~1 % (a time-sliced launch keeps the
@@ -679,10 +653,9 @@ class Engine:
             if self._segments == 0:
                 lone_segments = 0 if self.nsquare_launch_timesliced(n.bit_length(), count)[0] else 1
             out_t = self.powmod_nsquare_t(in_pin.to(self.device, non_blocking=True), n, exp, segments=lone_segments)
-            out_pin.copy_(out_t, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
+            out_np = self._fetched_rows("out", out_t)
             t2 = _t.perf_counter()
-            res = _limbs.unpack(out_pin.numpy().view(np.uint32))
+            res = _limbs.unpack(out_np)
             self.last_timing = {"chunks": 1, "pack_s": t1 - t0, "copies_and_gpu_s": t2 - t1, "unpack_s": _t.perf_counter() - t2}
             return (res, out_t) if keep_rows else res
         self.nsquare_plan(n, exp)          # prepared once, before the chunks fan out over streams
@@ -727,9 +700,7 @@ class Engine:
         outs: Dict[int, Any] = {}
         for j, k in enumerate(live):
             bases, exp, n = jobs[k]
-            _check_modulus(n)
-            n2 = n * n
-            limbs2 = _limbs.limbs_for(n2)
+            n2, limbs2 = _nsquare(n)
             rows = _limbs.pack_reduced(bases, limbs2, n2)
             self.nsquare_plan(n, exp)                     # prepared on the caller's stream, before the fan-out
             side = streams[j % len(streams)]
@@ -739,7 +710,7 @@ class Engine:
         res: List[List[int]] = [[] for _ in jobs]
         for j, k in enumerate(live):
             with torch.cuda.stream(streams[j % len(streams)]):
-                res[k] = _limbs.unpack(self.to_host(outs[k]))     # copied on, and waited for through, the producing stream
+                res[k] = self._download_ints(outs[k])     # copied on, and waited for through, the producing stream
         for side in streams[: len(live)]:
             cur.wait_stream(side)
         return res
@@ -795,7 +766,7 @@ class Engine:
         engine does not keep it forever: it measures again every RECHECK_CAPPED_EVERY requests."""
         torch = self.torch
         if self._side_streams_capped:
-            self._capped_calls = getattr(self, "_capped_calls", 0) + 1
+            self._capped_calls += 1
             if self._capped_calls % self.RECHECK_CAPPED_EVERY == 0:
                 self._side_streams_capped = False
         if len(self._side_streams) < wanted and not self._side_streams_capped:
@@ -803,7 +774,7 @@ class Engine:
                 # high-priority streams are served by their own set of hardware queues: the chunks do not
                 # collide with (and serialise behind) the caller's other streams even when the process runs
                 # with few hardware queues (profiles/r02_hw_queue_collisions.txt)
-                pool = self.__dict__.setdefault("_side_stream_pool", list(self._side_streams))
+                pool = self._side_stream_pool
                 while len(pool) < wanted:
                     # (the runtime serves at most four high-priority streams side by side whatever GPU_MAX_HW_QUEUES says —
                     # measured: 4 of 7 with 16 queues —, so the streams beyond four are ordinary ones, which do get queues
@@ -814,7 +785,7 @@ class Engine:
             if len(ok) < len(cands):
                 import warnings
 
-                if not getattr(self, "_capped_warned", False):
+                if not self._capped_warned:
                     self._capped_warned = True
                     # what the PROBE measured, and only then a guess at why: with enough hardware queues configured the
                     # shortfall is the runtime's own stream-to-queue mapping (streams of the process created earlier hold
@@ -843,12 +814,10 @@ class Engine:
             self._pin[which] = buf
         return buf[: rows * limbs].view(rows, limbs)
 
-    def _staged_rows(self, which: str, values, limbs: int, moduli, nested: int = 0):
-        """ints -> device rows [len(values), limbs] of their residues (limbs.pack_reduced) through the page-locked buffer
-        `which`: packed in place, one asynchronous copy.  The caller synchronises with the stream before it returns (every
-        int-level entry point fetches a result), so the buffer is free again by the time anybody packs into it.
-        `nested` = n: `values` is one list per group, every group `n` rows (its first n values, zero padded) —
-        limbs.pack_nested_into, no flattened copy."""
+    def _packed_rows(self, which: str, values, limbs: int, moduli, nested: int = 0):
+        """ints -> rows [len(values), limbs] of their residues (limbs.pack_reduced) packed in place into the page-locked
+        buffer `which`, which is returned.  `nested` = n: `values` is one list per group, every group `n` rows (its first n
+        values, zero padded) — limbs.pack_nested_into, no flattened copy."""
         if nested:
             lists = values if isinstance(values, (list, tuple)) else list(values)
             count = len(lists) * nested
@@ -867,17 +836,26 @@ class Engine:
             if nested:
                 vals = [v for g in lists for v in (list(g)[:nested] + [0] * (nested - min(nested, len(g))))]
             rows[:] = _limbs.pack_reduced(vals, limbs, moduli)
-        return pin.to(self.device, non_blocking=True)
+        return pin
+
+    def _staged_rows(self, which: str, values, limbs: int, moduli, nested: int = 0):
+        """_packed_rows and one asynchronous copy: the device rows.  The caller synchronises with the stream before it
+        returns (every int-level entry point fetches a result), so the buffer is free again by the time anybody packs
+        into it."""
+        return self._packed_rows(which, values, limbs, moduli, nested).to(self.device, non_blocking=True)
+
+    def _fetched_rows(self, which: str, rows_t) -> np.ndarray:
+        """Device rows -> host rows in the page-locked buffer `which` (waits for the current stream)."""
+        pin = self._pinned(which, rows_t.shape[0], rows_t.shape[1])
+        pin.copy_(rows_t, non_blocking=True)
+        self.torch.cuda.current_stream(self.device).synchronize()
+        return pin.numpy().view(np.uint32)
 
     def _fetched_ints(self, which: str, rows_t, groups=None):
         """Device rows -> ints through the page-locked buffer `which` (waits for the current stream).  `groups` =
         (counts, stride): one list per group instead (limbs.unpack_groups)."""
-        pin = self._pinned(which, rows_t.shape[0], rows_t.shape[1])
-        pin.copy_(rows_t, non_blocking=True)
-        self.torch.cuda.current_stream(self.device).synchronize()
-        if groups is not None:
-            return _limbs.unpack_groups(pin.numpy().view(np.uint32), groups[0], groups[1])
-        return _limbs.unpack(pin.numpy().view(np.uint32))
+        rows = self._fetched_rows(which, rows_t)
+        return _limbs.unpack(rows) if groups is None else _limbs.unpack_groups(rows, groups[0], groups[1])
 
     def _pipelined(self, vals: List[int], limbs_in: int, limbs_out: int, launch, modulus: int = 0) -> List[int]:
         """ints -> ints through `launch(device rows) -> device rows`, chunked over side streams with
@@ -946,9 +924,7 @@ class Engine:
             return []
         _check_modulus(mod)
         limbs = _limbs.limbs_for(mod)
-        rows = _limbs.pack_reduced(bases, limbs, mod)
-        out = self.powmod_shared_t(self.to_device(rows), mod, exp)
-        return _limbs.unpack(self.to_host(out))
+        return self._download_ints(self.powmod_shared_t(self._upload_ints(bases, limbs, mod), mod, exp))
 
     @_int_args
     def powmod_batch_multi(
@@ -970,9 +946,7 @@ class Engine:
         for b in bases:
             flat.extend(b)
             flat.extend([0] * (gsize - len(b)))
-        rows = _limbs.pack_reduced(flat, limbs, list(mods))
-        out = self.powmod_multi_t(self.to_device(rows), list(mods), list(exps), gsize)
-        vals = _limbs.unpack(self.to_host(out))
+        vals = self._download_ints(self.powmod_multi_t(self._upload_ints(flat, limbs, list(mods)), list(mods), list(exps), gsize))
         return [vals[g * gsize : g * gsize + len(bases[g])] for g in range(groups)]
 
 
@@ -980,11 +954,9 @@ class Engine:
     def multiexp_nsquare_shape(self, n: int, n_inputs: int, n_outputs: int, terms: int, weight_bits: int,
                                window: int = 0) -> Tuple[int, int, int]:
         """(window, split-K chunk in terms, table bytes per input and entry) of mx_multiexp_nsquare_shape."""
-        k, l, w = _ctypes_ints(3)
-        chunk = _ctypes.c_int64()
-        _lib.check(self.lib.mx_multiexp_nsquare_shape(int(n).bit_length(), n_inputs, n_outputs, terms, weight_bits, 0, int(window),
-                                                      k, l, w, chunk), "mx_multiexp_nsquare_shape")
-        return w.value, int(chunk.value), 2 * k.value * l.value * 4
+        k, l, w, chunk = self._query("mx_multiexp_nsquare_shape", int(n).bit_length(), n_inputs, n_outputs, terms, weight_bits, 0,
+                                     int(window), outs=_INTS[:3] + (_ctypes.c_int64,))
+        return w, int(chunk), 2 * k * l * 4
 
     def multiexp_nsquare_t(self, inputs_t, weights, n: int, bias: Optional[Sequence[int]] = None, window: int = 0):
         """y_j = (1 + (b_j mod n) n) * prod_i inputs[i]^W[j][i]  mod n^2 on the device (csrc/mx_multiexp_n2.hpp).
@@ -1000,8 +972,7 @@ class Engine:
         n = int(n)
         _check_modulus(n)
         n_inputs, limbs2 = inputs_t.shape
-        if _limbs.limbs_for(n * n) > limbs2:
-            raise ValueError("rows narrower than N^2")
+        _check_rows_n2(n, limbs2)
         nb = n.bit_length()
         plan = mp.plan_call(weights, n_inputs, n, bias, lambda a, b, c, d: self.multiexp_nsquare_shape(n, a, b, c, d),
                             window=int(window))
@@ -1010,16 +981,14 @@ class Engine:
     def _linear_map_ints(self, cts: Sequence[int], weights, n: int, bias=None, fixed_base=None) -> List[int]:
         if not weights:
             return []
-        _check_modulus(n)
-        n2 = n * n
-        limbs2 = _limbs.limbs_for(n2)
+        n2, limbs2 = _nsquare(n)
         if not len(cts):
             from . import multiexp_plan as mp
 
             mp.normalize_rows(weights, 0, n)          # (a map of no inputs: every row must be empty)
         vals = list(cts) if len(cts) else [0]
-        x_t = self.to_device(_limbs.pack_reduced(vals, limbs2, n2))
-        return _limbs.unpack(self.to_host(self._freshened(self.multiexp_nsquare_t(x_t, weights, n, bias), fixed_base)))
+        x_t = self._upload_ints(vals, limbs2, n2)
+        return self._download_ints(self._freshened(self.multiexp_nsquare_t(x_t, weights, n, bias), fixed_base))
 
     @_int_args
     def ciphertext_scale_batch(self, cts: Sequence[int], scalars: Sequence[int], n: int, fixed_base=None) -> List[int]:
@@ -1057,8 +1026,7 @@ class Engine:
         n, slot_bits, slots = int(n), int(slot_bits), int(slots)
         _check_modulus(n)
         count, limbs2 = cts_t.shape
-        if _limbs.limbs_for(n * n) > limbs2:
-            raise ValueError("rows narrower than N^2")
+        _check_rows_n2(n, limbs2)
         if slot_bits < 1 or slots < 1 or slot_bits * slots > n.bit_length() - 2:
             raise ValueError(f"{slots} slots of {slot_bits} bits do not fit a plaintext of {n.bit_length()} bits")
         torch = self.torch
@@ -1067,11 +1035,7 @@ class Engine:
             return out_t
         cts_t = cts_t.contiguous()
         plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
-        with torch.cuda.device(self.device):
-            self._use_plan(plan)
-            rc = self.lib.mx_pack_nsquare_run(plan.desc, cts_t.data_ptr(), count, limbs2, slot_bits, slots, out_t.data_ptr(),
-                                              0, self._stream_ptr())
-        _lib.check(rc, "mx_pack_nsquare_run")
+        self._call("mx_pack_nsquare_run", plan.desc, cts_t.data_ptr(), count, limbs2, slot_bits, slots, out_t.data_ptr(), 0, plans=(plan,))
         return out_t
 
     @_int_args
@@ -1079,23 +1043,20 @@ class Engine:
         """[prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 for j < ceil(len(cts) / slots)]
         (pack_nsquare_t).  Inputs are reduced modulo n^2; any residue is valid, 0 and multiples of n included (nothing
         is inverted)."""
-        _check_modulus(n)
+        n2, limbs2 = _nsquare(n)
         if not len(cts):
             return []
-        n2 = n * n
-        limbs2 = _limbs.limbs_for(n2)
-        x_t = self.to_device(_limbs.pack_reduced(cts if isinstance(cts, list) else list(cts), limbs2, n2))
-        return _limbs.unpack(self.to_host(self._freshened(self.pack_nsquare_t(x_t, n, slot_bits, slots), fixed_base)))
+        x_t = self._upload_ints(cts if isinstance(cts, list) else list(cts), limbs2, n2)
+        return self._download_ints(self._freshened(self.pack_nsquare_t(x_t, n, slot_bits, slots), fixed_base))
 
     # ------------------------------------------------------------------ fixed base: encryption and re-randomisation
     def fixed_base_shape(self, n: int, exp_bits: int, count: int, window: int = 0, table_budget_bytes: int = 0) -> Tuple[int, int, int]:
         """(window, windows, table bytes) of mx_fixedbase_nsquare_shape for `count` outputs per call."""
-        k, l, w, nw = _ctypes_ints(4)
         nb = int(n).bit_length()
-        _lib.check(self.lib.mx_fixedbase_nsquare_shape(nb, int(exp_bits), int(count), int(table_budget_bytes), 0, int(window),
-                                                       k, l, w, nw), "mx_fixedbase_nsquare_shape")
-        nbytes = _lib.check(self.lib.mx_fixedbase_nsquare_table_bytes(nb, int(exp_bits), 0, w.value), "mx_fixedbase_nsquare_table_bytes")
-        return w.value, nw.value, int(nbytes)
+        _, _, w, nw = self._query("mx_fixedbase_nsquare_shape", nb, int(exp_bits), int(count), int(table_budget_bytes), 0, int(window),
+                                  outs=_INTS[:4])
+        nbytes = _lib.check(self.lib.mx_fixedbase_nsquare_table_bytes(nb, int(exp_bits), 0, w), "mx_fixedbase_nsquare_table_bytes")
+        return w, nw, int(nbytes)
 
     FIXED_BASE_MODEL_COUNT = 100000      # outputs per call the automatic window is chosen for (the table is per key)
 
@@ -1106,31 +1067,22 @@ class Engine:
         discipline.  ``window`` = 0: the library's choice for FIXED_BASE_MODEL_COUNT outputs per call.  ``base`` is
         reduced modulo n^2; any residue is valid."""
         key = (n, base, exp_bits, window)
-        tab = self._fixed_base_tables.get(key)
+        tab = self._cached(self._fixed_base_tables, key)
         if tab is not None:
-            self._fixed_base_tables.move_to_end(key)
             return tab
-        _check_modulus(n)
+        n2, limbs2 = _nsquare(n)
         if exp_bits < 1 or exp_bits > 2 * n.bit_length() + 64:
             raise ValueError(f"exp_bits must lie in 1 .. 2 bits(n) + 64 = {2 * n.bit_length() + 64}")
         if not 0 <= window <= 8:
             raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
-        n2 = n * n
-        limbs2 = _limbs.limbs_for(n2)
         w, windows, nbytes = self.fixed_base_shape(n, exp_bits, self.FIXED_BASE_MODEL_COUNT, window)
         plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
-        torch = self.torch
-        with torch.cuda.device(self.device):
+        with self.torch.cuda.device(self.device):
             self._use_plan(plan)
-            base_t = self.to_device(_limbs.pack_reduced([base], limbs2, n2))
-            block = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            rc = self.lib.mx_fixedbase_nsquare_prepare(plan.desc, base_t.data_ptr(), limbs2, exp_bits, 0, w,
-                                                       block.data_ptr(), nbytes, self._stream_ptr())
-            _lib.check(rc, "mx_fixedbase_nsquare_prepare")
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(self.device))
-        tab = FixedBaseTable(plan, block, self._stream_ptr(), ready, n, base % n2, exp_bits, w, windows, nbytes)
-        return self._cache_plan(self._fixed_base_tables, key, tab)
+            base_t = self._upload_ints([base], limbs2, n2)
+        return self._prepare(self._fixed_base_tables, key, nbytes, "mx_fixedbase_nsquare_prepare",
+                             (plan.desc, base_t.data_ptr(), limbs2, exp_bits, 0, w),
+                             lambda *made: FixedBaseTable(plan, *made, n, base % n2, exp_bits, w, windows, nbytes))
 
     def _freshened(self, rows_t, fixed_base):
         """``rows_t`` (ciphertext rows modulo n^2, on the device) re-randomised there before they are fetched:
@@ -1155,21 +1107,18 @@ class Engine:
             if operand_t.shape[0] != count:
                 raise ValueError("one operand row per exponent row expected")
             op_limbs = operand_t.shape[1]
-            need = _limbs.limbs_for(table.n) if mode == _lib.MX_FIXEDBASE_ENCRYPT else limbs2
-            if op_limbs < need:
-                raise ValueError("operand rows narrower than N" if mode == _lib.MX_FIXEDBASE_ENCRYPT else "rows narrower than N^2")
+            if mode != _lib.MX_FIXEDBASE_ENCRYPT:
+                _check_rows_n2(table.n, op_limbs)
+            elif op_limbs < _limbs.limbs_for(table.n):
+                raise ValueError("operand rows narrower than N")
             operand_t = operand_t.contiguous()
         out_t = torch.empty((count, limbs2), dtype=torch.int32, device=self.device)
         if count == 0:
             return out_t
         exps_t = exps_t.contiguous()
-        with torch.cuda.device(self.device):
-            self._use_plan(table.plan)
-            self._use_plan(table)
-            rc = self.lib.mx_fixedbase_nsquare_run(table.desc, table.block.data_ptr(), table.exp_bits, table.window, mode,
-                                                   exps_t.data_ptr(), operand_t.data_ptr() if operand_t is not None else None,
-                                                   op_limbs, out_t.data_ptr(), count, limbs2, 0, self._stream_ptr())
-        _lib.check(rc, "mx_fixedbase_nsquare_run")
+        self._call("mx_fixedbase_nsquare_run", table.desc, table.block.data_ptr(), table.exp_bits, table.window, mode,
+                   exps_t.data_ptr(), operand_t.data_ptr() if operand_t is not None else None,
+                   op_limbs, out_t.data_ptr(), count, limbs2, 0, plans=(table.plan, table))
         return out_t
 
     def fixed_base_power_t(self, table: FixedBaseTable, exps_t):
@@ -1207,12 +1156,10 @@ class Engine:
         table = self.fixed_base_table(n, base, exp_bits, window)
         e_t = self.fixed_base_exponent_rows(exponents, exp_bits)
         op_t = None
-        if mode == _lib.MX_FIXEDBASE_ENCRYPT:
-            op_t = self.to_device(_limbs.pack_reduced(operands if isinstance(operands, list) else list(operands), _limbs.limbs_for(n), n))
-        elif mode == _lib.MX_FIXEDBASE_RANDOMIZE:
-            n2 = n * n
-            op_t = self.to_device(_limbs.pack_reduced(operands if isinstance(operands, list) else list(operands), _limbs.limbs_for(n2), n2))
-        return _limbs.unpack(self.to_host(self._fixed_base_run(table, mode, e_t, op_t)))
+        if operands is not None:
+            mod = n if mode == _lib.MX_FIXEDBASE_ENCRYPT else n * n          # messages modulo N, ciphertexts modulo N^2
+            op_t = self._upload_ints(operands if isinstance(operands, list) else list(operands), _limbs.limbs_for(mod), mod)
+        return self._download_ints(self._fixed_base_run(table, mode, e_t, op_t))
 
     @_int_args
     def fixed_base_power_batch(self, exponents, n: int, base: int, exp_bits: int, window: int = 0) -> List[int]:
@@ -1240,13 +1187,8 @@ class Engine:
         h_mod = _limbs.pack_one(mod, limbs)
         if out_t is None:
             out_t = self.torch.empty_like(a_t)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_mulmod_workspace_bytes(limbs))
-            rc = self.lib.mx_mulmod_shared(
-                a_t.data_ptr(), b_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
-                ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_mulmod_shared")
+        self._call("mx_mulmod_shared", a_t.data_ptr(), b_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
+                   workspace=("mx_mulmod_workspace_bytes", limbs))
         return out_t
 
     @_int_args
@@ -1257,9 +1199,8 @@ class Engine:
             return []
         _check_modulus(mod)
         limbs = _limbs.limbs_for(mod)
-        at = self.to_device(_limbs.pack_reduced(a, limbs, mod))
-        bt = self.to_device(_limbs.pack_reduced(b, limbs, mod))
-        return _limbs.unpack(self.to_host(self._freshened(self.mulmod_t(at, bt, mod), fixed_base)))
+        at, bt = self._upload_ints(a, limbs, mod), self._upload_ints(b, limbs, mod)
+        return self._download_ints(self._freshened(self.mulmod_t(at, bt, mod), fixed_base))
 
     DIRECT_MODINV_MAX = 4      # elements inverted directly (one wavefront each); longer batches use the product tree
 
@@ -1273,13 +1214,8 @@ class Engine:
         h_mod = _limbs.pack_one(mod, limbs)
         out_t = self.torch.empty_like(x_t)
         status_t = self.torch.empty(batch, dtype=self.torch.uint8, device=self.device)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_modinv_workspace_bytes(limbs))
-            rc = self.lib.mx_modinv(
-                x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
-                ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_modinv")
+        self._call("mx_modinv", x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
+                   workspace=("mx_modinv_workspace_bytes", limbs))
         if int(status_t.sum().item()) != 0:
             raise ValueError("base is not invertible for the given modulus")
         return out_t
@@ -1319,38 +1255,32 @@ class Engine:
             return []
         _check_modulus(mod)
         limbs = _limbs.limbs_for(mod)
-        x_t = self.to_device(_limbs.pack_reduced(values, limbs, mod))
-        return _limbs.unpack(self.to_host(self._freshened(self.modinv_t(x_t, mod), fixed_base)))
+        x_t = self._upload_ints(values, limbs, mod)
+        return self._download_ints(self._freshened(self.modinv_t(x_t, mod), fixed_base))
 
     @_int_args
     def encrypt_batch(self, messages: Sequence[int], randomness: Sequence[int], n: int) -> List[int]:
         """Paillier encryption with g = n + 1:  c = (1 + m n) * r^n mod n^2 for every (m, r)."""
-        if len(messages) != len(randomness):
-            raise ValueError("one randomness per message expected")
-        if len(messages) == 0:
-            return []
-        _check_modulus(n)
-        n2 = n * n
-        limbs = _limbs.limbs_for(n2)
-        rn_t = self.powmod_nsquare_t(self.to_device(_limbs.pack_reduced(randomness, limbs, n2)), n, n)
-        g_t = self.to_device(_limbs.pack([(1 + (m % n) * n) % n2 for m in messages], limbs))
-        return _limbs.unpack(self.to_host(self.mulmod_t(rn_t, g_t, n2, out_t=rn_t)))
+        return self._times_rn(messages, "message", randomness, n,
+                              lambda limbs, n2: _limbs.pack([(1 + (m % n) * n) % n2 for m in messages], limbs))
 
     @_int_args
     def randomize_batch(self, ciphertexts: Sequence[int], randomness: Sequence[int], n: int) -> List[int]:
         """Re-randomisation of Paillier ciphertexts, c * r^n mod n^2 for every (c, r) — what the
         un-vendored scheme's ``randomize`` does before a ciphertext is sent (README.md:165-171 of the
         reference: a ciphertext must be fresh when it leaves); r^n through the N^2 pair kernel."""
-        if len(ciphertexts) != len(randomness):
-            raise ValueError("one randomness per ciphertext expected")
-        if len(ciphertexts) == 0:
+        return self._times_rn(ciphertexts, "ciphertext", randomness, n,
+                              lambda limbs, n2: _limbs.pack_reduced(ciphertexts, limbs, n2))
+
+    def _times_rn(self, values, what: str, randomness, n: int, rows) -> List[int]:
+        """[v * r^n mod n^2 for v, r]: r^n through the N^2 pair kernel, times the rows ``rows(limbs, n^2)`` packs of `values`."""
+        if len(values) != len(randomness):
+            raise ValueError(f"one randomness per {what} expected")
+        if len(values) == 0:
             return []
-        _check_modulus(n)
-        n2 = n * n
-        limbs = _limbs.limbs_for(n2)
-        rn_t = self.powmod_nsquare_t(self.to_device(_limbs.pack_reduced(randomness, limbs, n2)), n, n)
-        c_t = self.to_device(_limbs.pack_reduced(ciphertexts, limbs, n2))
-        return _limbs.unpack(self.to_host(self.mulmod_t(rn_t, c_t, n2, out_t=rn_t)))
+        n2, limbs = _nsquare(n)
+        rn_t = self.powmod_nsquare_t(self._upload_ints(randomness, limbs, n2), n, n)
+        return self._download_ints(self.mulmod_t(rn_t, self.to_device(rows(limbs, n2)), n2, out_t=rn_t))
 
     # ------------------------------------------------------------------ Shamir field of the key generation
     @_int_args
@@ -1364,13 +1294,8 @@ class Engine:
         h_mod = _limbs.pack_one(prime, limbs)
         if out_t is None:
             out_t = self.torch.empty_like(a_t)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_field_workspace_bytes(limbs, 0))
-            rc = self.lib.mx_fma_mod(
-                a_t.data_ptr(), b_t.data_ptr(), c_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
-                ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_fma_mod")
+        self._call("mx_fma_mod", a_t.data_ptr(), b_t.data_ptr(), c_t.data_ptr(), out_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
+                   workspace=("mx_field_workspace_bytes", limbs, 0))
         return out_t
 
     @_int_args
@@ -1386,13 +1311,8 @@ class Engine:
         h_cf = _limbs.pack([c % prime for c in coeffs], limbs)
         if out_t is None:
             out_t = self.torch.empty((batch, limbs), dtype=self.torch.int32, device=self.device)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_field_workspace_bytes(limbs, terms))
-            rc = self.lib.mx_lincomb_mod(
-                x_t.data_ptr(), h_cf.ctypes.data, out_t.data_ptr(), h_mod.ctypes.data, limbs, terms, batch,
-                ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_lincomb_mod")
+        self._call("mx_lincomb_mod", x_t.data_ptr(), h_cf.ctypes.data, out_t.data_ptr(), h_mod.ctypes.data, limbs, terms, batch,
+                   workspace=("mx_field_workspace_bytes", limbs, terms))
         return out_t
 
     @_int_args
@@ -1402,8 +1322,8 @@ class Engine:
         if len(a) == 0:
             return []
         limbs = _limbs.limbs_for(prime)
-        ts = [self.to_device(_limbs.pack_reduced(col, limbs, prime)) for col in (a, b, c)]
-        return _limbs.unpack(self.to_host(self.shamir_fma_t(ts[0], ts[1], ts[2], prime)))
+        ts = [self._upload_ints(col, limbs, prime) for col in (a, b, c)]
+        return self._download_ints(self.shamir_fma_t(ts[0], ts[1], ts[2], prime))
 
     @_int_args
     def shamir_lincomb_batch(self, columns: Sequence[Sequence[int]], coeffs: Sequence[int], prime: int) -> List[int]:
@@ -1414,7 +1334,7 @@ class Engine:
             raise ValueError("columns must have the same length")
         limbs = _limbs.limbs_for(prime)
         x = np.stack([_limbs.pack_reduced(col, limbs, prime) for col in columns])
-        return _limbs.unpack(self.to_host(self.shamir_lincomb_t(self.to_device(x), coeffs, prime)))
+        return self._download_ints(self.shamir_lincomb_t(self.to_device(x), coeffs, prime))
 
     @_int_args
     def shamir_reconstruct_sieve_batch(self, columns: Sequence[Sequence[int]], coeffs: Sequence[int], prime: int,
@@ -1455,7 +1375,7 @@ class Engine:
         if len(keep):
             idx = self.torch.from_numpy(keep.astype(np.int64)).to(self.device)
             rows_t = mods_t.index_select(0, idx)
-            vals = _limbs.unpack(self.to_host(rows_t))
+            vals = self._download_ints(rows_t)
             survivors = {int(k): v for k, v in zip(keep, vals)}
             rows = _ModulusRows(rows_t, _limbs.max_bits(vals))
         flags = bad.astype(bool).tolist()
@@ -1469,10 +1389,8 @@ class Engine:
         the rows [first, first+count) of every group are evaluated (the other entries of out_t are left
         as they are); groups with skip_counts_t[g] >= skip_threshold are skipped."""
         total, limbs = values_t.shape
-        if not (isinstance(mods, tuple) and hasattr(mods[0], "data_ptr")):
-            for m in mods:
-                if m < 1 or m % 2 == 0:
-                    raise ValueError("n should be an odd positive integer")
+        if not _is_device_pair(mods):
+            _check_jacobi_moduli(mods)
         mods_t, _ = self._mods_operand(mods, limbs, odd_only=False)
         groups = mods_t.shape[0]
         if total != groups * group_size:
@@ -1482,12 +1400,8 @@ class Engine:
         if out_t is None:
             full = first == 0 and count == group_size and skip_counts_t is None
             out_t = (self.torch.empty if full else self.torch.zeros)(total, dtype=self.torch.int8, device=self.device)
-        with self.torch.cuda.device(self.device):
-            rc = self.lib.mx_jacobi_dev_range(
-                values_t.data_ptr(), out_t.data_ptr(), mods_t.data_ptr(), limbs, groups, group_size, first, count,
-                skip_counts_t.data_ptr() if skip_counts_t is not None else None, skip_threshold, self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_jacobi_dev_range")
+        self._call("mx_jacobi_dev_range", values_t.data_ptr(), out_t.data_ptr(), mods_t.data_ptr(), limbs, groups, group_size, first,
+                   count, skip_counts_t.data_ptr() if skip_counts_t is not None else None, skip_threshold)
         return out_t
 
     @_int_args
@@ -1496,9 +1410,7 @@ class Engine:
         groups = len(mods)
         if groups == 0:
             return []
-        for m in mods:
-            if m < 1 or m % 2 == 0:
-                raise ValueError("n should be an odd positive integer")
+        _check_jacobi_moduli(mods)
         gsize = max(len(v) for v in values)
         if gsize == 0:
             return [[] for _ in values]
@@ -1507,7 +1419,7 @@ class Engine:
         for vs in values:
             flat.extend(vs)
             flat.extend([0] * (gsize - len(vs)))
-        out = self.jacobi_t(self.to_device(_limbs.pack_reduced(flat, limbs, list(mods))), list(mods), gsize)
+        out = self.jacobi_t(self._upload_ints(flat, limbs, list(mods)), list(mods), gsize)
         arr = out.cpu().numpy()
         return [[int(x) for x in arr[g * gsize : g * gsize + len(values[g])]] for g in range(groups)]
 
@@ -1518,12 +1430,8 @@ class Engine:
         groups = total // group_size
         out_t = self.torch.empty((groups * keep, limbs), dtype=self.torch.int32, device=self.device)
         cnt_t = self.torch.empty(groups, dtype=self.torch.int32, device=self.device)
-        with self.torch.cuda.device(self.device):
-            rc = self.lib.mx_select_first(
-                rows_t.data_ptr(), flags_t.data_ptr(), out_t.data_ptr(), cnt_t.data_ptr(), limbs, groups,
-                group_size, keep, self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_select_first")
+        self._call("mx_select_first", rows_t.data_ptr(), flags_t.data_ptr(), out_t.data_ptr(), cnt_t.data_ptr(), limbs, groups,
+                   group_size, keep)
         return out_t, cnt_t
 
     JACOBI_ONE_LAUNCH_SYMBOLS = 16384        # 256 wavefronts: a quarter of the SIMDs
@@ -1595,13 +1503,8 @@ class Engine:
         h_primes = np.ascontiguousarray(np.asarray(list(primes), dtype=np.uint32))
         if out_t is None:
             out_t = self.torch.empty(batch, dtype=self.torch.uint8, device=self.device)
-        with self.torch.cuda.device(self.device):
-            ws = self._workspace(self.lib.mx_sieve_workspace_bytes(limbs, len(h_primes)))
-            rc = self.lib.mx_sieve(
-                cands_t.data_ptr(), out_t.data_ptr(), h_primes.ctypes.data, len(h_primes), limbs, batch,
-                ws.data_ptr(), ws.numel(), self._stream_ptr(),
-            )
-        _lib.check(rc, "mx_sieve")
+        self._call("mx_sieve", cands_t.data_ptr(), out_t.data_ptr(), h_primes.ctypes.data, len(h_primes), limbs, batch,
+                   workspace=("mx_sieve_workspace_bytes", limbs, len(h_primes)))
         return out_t
 
     @_int_args
@@ -1635,16 +1538,8 @@ class Engine:
             raise ValueError("output rows of the wrong shape")
         if status_t is None and not packed:
             status_t = self.torch.empty(batch, dtype=self.torch.uint8, device=self.device)
-        def run():
-            with self.torch.cuda.device(self.device):
-                self._use_plan(plan)
-                rc = self.lib.mx_combine_run(
-                    plan.desc, partials_t.data_ptr(), out_t.data_ptr(), stride,
-                    status_t.data_ptr() if status_t is not None else None, n_partials, batch, self._stream_ptr(),
-                )
-            _lib.check(rc, "mx_combine_run")
-
-        self._small(run)
+        self._small(lambda: self._call("mx_combine_run", plan.desc, partials_t.data_ptr(), out_t.data_ptr(), stride,
+                                       status_t.data_ptr() if status_t is not None else None, n_partials, batch, plans=(plan,)))
         return out_t if packed else (out_t, status_t)
 
     @_int_args
@@ -1663,7 +1558,7 @@ class Engine:
         rows = np.stack([_limbs.pack_reduced([p[i] for p in partials], limbs2, n2) for i in range(n_partials)])
         out_t, status_t = self.combine_t(self.to_device(rows), n, theta_inv)
         ok = [not bool(x) for x in status_t.cpu().numpy()]
-        return _limbs.unpack(self.to_host(out_t)), ok
+        return self._download_ints(out_t), ok
 
     @_int_args
     def combine_columns(self, columns: Sequence[Any], n: int, theta_inv: int) -> Tuple[List[int], List[bool]]:
@@ -1677,9 +1572,7 @@ class Engine:
 
         if len(columns) == 0:
             return [], []
-        _check_modulus(n)
-        n2 = n * n
-        limbs2 = _limbs.limbs_for(n2)
+        n2, limbs2 = _nsquare(n)
         torch = self.torch
         cols = []
         for col in columns:
@@ -1709,16 +1602,9 @@ class Engine:
             raise ValueError("one modulus per group expected")
         if pass_t is None:
             pass_t = self.torch.empty((groups, n_slots), dtype=self.torch.uint8, device=self.device)
-        def run():
-            with self.torch.cuda.device(self.device):
-                ws = self._workspace(self.lib.mx_verdict_workspace_bytes(limbs, n_parties, groups, n_slots))
-                rc = self.lib.mx_biprime_verdict_dev(
-                    v_t.data_ptr(), pass_t.data_ptr(), mods_t.data_ptr(), limbs, mod_bits, n_parties, groups, n_slots,
-                    ws.data_ptr(), ws.numel(), self._stream_ptr(),
-                )
-            _lib.check(rc, "mx_biprime_verdict_dev")
-
-        self._small(run)
+        self._small(lambda: self._call("mx_biprime_verdict_dev", v_t.data_ptr(), pass_t.data_ptr(), mods_t.data_ptr(), limbs, mod_bits,
+                                       n_parties, groups, n_slots,
+                                       workspace=("mx_verdict_workspace_bytes", limbs, n_parties, groups, n_slots)))
         return pass_t
 
     @_int_args
@@ -1780,10 +1666,6 @@ class Engine:
         return [list(map(bool, arr[g])) for g in range(groups)]
 
 
-def _ctypes_ints(k: int):
-    return tuple(_ctypes.c_int() for _ in range(k))
-
-
 class _MultiexpBackend:
     """multiexp_plan.execute over device rows of one Engine and modulus."""
 
@@ -1802,7 +1684,7 @@ class _MultiexpBackend:
         return self.eng.modinv_t(rows_t, self.n * self.n)
 
     def bias_rows(self, residues):
-        return self.eng.to_device(_limbs.pack_reduced([1 + b * self.n for b in residues], self.limbs2, self.n * self.n))
+        return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
 
     def gather(self, inputs_t, inv_t, bias_t, parts):
         pools = [inputs_t] + [t for t in (inv_t, bias_t) if t is not None]
@@ -1822,17 +1704,12 @@ class _MultiexpBackend:
         out_t = torch.empty((rows, self.limbs2), dtype=torch.int32, device=eng.device)
         idx_t = eng.to_device(launch.index.view(np.uint32))
         w_t = eng.to_device(launch.weights.reshape(rows, -1))
-        with torch.cuda.device(eng.device):
-            eng._use_plan(self.plan)
-            ws = eng._workspace(eng.lib.mx_multiexp_nsquare_workspace_bytes(self.n_bits, n_tables, 0, window))
-            rc = eng.lib.mx_multiexp_nsquare_run(
-                self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_tables, self.limbs2,
-                idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, out_t.data_ptr(), rows, 0, window,
-                ws.data_ptr(), ws.numel(), eng._stream_ptr())
-        _lib.check(rc, "mx_multiexp_nsquare_run")
+        eng._call("mx_multiexp_nsquare_run", self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_tables, self.limbs2,
+                  idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, out_t.data_ptr(), rows, 0, window,
+                  workspace=("mx_multiexp_nsquare_workspace_bytes", self.n_bits, n_tables, 0, window), plans=(self.plan,))
         return out_t
 
-    def _pick(self, picks, with_one: bool):
+    def _pick(self, picks):
         torch = self.torch
         outs, first, index = [], {}, []
         one = None
@@ -1855,11 +1732,7 @@ class _MultiexpBackend:
         pool = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
         return self.take(pool, index)
 
-    def rows_of(self, picks):
-        return self._pick(picks, False)
-
-    def assemble(self, picks):
-        return self._pick(picks, True)
+    rows_of = assemble = _pick          # the two names multiexp_plan.execute calls
 
 
 def _check_modulus(mod: int) -> None:
@@ -1867,9 +1740,27 @@ def _check_modulus(mod: int) -> None:
         raise ValueError("modulus must be odd and >= 3 (Paillier moduli N and N^2 are)")
 
 
-def _reduce(value: int, mod: int) -> int:
-    value = int(value)
-    return value if 0 <= value < mod else value % mod
+def _check_jacobi_moduli(mods) -> None:
+    for m in mods:
+        if m < 1 or m % 2 == 0:
+            raise ValueError("n should be an odd positive integer")
+
+
+def _nsquare(n: int) -> Tuple[int, int]:
+    """(N^2, limbs of its rows) for a valid Paillier modulus N."""
+    _check_modulus(n)
+    n2 = n * n
+    return n2, _limbs.limbs_for(n2)
+
+
+def _check_rows_n2(n: int, limbs2: int) -> None:
+    if _limbs.limbs_for(n * n) > limbs2:
+        raise ValueError("rows narrower than N^2")
+
+
+def _is_device_pair(x) -> bool:
+    """An operand that is already on the device: (rows, max bits)."""
+    return isinstance(x, tuple) and len(x) == 2 and hasattr(x[0], "data_ptr")
 
 
 _default_engine: Optional[Engine] = None

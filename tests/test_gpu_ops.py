@@ -424,6 +424,42 @@ def test_chunked_int_level_batch_on_several_streams(eng):
     assert again == got
 
 
+def test_jobs_of_several_keys_side_by_side_on_separate_streams(eng, monkeypatch):
+    """Engine.powmod_nsquare_groups: the jobs of two keys of different lengths (and an empty one between them) run side
+    by side on side streams; every job's results equal pow.  The stream order is checked from the waits the engine
+    enqueues: every side stream that got a job first waited for the caller's stream, and by the time the call returns
+    the caller's stream has waited for every one of them — so once the caller's stream is drained the side streams are
+    idle too.  (Stream.query() of the caller's stream right after the call says nothing: the waits it was just given
+    may still sit in its queue.)"""
+    rng = random.Random(515 + 1027)
+    jobs = []
+    for bits, count in ((515, 5), (0, 0), (1027, 9)):
+        n = (rng.getrandbits(bits) | (1 << (bits - 1)) | 1) if bits else 15
+        jobs.append(([rng.randrange(n * n) for _ in range(count)], rng.getrandbits(130) | (1 << 129), n))
+    stream_cls = eng.torch.cuda.Stream
+    plain_wait = stream_cls.wait_stream
+    waits, seen = [], {}
+
+    def recording_wait(self, other):
+        waits.append((int(self.cuda_stream), int(other.cuda_stream)))
+        seen[int(self.cuda_stream)], seen[int(other.cuda_stream)] = self, other
+        return plain_wait(self, other)
+
+    monkeypatch.setattr(stream_cls, "wait_stream", recording_wait)
+    got = eng.powmod_nsquare_groups(jobs)
+    monkeypatch.undo()
+    cur = eng._stream_ptr()
+    sides = [w for w, o in waits if o == cur]
+    assert len(sides) == 2 and cur not in sides                       # one wait per job that has bases, before its launch
+    last_fan_out = max(k for k, (w, o) in enumerate(waits) if o == cur)
+    joined = {o for k, (w, o) in enumerate(waits) if w == cur and k > last_fan_out}
+    assert joined >= set(sides)                                        # the caller's stream waits for every stream that ran a job
+    eng.synchronize()
+    assert all(seen[s].query() for s in sides)
+    assert got == [[pow(b, e, n * n) for b in bases] for bases, e, n in jobs]
+    assert [len(g) for g in got] == [5, 0, 9]
+
+
 # ------------------------------------------------------------------ device modular inverse (PSK:50, PSK:89-91)
 @pytest.mark.parametrize("bits", [5, 64, 65, 1027, 2051, 2080, 4102, 6200, 8198, 16700])
 def test_modinv_direct_wave_kernel(eng, bits):
