@@ -487,6 +487,25 @@ int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void* d_table, i
  * max_entries written; returns their number. */
 int mx_fixedbase_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- random rows on the device: ChaCha20 keystream (ABI 4.4, additions) -------------------------------------------
+ *   d_out[r][j] = keystream word r * w + j,   r < count, j < w = ceil(bits / 32)
+ * of ChaCha20 as RFC 8439 specifies it (csrc/mx_chacha.hpp; tools/chacha_model.py is the bit-exact model): state = four
+ * constants, the eight key words, a 32-bit block counter in word 12, the three nonce words in words 13-15; twenty rounds
+ * and the feed-forward addition; output words in state order.  Keystream word i is word i mod 16 of block
+ * counter0 + i div 16.  The top word of every row is masked to bits mod 32 bits when that is not 0, words
+ * w .. row_words - 1 of every row are written as 0, and the unused tail of the last block is discarded (never carried into
+ * another call).  The mapping does not depend on the launch shape.  These rows are what mx_fixedbase_nsquare_run takes as
+ * d_exps and, at the width of N^2, what mx_powmod_nsquare_run takes as bases: exponents and randomness r without a host
+ * draw and an upload.
+ *   key, nonce: HOST arrays that travel by value in the kernel-argument block (they may be freed or overwritten on
+ *   return).  The caller owns the discipline that makes the stream unpredictable: a secret uniform key, and no
+ *   (key, nonce, block counter) triple used twice.
+ *   One launch on `stream`, no workspace, no synchronisation; count = 0 returns MX_OK without a launch.
+ *   MX_ERR_ARG for a null pointer, count < 0, bits < 1, bits > 32 * row_words, or a request whose blocks do not fit the
+ *   counter: counter0 + ceil(count * w / 16) > 2^32.  A refused call launches nothing. */
+int mx_chacha20_rows(const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, uint32_t* d_out, int64_t count,
+                     int row_words, int bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

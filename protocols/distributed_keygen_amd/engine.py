@@ -1136,8 +1136,16 @@ class Engine:
 
     def fixed_base_exponent_rows(self, exponents, exp_bits: int):
         """Exponents -> device rows ``[count, ceil(exp_bits / 32)]``: a sequence of ints below ``2^exp_bits`` (ValueError
-        otherwise), or a uint32 numpy array of that shape taken as it is (drawn bytes; the kernel masks the top bits)."""
+        otherwise), or a uint32 numpy array of that shape taken as it is (drawn bytes; the kernel masks the top bits),
+        or an int32 tensor of that shape already on this engine's device (random_rows_t), returned as it is — ValueError
+        if it lives on another device."""
         ewords = (int(exp_bits) + 31) // 32
+        if _is_device_rows(exponents):
+            if exponents.dim() != 2 or exponents.shape[1] != ewords or exponents.dtype != self.torch.int32:
+                raise ValueError(f"int32 exponent rows of {ewords} words expected")
+            if exponents.device != self.device:
+                raise ValueError(f"the exponent rows were drawn on {exponents.device}, the operation runs on {self.device}")
+            return exponents
         if isinstance(exponents, np.ndarray):
             if exponents.ndim != 2 or exponents.shape[1] != ewords:
                 raise ValueError(f"exponent rows of {ewords} words expected")
@@ -1281,6 +1289,71 @@ class Engine:
         n2, limbs = _nsquare(n)
         rn_t = self.powmod_nsquare_t(self._upload_ints(randomness, limbs, n2), n, n)
         return self._download_ints(self.mulmod_t(rn_t, self.to_device(rows(limbs, n2)), n2, out_t=rn_t))
+
+    # ------------------------------------------------------------------ randomness drawn on the device
+    def chacha20_rows_t(self, key: Sequence[int], nonce: Sequence[int], counter0: int, count: int, bits: int,
+                        row_words: Optional[int] = None):
+        """``[count, row_words]`` int32 rows of the ChaCha20 keystream (mx_chacha20_rows, csrc/mx_chacha.hpp) for the
+        eight key words, three nonce words and first block counter given: keystream word r * w + j in out[r][j] for
+        j < w = ceil(bits / 32), the top word masked to `bits`, zero beyond w.  The raw kernel call — the nonce
+        discipline that makes the rows fit for use as secrets is device_rng.DeviceRng's (random_rows_t)."""
+        count, bits, counter0 = int(count), int(bits), int(counter0)
+        words = (bits + 31) // 32
+        row_words = words if row_words is None else int(row_words)
+        if len(key) != 8 or len(nonce) != 3:
+            raise ValueError("eight key words and three nonce words expected")
+        if count < 0 or bits < 1 or row_words < words:
+            raise ValueError("count >= 0 and 1 <= bits <= 32 * row_words expected")
+        if not 0 <= counter0 <= 0xFFFFFFFF or counter0 + (count * words + 15) // 16 > 1 << 32:
+            raise ValueError("the request does not fit the 32-bit block counter")
+        out_t = self.torch.empty((count, row_words), dtype=self.torch.int32, device=self.device)
+        if count:
+            self._call("mx_chacha20_rows", (_ctypes.c_uint32 * 8)(*key), (_ctypes.c_uint32 * 3)(*nonce), counter0,
+                       out_t.data_ptr(), count, row_words, bits)
+        return out_t
+
+    def random_rows_t(self, rng, count: int, bits: int, row_words: Optional[int] = None):
+        """``count`` rows of ``bits`` random bits from the device generator `rng` (device_rng.DeviceRng), drawn on this
+        engine's current stream: ``[count, row_words]`` int32, what the ``*_t`` functions take as exponents or bases."""
+        return rng.rows_t(self, count, bits, row_words)
+
+    @_int_args
+    def encrypt_fresh_batch(self, messages: Sequence[int], n: int, rng, return_randomness: bool = False):
+        """Paillier encryption with g = n + 1 and randomness of the library's own: c = (1 + m n) * r^n mod n^2 with r
+        drawn on the device by `rng` (device_rng.DeviceRng) — ``encrypt_batch`` without the list of r.
+
+        r is drawn as bits(n) + 64 random bits in a row of the width of n^2.  Since (r + k n)^n = r^n (mod n^2), the
+        pair kernel computes (r mod n)^n without a reduction, and r mod n is uniform on [0, n) up to a bias below 2^-64.
+        ValueError for an n so small that bits(n) + 64 > bits(n^2) - 1 (r must stay below n^2).
+
+        NO coprimality check is made: r mod n shares a factor with n with probability about 2^(1 - bits(n) / 2) (it is
+        then a multiple of p or q, or 0), the ciphertext would not decrypt, and the event would factor n — at the key
+        lengths in use it does not happen.  The reference's scheme rejects such an r; a caller who must do the same
+        asks for the randomness and checks it.
+
+        ``return_randomness``: the result is ``(ciphertexts, [r, ...])`` with the drawn r as ints (not reduced modulo
+        n) — for tests and for callers who must log their randomness."""
+        return self._fresh_rn(messages, n, rng, return_randomness,
+                              lambda limbs, n2: _limbs.pack([(1 + (m % n) * n) % n2 for m in messages], limbs))
+
+    @_int_args
+    def randomize_fresh_batch(self, ciphertexts: Sequence[int], n: int, rng, return_randomness: bool = False):
+        """Re-randomisation c * r^n mod n^2 with r drawn on the device by `rng` — ``randomize_batch`` without the list
+        of r; what is drawn, what is not checked and ``return_randomness`` as in encrypt_fresh_batch."""
+        return self._fresh_rn(ciphertexts, n, rng, return_randomness,
+                              lambda limbs, n2: _limbs.pack_reduced(ciphertexts, limbs, n2))
+
+    def _fresh_rn(self, values, n: int, rng, return_randomness: bool, rows):
+        n2, limbs = _nsquare(n)
+        r_bits = n.bit_length() + 64
+        if r_bits > n2.bit_length() - 1:
+            raise ValueError(f"a modulus of {n.bit_length()} bits leaves no room for 64 extra bits of randomness below n^2")
+        if len(values) == 0:
+            return ([], []) if return_randomness else []
+        r_t = self.random_rows_t(rng, len(values), r_bits, limbs)
+        rn_t = self.powmod_nsquare_t(r_t, n, n)      # leaves r_t as it is; the rows are packed while it runs, as in _times_rn
+        out = self._download_ints(self.mulmod_t(rn_t, self.to_device(rows(limbs, n2)), n2, out_t=rn_t))
+        return (out, self._download_ints(r_t)) if return_randomness else out
 
     # ------------------------------------------------------------------ Shamir field of the key generation
     @_int_args
@@ -1761,6 +1834,11 @@ def _check_rows_n2(n: int, limbs2: int) -> None:
 def _is_device_pair(x) -> bool:
     """An operand that is already on the device: (rows, max bits)."""
     return isinstance(x, tuple) and len(x) == 2 and hasattr(x[0], "data_ptr")
+
+
+def _is_device_rows(x) -> bool:
+    """Rows that are already a device tensor (not a numpy array, not a sequence of ints)."""
+    return hasattr(x, "data_ptr") and hasattr(x, "device")
 
 
 _default_engine: Optional[Engine] = None
