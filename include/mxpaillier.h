@@ -434,6 +434,39 @@ int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_input
  * max_entries written; returns their number. */
 int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- encrypted matrix products over a batch of ciphertext vectors (ABI 4.4, additions) ---------------------------
+ *   d_out[b][j] = prod_{t < terms} T(d_index[j][t], b) ^ w[j][t]  mod N^2,   w[j][t] >= 0,  j < n_rows,  b < tile_batch
+ * — the multi-exponentiation above with the weight rows SHARED by every sample of a tile (csrc/mx_matmul_n2.hpp): the
+ * same table pass over n_cols * tile_batch + n_shared inputs, then one group of lanes per (weight row, sample), the
+ * groups of a wavefront being consecutive samples of one row.  d_index and d_weights are per WEIGHT ROW, never per sample.
+ *   d_inputs:  [n_cols * tile_batch + n_shared][limbs2] residues < N^2: row c * tile_batch + b is table column c of
+ *              sample b (column-major), followed by the n_shared rows that do not depend on the sample (the bias inputs
+ *              1 + (b_j mod N) N), stored once.  NULL = the tables already in the workspace (an earlier run with the same
+ *              inputs, n_cols, n_shared, tile_batch, window and workspace on the same stream)
+ *   d_index:   [n_rows][terms] int32: a value c >= 0 names table column c (read at the sample's offset), a value
+ *              s < 0 names the shared table -1 - s (read without it);  d_weights: [n_rows][terms][(weight_bits + 31) / 32]
+ *   d_out:     [tile_batch][n_rows][limbs2], sample-major
+ * A digit that is zero costs no multiplication.  THE WEIGHTS MUST BE PUBLIC: the kernel's control flow depends on them.
+ * The shape query: the window of the cost model above for ONE sample (n_inputs = n_cols, n_outputs = n_rows; `window`
+ * > 0 overrides it), lowered until one sample's tables fit table_budget_bytes; *tile_batch = the largest sample count
+ * <= batch whose per-sample tables fit (at least 1); *chunk_terms = the split-K rule above for n_rows * *tile_batch
+ * outputs.  MX_ERR_ARG for a null pointer, a zero or negative size, window outside 1 .. 8 (0 .. 8 in the shape query),
+ * weight_bits above 2 * bits(N) + 64, or rows too narrow for N^2; MX_ERR_SIZE outside the narrow geometry (limbs_per_lane 9
+ * or 0, groups of up to 32 lanes), for n_cols, n_rows or terms above 2^31, or beyond one grid; MX_ERR_WORKSPACE for a workspace below the query's size.  Everything
+ * is checked before anything is enqueued.  Results are canonical residues in [0, N^2), NOT fresh ciphertexts. */
+int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_rows, int64_t terms, int weight_bits, int64_t batch,
+                            int64_t table_budget_bytes, int limbs_per_lane, int window, int* lanes,
+                            int* limbs_per_lane_out, int* window_out, int64_t* tile_batch, int64_t* chunk_terms);
+int64_t mx_matmul_nsquare_workspace_bytes(int n_bits, int64_t n_cols, int64_t n_shared, int64_t tile_batch,
+                                          int limbs_per_lane, int window);
+int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_cols, int64_t n_shared,
+                          int64_t tile_batch, int limbs2, const int32_t* d_index, const uint32_t* d_weights, int terms,
+                          int weight_bits, uint32_t* d_out, int64_t n_rows, int limbs_per_lane, int window,
+                          void* d_workspace, int64_t workspace_bytes, void* stream);
+/* The kernel instances mx_matmul_nsquare_run can select: (lanes per element, limbs per lane) pairs, at most max_entries
+ * written; returns their number. */
+int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 /* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
  *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
  * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of

@@ -100,6 +100,10 @@ SYMBOLS = {
     "mx_multiexp_nsquare_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int]),
     "mx_multiexp_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_multiexp_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_matmul_nsquare_shape": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_int, *[POINTER(c_int)] * 3, POINTER(c_int64), POINTER(c_int64)]),
+    "mx_matmul_nsquare_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int64, c_int, c_int]),
+    "mx_matmul_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_matmul_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_fixedbase_nsquare_shape": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, *_P4]),

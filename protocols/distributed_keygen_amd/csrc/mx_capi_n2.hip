@@ -5,6 +5,7 @@
 #include "mx_powmod_n2_split.hpp"
 #include "mx_bipair.hpp"
 #include "mx_multiexp_n2.hpp"
+#include "mx_matmul_n2.hpp"
 #include "mx_pack_n2.hpp"
 #include "mx_fixedbase_n2.hpp"
 
@@ -1052,4 +1053,123 @@ extern "C" int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void*
   const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
   return mxf::launch_fixedbase(g.K, 2, a, (count + gpw - 1) / gpw, s);
+}
+
+// ---- encrypted matrix products over a batch of ciphertext vectors (mx_matmul_n2.hpp) ---------------------------------
+namespace mxmm { int launch_matmul(int K, const mx::MatmulN2Args& a, int64_t nblocks, hipStream_t s); }
+
+extern "C" int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_rows, int64_t terms, int weight_bits,
+                                       int64_t batch, int64_t table_budget_bytes, int limbs_per_lane, int window,
+                                       int* lanes, int* limbs_per_lane_out, int* window_out, int64_t* tile_batch,
+                                       int64_t* chunk_terms) {
+  if (!lanes || !limbs_per_lane_out || !window_out || !tile_batch || !chunk_terms) return MX_ERR_ARG;
+  if (n_cols < 0 || n_rows < 0 || terms < 0 || weight_bits < 0 || batch < 0 || table_budget_bytes < 0) return MX_ERR_ARG;
+  if (window < 0 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  // counts beyond what one launch takes (mx_matmul_nsquare_run) are refused here too; this keeps every product below
+  // inside 64 bits: 2^31 columns of at most 2^20 bytes, 2^31 rows of at most 2^30 samples, and terms * outputs is formed
+  // only for fewer outputs than fill the device
+  const int64_t lim = (int64_t)1 << 31;
+  if (n_cols > lim || n_rows > lim || terms > lim) return MX_ERR_SIZE;
+  *lanes = g.K;
+  *limbs_per_lane_out = g.L;
+  // the window of ONE sample's map (every sample pays for its own tables), limited so that one sample's tables fit
+  const int64_t entry_bytes = (int64_t)2 * g.K * g.L * 4;
+  int w = window > 0 ? window : multiexp_window(n_cols, n_rows, terms, weight_bits);
+  if (window == 0)
+    while (w > 1 && n_cols * (entry_bytes << w) > table_budget_bytes) --w;
+  *window_out = w;
+  const int64_t per_sample = n_cols * (entry_bytes << w);
+  int64_t tile = per_sample > 0 ? table_budget_bytes / per_sample : batch;
+  if (tile > batch) tile = batch;
+  if (tile > (int64_t)1 << 30) tile = (int64_t)1 << 30;
+  if (tile < 1) tile = 1;
+  *tile_batch = tile;
+  // split-K by the rule of mx_multiexp_nsquare_shape, on the outputs of one tile
+  const int64_t target = (int64_t)device_cus() * 4 * (64 / g.K);
+  const int64_t n_outputs = n_rows * tile;
+  int64_t chunk = terms;
+  if (n_outputs > 0 && n_outputs < target && terms > 64) {
+    chunk = (terms * n_outputs + target - 1) / target;
+    if (chunk < 64) chunk = 64;
+  }
+  *chunk_terms = chunk < 1 ? 1 : chunk;
+  return MX_OK;
+}
+
+extern "C" int64_t mx_matmul_nsquare_workspace_bytes(int n_bits, int64_t n_cols, int64_t n_shared, int64_t tile_batch,
+                                                     int limbs_per_lane, int window) {
+  if (n_cols < 0 || n_shared < 0 || tile_batch < 1 || tile_batch > ((int64_t)1 << 30) || n_cols > ((int64_t)1 << 31) ||
+      n_shared > ((int64_t)1 << 31)) return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  // the table pass runs one group per table in one grid: at most 2^31 wavefronts — which also keeps the byte count
+  // (below 2^37 tables of at most 2^19 bytes) inside 64 bits
+  const int64_t n_tables = n_cols * tile_batch + n_shared;
+  const int gpw = 64 / g.K;
+  if ((n_tables + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
+  return mx_multiexp_nsquare_workspace_bytes(n_bits, n_tables, limbs_per_lane, window);
+}
+
+extern "C" int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_cols, int64_t n_shared,
+                                     int64_t tile_batch, int limbs2, const int32_t* d_index, const uint32_t* d_weights,
+                                     int terms, int weight_bits, uint32_t* d_out, int64_t n_rows, int limbs_per_lane,
+                                     int window, void* d_ws, int64_t ws_bytes, void* stream) {
+  if (!plan || !plan->d_plan || !d_out || !d_ws || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_cols < 0 || n_shared < 0 || n_cols > ((int64_t)1 << 31) || n_shared > ((int64_t)1 << 31)) return MX_ERR_ARG;
+  if (tile_batch < 1 || tile_batch > ((int64_t)1 << 30) || n_rows <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
+  if (n_cols * tile_batch + n_shared <= 0) return MX_ERR_ARG;
+  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
+  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  const int gpw = 64 / g.K;
+  const int64_t tile_blocks = (tile_batch + gpw - 1) / gpw;
+  if (n_rows > ((int64_t)1 << 31) / tile_blocks - 1) return MX_ERR_SIZE;      // more wavefronts than one grid holds
+  const int64_t n_tables = n_cols * tile_batch + n_shared;
+  if ((n_tables + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
+  const int64_t need = mx_matmul_nsquare_workspace_bytes(bits, n_cols, n_shared, tile_batch, LIMBS_PER_LANE, window);
+  if (need < 0) return (int)need;
+  if (need > ws_bytes) return MX_ERR_WORKSPACE;
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  const u32* consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs, tile and window)
+  if (d_inputs) {
+    mx::MultiexpN2Args t{};
+    t.inputs = d_inputs;
+    t.tables = (u32*)d_ws;
+    t.consts = consts;
+    t.n_inputs = n_tables;
+    t.window = window;
+    t.limbsn = plan->limbs_n; t.limbs2 = limbs2; t.nblk = g.nblk; t.ksplit = bits - 1;
+    MX_TRY(mxm::launch_multiexp(g.K, true, t, (n_tables + gpw - 1) / gpw, s));
+  }
+  mx::MatmulN2Args a{};
+  a.tables = (const u32*)d_ws;
+  a.consts = consts;
+  a.index = d_index;
+  a.weights = d_weights;
+  a.out = d_out;
+  a.n_cols = n_cols; a.n_shared = n_shared; a.rows = n_rows;
+  a.tile = (int)tile_batch; a.tile_blocks = (int)tile_blocks;
+  a.terms = terms;
+  a.wwords = (weight_bits + 31) / 32;
+  a.window = window;
+  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk;
+  return mxmm::launch_matmul(g.K, a, n_rows * tile_blocks, s);
 }

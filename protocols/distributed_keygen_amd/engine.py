@@ -1015,6 +1015,78 @@ class Engine:
         """The encrypted W x + b: [(1 + (b_j mod n) n) prod_i cts[i]^W[j][i] mod n^2 for j] (rows dense or {index: weight})."""
         return self._linear_map_ints(cts, list(weights), n, bias, fixed_base=fixed_base)
 
+    # ------------------------------------------------------------------ encrypted matrix products over a batch of vectors
+    def matmul_nsquare_shape(self, n: int, n_cols: int, n_rows: int, terms: int, weight_bits: int, batch: int,
+                             table_budget: int, window: int = 0) -> Tuple[int, int, int]:
+        """(window, samples per tile, split-K chunk in terms) of mx_matmul_nsquare_shape."""
+        k, l, w, tile, chunk = self._query("mx_matmul_nsquare_shape", int(n).bit_length(), n_cols, n_rows, terms, weight_bits,
+                                           int(batch), int(table_budget), 0, int(window),
+                                           outs=_INTS[:3] + (_ctypes.c_int64, _ctypes.c_int64))
+        return w, int(tile), int(chunk)
+
+    def _matmul_plan(self, n: int, n_inputs: int, batch: int, weights, bias, window: int = 0, table_budget=None):
+        from . import multiexp_plan as mp
+
+        _check_modulus(n)
+        return mp.plan_matmul(weights, n_inputs, n, bias, batch,
+                              lambda *a: self.matmul_nsquare_shape(n, *a),
+                              table_budget=mp.TABLE_BUDGET_BYTES if table_budget is None else int(table_budget), window=int(window))
+
+    def matmul_nsquare_t(self, x_t, batch: int, weights, n: int, bias: Optional[Sequence[int]] = None, window: int = 0,
+                         table_budget: Optional[int] = None):
+        """Y[b][j] = (1 + (bias_j mod n) n) * prod_i X[b][i]^W[j][i]  mod n^2 for a batch of ciphertext vectors and ONE
+        public matrix W, on the device (csrc/mx_matmul_n2.hpp).
+
+        ``x_t``: ``[batch * n_inputs, limbs2]`` rows of residues below n^2, sample-major; ``weights``: one row per output,
+        a dense sequence of ``n_inputs`` signed ints or a sparse ``{column: weight}`` — PUBLIC values: the kernel skips
+        their zero digits; ``bias``: one plaintext per output or None.  A negative weight uses the inverses of its column
+        (one product tree per call; ValueError like ``pow`` if a sample has none), a zero weight gives 1 even for a zero
+        input.  ``window`` > 0 overrides the library's window, ``table_budget`` the bytes of tables one tile of samples may
+        take (multiexp_plan.TABLE_BUDGET_BYTES).  Returns ``[batch * n_outputs, limbs2]`` canonical residues, sample-major,
+        on the current stream — not fresh ciphertexts.  The planning (column sign split, shared bias tables, tiles,
+        split-K, buckets) is multiexp_plan.plan_matmul: once per call, whatever the batch."""
+        n, batch = int(n), int(batch)
+        _check_modulus(n)
+        rows = x_t.shape[0]
+        if batch < 0 or (batch == 0 and rows) or (batch and rows % batch):
+            raise ValueError("x_t must hold batch * n_inputs rows")
+        n_inputs = rows // batch if batch else 0
+        return self._matmul_run_t(x_t, batch, n, self._matmul_plan(n, n_inputs, batch, weights, bias, window, table_budget))
+
+    def _matmul_run_t(self, x_t, batch: int, n: int, plan):
+        """matmul_nsquare_t with the plan of _matmul_plan already made (for the same n, batch and row width)."""
+        from . import multiexp_plan as mp
+
+        limbs2 = x_t.shape[1]
+        _check_rows_n2(n, limbs2)
+        if x_t.shape[0] != batch * plan.n_inputs:
+            raise ValueError("x_t must hold batch * n_inputs rows")
+        return mp.execute_matmul(plan, _MatmulBackend(self, n, limbs2, n.bit_length()), x_t, batch)
+
+    @_int_args
+    def ciphertext_matmul_batch(self, samples: Sequence[Sequence[int]], weights, n: int, bias: Optional[Sequence[int]] = None,
+                                fixed_base=None) -> List[List[int]]:
+        """The encrypted W x_b + bias of every sample: [[(1 + (bias_j mod n) n) prod_i samples[b][i]^W[j][i] mod n^2 for j]
+        for b] — one public W (rows dense or {column: weight}) over a batch of ciphertext vectors of equal length."""
+        samples = [list(smp) for smp in samples]
+        if not samples:
+            return []
+        n_inputs = len(samples[0])
+        for b, smp in enumerate(samples):
+            if len(smp) != n_inputs:
+                raise ValueError(f"sample {b} has {len(smp)} ciphertexts, sample 0 has {n_inputs}")
+        weights = weights if isinstance(weights, np.ndarray) else list(weights)
+        n2, limbs2 = _nsquare(n)
+        plan = self._matmul_plan(n, n_inputs, len(samples), weights, bias)         # every refusal of W and bias: before any launch
+        if plan.n_rows == 0:
+            return [[] for _ in samples]
+        if n_inputs:
+            x_t = self._upload_ints([c for smp in samples for c in smp], limbs2, n2)
+        else:
+            x_t = self.torch.empty((0, limbs2), dtype=self.torch.int32, device=self.device)
+        flat = self._download_ints(self._freshened(self._matmul_run_t(x_t, len(samples), n, plan), fixed_base))
+        return [flat[b * plan.n_rows : (b + 1) * plan.n_rows] for b in range(len(samples))]
+
     # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
     def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
         """out[j] = prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 on the device (csrc/mx_pack_n2.hpp):
@@ -1806,6 +1878,72 @@ class _MultiexpBackend:
         return self.take(pool, index)
 
     rows_of = assemble = _pick          # the two names multiexp_plan.execute calls
+
+
+class _MatmulBackend:
+    """multiexp_plan.execute_matmul over device rows of one Engine and modulus.  A column block is a tensor
+    [columns, samples, limbs2]; the launch arrays go to the device once per call."""
+
+    def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
+        self.eng, self.n, self.limbs2, self.n_bits = eng, n, limbs2, n_bits
+        self.torch = eng.torch
+        self.plan = eng.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+        self._arrays: Dict[int, Tuple[Any, Any]] = {}
+
+    def _index(self, positions):
+        return self.torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.eng.device)
+
+    def _empty(self, rows: int = 0):
+        return self.torch.empty((rows, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
+
+    def columns(self, inputs_t, n_inputs, batch, cols):
+        return inputs_t.view(batch, n_inputs, self.limbs2).index_select(1, self._index(cols)).permute(1, 0, 2).contiguous()
+
+    def invert(self, block_t):
+        return self.eng.modinv_t(block_t.view(-1, self.limbs2), self.n * self.n).view_as(block_t)
+
+    def tile(self, block_t, batch, lo, hi):
+        return block_t[:, lo:hi, :].reshape(-1, self.limbs2)
+
+    def bias_rows(self, residues):
+        return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
+
+    def concat(self, parts):
+        return self._empty() if not parts else (parts[0] if len(parts) == 1 else self.torch.cat(parts, dim=0))
+
+    def run_matmul(self, tables_t, n_cols, n_shared, tile, launch, window):
+        eng = self.eng
+        rows, terms = launch.index.shape
+        if id(launch) not in self._arrays:
+            self._arrays[id(launch)] = (eng.to_device(launch.index.view(np.uint32)), eng.to_device(launch.weights.reshape(rows, -1)))
+        idx_t, w_t = self._arrays[id(launch)]
+        out_t = self._empty(tile * rows)
+        if tables_t is not None:
+            tables_t = tables_t.contiguous()
+            if tables_t.shape[0] != n_cols * tile + n_shared:
+                raise ValueError("table rows do not match the launch")
+        eng._call("mx_matmul_nsquare_run", self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_cols, n_shared,
+                  tile, self.limbs2, idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, out_t.data_ptr(), rows, 0, window,
+                  workspace=("mx_matmul_nsquare_workspace_bytes", self.n_bits, n_cols, n_shared, tile, 0, window), plans=(self.plan,))
+        return out_t
+
+    def select(self, outs, picks, tile, column_major):
+        torch = self.torch
+        if not picks:
+            return self._empty()
+        views = [o.view(tile, -1, self.limbs2) for o in outs]
+        first = [0]
+        for v in views:
+            first.append(first[-1] + v.shape[1])
+        if any(pk is None for pk in picks):
+            one = torch.zeros((tile, 1, self.limbs2), dtype=torch.int32, device=self.eng.device)
+            one[:, 0, 0] = 1
+            views.append(one)
+        pool = views[0] if len(views) == 1 else torch.cat(views, dim=1)
+        sel = pool.index_select(1, self._index([first[-1] if pk is None else first[pk[0]] + pk[1] for pk in picks]))
+        if column_major:
+            sel = sel.permute(1, 0, 2)
+        return sel.reshape(-1, self.limbs2)
 
 
 def _check_modulus(mod: int) -> None:

@@ -7,7 +7,10 @@ them to many ciphertexts at once:
   * ``scale``: c_i^(k_i) — a scalar of any sign per ciphertext;
   * ``add`` / ``neg``: c_i * d_i and c_i^-1;
   * ``sum_groups``: the product of every group (ragged groups, any size);
-  * ``linear_map``: the encrypted W x + b (dense rows or sparse ``{index: weight}`` rows, optional plaintext bias).
+  * ``linear_map``: the encrypted W x + b (dense rows or sparse ``{index: weight}`` rows, optional plaintext bias);
+  * ``matmul``: the same public W applied to a BATCH of ciphertext vectors (encrypted scoring, linear layers): W is
+    planned and uploaded once, and the kernel reads every weight row once per wavefront of samples.  The weights are
+    public plaintexts — the kernel's control flow depends on them.
 
 Ciphertexts are ints or objects with ``get_value()`` (the reference's ``PaillierCiphertext``); for objects the modulus
 comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` is called once per distinct object.  The
@@ -103,3 +106,21 @@ def linear_map(cts: Sequence[Any], weights: Sequence[Any], n: Optional[int] = No
     vals, n = _values(cts, n)
     weights = list(weights)
     return _engine(engine).ciphertext_linear_map_batch(vals, weights, n, bias=bias, **_fresh(randomizer, n, len(weights)))
+
+
+def matmul(x: Sequence[Sequence[Any]], weights: Sequence[Any], n: Optional[int] = None, bias: Optional[Sequence[int]] = None,
+           engine: Any = None, randomizer: Any = None) -> List[List[int]]:
+    """The encrypted W x_b + bias of every sample x_b of a batch: [[(1 + (bias_j mod N) N) prod_i x[b][i]^(W_ji) mod N^2
+    for every row j of W] for every b].  All samples have the same length; W (dense rows or ``{column: weight}``) and the
+    bias are public plaintexts."""
+    samples = [list(smp) for smp in x]
+    if not samples:
+        return []
+    for b, smp in enumerate(samples):
+        if len(smp) != len(samples[0]):
+            raise ValueError(f"sample {b} has {len(smp)} ciphertexts, sample 0 has {len(samples[0])}")
+    flat, n = _values([c for smp in samples for c in smp], n)
+    width = len(samples[0])
+    vals = [flat[b * width : (b + 1) * width] for b in range(len(samples))]
+    weights = weights if hasattr(weights, "shape") else list(weights)
+    return _engine(engine).ciphertext_matmul_batch(vals, weights, n, bias=bias, **_fresh(randomizer, n, len(samples) * len(weights)))

@@ -18,6 +18,9 @@ A call is turned into launches of ``mx_multiexp_nsquare_run``, which takes non-n
     term by term.
 
 ``execute`` runs a plan against a backend (the engine's device tensors, or the test double's Python ints).
+
+``plan_matmul`` / ``execute_matmul`` (at the end) are the batched form, csrc/mx_matmul_n2.hpp: one public W applied to a
+batch of ciphertext vectors, planned once per call whatever the batch.
 """
 
 from __future__ import annotations
@@ -364,3 +367,165 @@ def execute(plan: Plan, be: Any, inputs: Any) -> Any:
     for kind, v in plan.result:
         picks.append(None if kind == "one" else (p1_out[v] if kind == "p1" else p2_out[v]))
     return be.assemble(picks)
+
+
+# ---- encrypted matrix products over a batch of ciphertext vectors (csrc/mx_matmul_n2.hpp) ----------
+#
+#     Y[b][j] = (1 + (bias_j mod N) N) * prod_i X[b][i]^(W[j][i])   mod N^2
+#
+# The weight rows are shared by every sample, so everything below is planned ONCE per call, whatever the batch:
+#
+#   * W is normalised once (dense int64 rows as array operations on the block, anything else through normalize_rows);
+#   * sign split BY COLUMN: a column used with a negative weight anywhere gets a second table column, built from the
+#     inverses of that column's samples (one product tree per call over every inverted column of every sample);
+#   * the bias is one SHARED table per row with a non-zero bias: index -1 - k in the launch arrays, stored once per tile
+#     behind the per-sample tables (the kernel reads it without the sample's offset);
+#   * tiles of `tile_batch` samples under the table budget, the last one ragged;
+#   * split-K: pieces of a row's term list are extra weight rows, and the second pass is itself a shared-weight
+#     product (weights 1, window 1) whose table columns are the split rows' pieces of every sample;
+#   * buckets of weight rows of similar length, as _bucket_launches makes them.
+#
+# The launch arrays have one leading entry per weight row (times pieces) and are reused by every tile.
+
+@dataclass
+class MatmulPlan:
+    n_rows: int
+    n_inputs: int
+    x_cols: List[int]                     # input columns with a table of their own (a positive weight somewhere), ascending
+    inverted: List[int]                   # input columns whose inverses get a table column (a negative weight somewhere)
+    bias: Dict[int, int]                  # row -> b mod N (non-zero); shared table k belongs to sorted(bias)[k]
+    window: int
+    tile_batch: int
+    chunk: int
+    launches: List[Launch]                # pass 1: Launch.rows are pass-1 weight rows; index >= 0: table column
+                                          # (x_cols, then inverted), index < 0: shared table -1 - index
+    pass1_rows: int
+    part_rows: List[int]                  # pass-1 rows that are pieces of split rows = the table columns of pass 2
+    combine: List[Launch]                 # pass 2 (empty if no row was split): Launch.rows are pass-2 rows
+    result: List[Tuple[str, int]]         # per weight row: ("one", 0) | ("p1", pass-1 row) | ("p2", pass-2 row)
+
+    @property
+    def n_cols(self) -> int:
+        return len(self.x_cols) + len(self.inverted)
+
+
+def _matmul_rows(weights: Sequence[Any], n_inputs: int, n: int) -> List[Tuple[List[int], List[int]]]:
+    """Per weight row (columns, signed weights) with the zero weights dropped, columns ascending: the dense int64 block
+    by array operations, anything else (sparse, mixed, weights beyond int64) through normalize_rows.  ValueError as
+    normalize_rows raises it."""
+    block = _dense_block(weights, n_inputs)
+    if block is not None:                          # (an int64 weight is always within the bound)
+        out = []
+        for row in block:
+            nz = np.flatnonzero(row)
+            out.append((nz.tolist(), row[nz].tolist()))
+        return out
+    return [([i for i, _ in row], [w for _, w in row]) for row in normalize_rows(weights, n_inputs, n)]
+
+
+def plan_matmul(weights: Sequence[Any], n_inputs: int, n: int, bias: Optional[Sequence[int]], batch: int,
+                shape: Callable[[int, int, int, int, int, int, int], Tuple[int, int, int]],
+                table_budget: int = TABLE_BUDGET_BYTES, window: int = 0) -> MatmulPlan:
+    """The launches of one batched matrix product.  `weights`: one row per output, a dense sequence of `n_inputs` signed
+    ints or a sparse ``{column: weight}`` (they may be mixed).  ``shape(n_cols, n_rows, terms, weight_bits, batch,
+    table_budget, window) -> (window, tile_batch, chunk_terms)`` is the library's choice (mx_matmul_nsquare_shape).
+    Raises ValueError — before anything is launched — for a row of the wrong length, a bad column, a weight out of
+    bounds or a bias of the wrong length."""
+    weights = weights if isinstance(weights, np.ndarray) else list(weights)
+    n_rows = len(weights)
+    if bias is not None and len(bias) != n_rows:
+        raise ValueError(f"{len(bias)} bias values for {n_rows} outputs")
+    rows = _matmul_rows(weights, n_inputs, n)
+    bias_res = {j: int(b) % n for j, b in enumerate(bias)} if bias is not None else {}
+    bias_res = {j: b for j, b in bias_res.items() if b}
+    shared_of = {j: k for k, j in enumerate(sorted(bias_res))}
+    pos, neg = set(), set()
+    for cols, ws in rows:
+        for i, w in zip(cols, ws):
+            (pos if w > 0 else neg).add(i)
+    x_cols, inverted = sorted(pos), sorted(neg)
+    x_of = {i: c for c, i in enumerate(x_cols)}
+    inv_of = {i: len(x_cols) + c for c, i in enumerate(inverted)}
+    term_rows: List[List[Term]] = []
+    for j, (cols, ws) in enumerate(rows):
+        terms = [(x_of[i], w) if w > 0 else (inv_of[i], -w) for i, w in zip(cols, ws)]
+        if j in shared_of:
+            terms.append((-1 - shared_of[j], 1))
+        term_rows.append(terms)
+    max_terms = max((len(r) for r in term_rows), default=0)
+    max_bits = max((w.bit_length() for r in term_rows for _, w in r), default=0)
+    win, tile, chunk = shape(len(x_cols) + len(inverted), n_rows, max_terms, max_bits, int(batch), int(table_budget), int(window))
+    tile, chunk = max(1, int(tile)), max(1, int(chunk))
+    # split-K: pieces of a row are weight rows of their own
+    p1: List[List[Term]] = []
+    result: List[Tuple[str, int]] = []
+    split: List[List[int]] = []
+    for terms in term_rows:
+        if not terms:
+            result.append(("one", 0))
+            continue
+        ks = []
+        for lo in range(0, len(terms), chunk):
+            ks.append(len(p1))
+            p1.append(terms[lo : lo + chunk])
+        if len(ks) == 1:
+            result.append(("p1", ks[0]))
+        else:
+            result.append(("p2", len(split)))
+            split.append(ks)
+    launches = _bucket_launches(p1, list(range(len(p1))))
+    part_rows = [k for ks in split for k in ks]
+    combine: List[Launch] = []
+    if split:
+        local, at = [], 0
+        for ks in split:
+            local.append([(at + t, 1) for t in range(len(ks))])
+            at += len(ks)
+        combine = _bucket_launches(local, list(range(len(split))))
+    return MatmulPlan(n_rows, n_inputs, x_cols, inverted, bias_res, int(win), tile, chunk, launches, len(p1), part_rows,
+                      combine, result)
+
+
+def execute_matmul(plan: MatmulPlan, be: Any, inputs: Any, batch: int) -> Any:
+    """Runs `plan` on backend `be` over the sample-major input rows `inputs` (row b * n_inputs + i) and returns the
+    sample-major result rows (row b * n_rows + j).  A "column block" is a set of rows [column][sample], column-major.
+    The backend provides
+      ``columns(inputs, n_inputs, batch, cols)``: the column block of the listed input columns over all samples;
+      ``invert(block)``: its element-wise inverse (ValueError if some row is not invertible);
+      ``tile(block, batch, lo, hi)``: the block restricted to samples lo .. hi - 1;
+      ``bias_rows(residues)``: the rows 1 + b N;  ``concat(parts)``: row sets one behind the other;
+      ``run_matmul(table_rows or None, n_cols, n_shared, tile, launch, window)``: the sample-major results
+        [tile][len(launch.rows)] of one launch (None: the tables of the previous launch are still in place);
+      ``select(outs, picks, tile, column_major)``: from the results of several launches, for every sample the entries
+        picks = [(launch, row) or None (= one)] — sample-major [tile][len(picks)], or as a column block.
+    The engine's device form is engine._MatmulBackend; tests/test_matmul_host.py has one over Python ints."""
+    if batch == 0:
+        return be.concat([])
+    n_cols, shared = plan.n_cols, sorted(plan.bias)
+    x_block = be.columns(inputs, plan.n_inputs, batch, plan.x_cols) if plan.x_cols else None
+    inv_block = be.invert(be.columns(inputs, plan.n_inputs, batch, plan.inverted)) if plan.inverted else None
+    bias_rows = be.bias_rows([plan.bias[j] for j in shared]) if shared else None
+    where1 = {rid: (k, r) for k, launch in enumerate(plan.launches) for r, rid in enumerate(launch.rows)}
+    where2 = {rid: (len(plan.launches) + k, r) for k, launch in enumerate(plan.combine) for r, rid in enumerate(launch.rows)}
+    part_picks = [where1[m] for m in plan.part_rows]
+    picks = [None if kind == "one" else (where1[v] if kind == "p1" else where2[v]) for kind, v in plan.result]
+    results = []
+    for lo in range(0, batch, plan.tile_batch):
+        hi = min(batch, lo + plan.tile_batch)
+        t = hi - lo
+        outs = []
+        if plan.launches:
+            parts = [be.tile(blk, batch, lo, hi) for blk in (x_block, inv_block) if blk is not None]
+            if bias_rows is not None:
+                parts.append(bias_rows)
+            tables = be.concat(parts)
+            for launch in plan.launches:
+                outs.append(be.run_matmul(tables, n_cols, len(shared), t, launch, plan.window))
+                tables = None
+        if plan.combine:
+            tables = be.select(outs, part_picks, t, True)
+            for launch in plan.combine:
+                outs.append(be.run_matmul(tables, len(part_picks), 0, t, launch, 1))
+                tables = None
+        results.append(be.select(outs, picks, t, False))
+    return be.concat(results)
