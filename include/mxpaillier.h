@@ -485,6 +485,30 @@ int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_cts, int6
  * written; returns their number. */
 int mx_pack_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- slot-packed plaintexts: the codec between int64 values and plaintext rows (ABI 4.4, additions) ---------------
+ * The layout of the packing above, produced BEFORE encryption: value j * slots + i occupies bits
+ * [slot_bits * i, slot_bits * (i + 1)) of plaintext j, j < ceil(count / slots); the last plaintext holds the remaining
+ * values, its missing slots count as 0 (csrc/mx_slots.hpp).
+ *   is_signed != 0: values in [-2^(slot_bits-1), 2^(slot_bits-1)), slot_bits 1 .. 64; plaintext j is
+ *                   (sum_i m_(j slots + i) 2^(slot_bits i)) mod N, and decode reads a residue v > N div 2 as v - N
+ *   is_signed == 0: values in [0, 2^slot_bits), slot_bits 1 .. 63
+ * mx_slots_encode writes d_out [ceil(count / slots)][out_stride] rows — the canonical residue in [0, N) in the first
+ * limbs_n words, zeros beyond — and d_status [ceil(count / slots)]: 1 if any value of that plaintext lies outside the
+ * slot range (its row is then unspecified), else 0.  These rows are what mx_fixedbase_nsquare_run takes as the operand
+ * of MX_FIXEDBASE_ENCRYPT.
+ * mx_slots_decode reads d_rows [ceil(count / slots)][row_stride] residues in [0, N) — words at limbs_n and beyond are
+ * ignored, so the rows of mx_combine_run with out_stride = limbs + 1 are taken as they are — and writes d_out [count].
+ * Any residue decodes: fields are extracted from ((v or v - N) + offset) mod 2^(slot_bits * slots), so values that had
+ * overflowed their slots come out as they would from the same arithmetic on integers.
+ *   h_n: limbs_n HOST words, travelling by value in the kernel-argument block (limbs_n <= 258, MX_ERR_SIZE beyond).
+ *   MX_ERR_ARG for a null pointer, count < 0, slots < 1, slot_bits outside its range, slot_bits * slots > bits(N) - 2
+ *   or a stride below limbs_n; MX_ERR_MODULUS for an even N.  count = 0 returns MX_OK without a launch.  One launch on
+ *   `stream`, no workspace, no synchronisation. */
+int mx_slots_encode(const int64_t* d_values, int64_t count, const uint32_t* h_n, int limbs_n, int slot_bits, int slots,
+                    int is_signed, uint32_t* d_out, int out_stride, uint8_t* d_status, void* stream);
+int mx_slots_decode(const uint32_t* d_rows, int row_stride, int64_t count, const uint32_t* h_n, int limbs_n,
+                    int slot_bits, int slots, int is_signed, int64_t* d_out, void* stream);
+
 /* ---- fixed-base exponentiation: encryption and re-randomisation (ABI 4.4, additions) -------------------------------
  *   d_out[r] = f_r * g^(e_r)  mod N^2,   r < count,   ONE base g per table, exponents e_r < 2^exp_bits
  * with the constants of a plan of mx_powmod_nsquare_prepare (its exponent is not used).  mx_fixedbase_nsquare_prepare

@@ -28,7 +28,7 @@ def configure_hw_queues(queues: int = 16) -> bool:
     return True
 
 
-from . import device_rng, homomorphic, limbs, packing, randomizer  # noqa: F401
+from . import device_rng, homomorphic, limbs, packing, randomizer, slots  # noqa: F401
 from .device_rng import DeviceRng  # noqa: F401
 from .engine import Engine, default_engine  # noqa: F401
 from .randomizer import FastRandomizer, generate_base  # noqa: F401

@@ -106,6 +106,8 @@ SYMBOLS = {
     "mx_matmul_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_slots_encode": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "mx_slots_decode": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mx_fixedbase_nsquare_shape": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, *_P4]),
     "mx_fixedbase_nsquare_table_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "mx_fixedbase_nsquare_prepare": (c_int, [POINTER(NsquarePlan), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),

@@ -1121,6 +1121,93 @@ class Engine:
         x_t = self._upload_ints(cts if isinstance(cts, list) else list(cts), limbs2, n2)
         return self._download_ints(self._freshened(self.pack_nsquare_t(x_t, n, slot_bits, slots), fixed_base))
 
+    # ------------------------------------------------------------------ slot-packed plaintexts: the codec on the device
+    def _slot_layout(self, n: int, slot_bits: int, signed: bool) -> Tuple[int, int, Any]:
+        """(k, limbs(n), N as a host array of words) of packing.py's layout; ValueError for a slot the int64 codec does not take."""
+        from .packing import slots_per_ciphertext
+
+        _check_modulus(n)
+        top = 64 if signed else 63
+        if not 1 <= slot_bits <= top:
+            raise ValueError(f"the device codec takes {'signed' if signed else 'unsigned'} slots of 1 .. {top} bits (int64 values); "
+                             "wider slots stay with packing.unpack")
+        k = slots_per_ciphertext(n, slot_bits)
+        limbs = _limbs.limbs_for(n)
+        return k, limbs, np.ascontiguousarray(_limbs.pack_one(n, limbs))
+
+    def _slot_values(self, values_t):
+        """An int64 vector on this engine's device: a device tensor as it is, a host tensor or numpy array uploaded."""
+        torch = self.torch
+        if isinstance(values_t, np.ndarray):
+            if values_t.dtype.kind not in "iu" or (values_t.dtype.kind == "u" and values_t.dtype.itemsize == 8 and values_t.size
+                                                   and int(values_t.max()) >> 63):
+                raise ValueError("an integer array within int64 expected")
+            values_t = torch.from_numpy(np.ascontiguousarray(values_t, dtype=np.int64))
+        if torch.is_tensor(values_t) and values_t.dtype in (torch.int8, torch.uint8, torch.int16, torch.int32):
+            values_t = values_t.to(torch.int64)
+        if not torch.is_tensor(values_t) or values_t.dtype != torch.int64 or values_t.dim() != 1:
+            raise ValueError("a one-dimensional integer tensor (int64 or narrower) expected")
+        if values_t.is_cuda and values_t.device != self.device:
+            raise ValueError(f"the values live on {values_t.device}, the operation runs on {self.device}")
+        return values_t.to(self.device).contiguous()
+
+    @_int_args
+    def slots_encode_t(self, values_t, n: int, slot_bits: int, signed: bool = True, row_words: Optional[int] = None):
+        """int64 values -> ``[ceil(count / k), limbs(n)]`` int32 plaintext rows of packing.py's layout on the device
+        (csrc/mx_slots.hpp): value j k + i in bits [b i, b (i + 1)) of plaintext j, k = slots_per_ciphertext(n, b);
+        signed plaintexts are (sum_i m_i 2^(b i)) mod n.  The rows are what fixed_base_encrypt_t takes as messages.
+
+        ``values_t``: an int64 tensor on this engine's device, or a host tensor or numpy integer array, which is
+        uploaded.  ``row_words`` > limbs(n) widens the rows with zero words.  ValueError naming the first offending
+        index when a value lies outside [-2^(b-1), 2^(b-1)) (signed) or [0, 2^b) (unsigned); no rows are returned then.
+        Reading the status bytes waits for the kernel."""
+        signed = bool(signed)
+        k, limbs, n_words = self._slot_layout(n, slot_bits, signed)
+        torch = self.torch
+        v_t = self._slot_values(values_t)
+        count = v_t.shape[0]
+        outputs = -(-count // k)
+        stride = limbs if row_words is None else int(row_words)
+        if stride < limbs:
+            raise ValueError("rows narrower than N")
+        out_t = torch.empty((outputs, stride), dtype=torch.int32, device=self.device)
+        if count == 0:
+            return out_t
+        status_t = torch.empty(outputs, dtype=torch.uint8, device=self.device)
+        self._call("mx_slots_encode", v_t.data_ptr(), count, n_words.ctypes.data, limbs, slot_bits, k, int(signed), out_t.data_ptr(), stride,
+                   status_t.data_ptr())
+        if bool(status_t.any()):
+            j = int(torch.nonzero(status_t)[0])
+            part = v_t[j * k : (j + 1) * k]
+            lo, hi = (-(1 << (slot_bits - 1)), (1 << (slot_bits - 1)) - 1) if signed else (0, (1 << slot_bits) - 1)
+            idx = j * k + int(torch.nonzero((part < lo) | (part > hi))[0])
+            raise ValueError(f"value {idx} ({int(v_t[idx])}) does not fit a {'signed' if signed else 'unsigned'} slot of {slot_bits} bits")
+        return out_t
+
+    @_int_args
+    def slots_decode_t(self, rows_t, n: int, slot_bits: int, count: int, signed: bool = True):
+        """Plaintext rows -> the ``count`` int64 slot values, on the device: packing.unpack for slots of up to 64 (unsigned:
+        63) bits.  ``rows_t``: ``[ceil(count / k), >= limbs(n)]`` int32 residues in [0, n) — words beyond limbs(n) are
+        ignored, so the rows of ``combine_t(..., packed=True)`` are taken as they are.  Enqueues on the current stream and
+        does not wait; ValueError for a wrong number of rows or rows narrower than n."""
+        signed = bool(signed)
+        k, limbs, n_words = self._slot_layout(n, slot_bits, signed)
+        torch = self.torch
+        outputs = -(-count // k)
+        if count < 0 or rows_t.dim() != 2 or rows_t.shape[0] != outputs:
+            raise ValueError(f"{count} values of {slot_bits} bits need {outputs} packed plaintext rows, got {tuple(rows_t.shape)}")
+        if rows_t.shape[1] < limbs:
+            raise ValueError("plaintext rows narrower than N")
+        if rows_t.dtype != torch.int32 or rows_t.device != self.device:
+            raise ValueError(f"int32 plaintext rows on {self.device} expected")
+        out_t = torch.empty(count, dtype=torch.int64, device=self.device)
+        if count == 0:
+            return out_t
+        rows_t = rows_t.contiguous()
+        self._call("mx_slots_decode", rows_t.data_ptr(), rows_t.shape[1], count, n_words.ctypes.data, limbs, slot_bits, k, int(signed),
+                   out_t.data_ptr())
+        return out_t
+
     # ------------------------------------------------------------------ fixed base: encryption and re-randomisation
     def fixed_base_shape(self, n: int, exp_bits: int, count: int, window: int = 0, table_budget_bytes: int = 0) -> Tuple[int, int, int]:
         """(window, windows, table bytes) of mx_fixedbase_nsquare_shape for `count` outputs per call."""
