@@ -467,6 +467,44 @@ int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs,
  * written; returns their number. */
 int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- encrypted convolutions of ciphertext grids with a public kernel (ABI 4.4, additions) -------------------------
+ *   d_out[m][j][q] = prod_{t < terms} T(d_index[j][t], b) ^ w[j][t]  mod N^2,   w[j][t] >= 0,  j < n_rows,
+ *   b = m * image_positions + q < n_positions
+ * — the shared-weight product above with the address rule of a sliding window (csrc/mx_conv_n2.hpp): the tables are the
+ * PIXELS of the padded input grids, one table each however many windows cover it, and term t of position b reads
+ *   T(i, b) = table i + d_origin[b]        for i >= 0  (i: the table of the tap at output position 0)
+ *           = table n_local + (-1 - i)     for i <  0  (a shared table — the bias inputs 1 + (b_j mod N) N — read
+ *                                                       without the origin)
+ * Stride, dilation, channels and padding are in d_index and d_origin alone.  The same table pass over n_local + n_shared
+ * inputs, then one group of lanes per (weight row, position), the groups of a wavefront being consecutive positions of
+ * one row.
+ *   d_inputs:  [n_local + n_shared][limbs2] residues < N^2 (a padded pixel is the residue 1).  NULL = the tables
+ *              already in the workspace (an earlier run with the same inputs, counts, window and workspace on the same
+ *              stream)
+ *   d_index:   [n_rows][terms] int32;  d_weights: [n_rows][terms][(weight_bits + 31) / 32];  d_origin: [n_positions] int64
+ *   THE CALLER guarantees 0 <= d_index[j][t] + d_origin[b] < n_local for every term with a non-zero weight (the arrays
+ *   are device memory: the library cannot read them before the launch); the kernel clamps every table address into the
+ *   table set, so a wrong array gives wrong values, never an access outside the workspace.
+ *   d_out:     [n_positions / image_positions][n_rows][image_positions][limbs2]; image_positions divides n_positions.
+ *              With the kernels as rows and whole images per launch that is the layout [image][kernel][y][x].
+ * A digit that is zero costs no multiplication.  THE WEIGHTS MUST BE PUBLIC: the kernel's control flow depends on them.
+ * No cost model of its own: a tile is a linear map of n_local + n_shared inputs and n_rows * n_positions outputs —
+ * window and split-K chunk are those of mx_multiexp_nsquare_shape.
+ * MX_ERR_ARG for a null pointer, a zero or negative size, no table at all, n_positions above 2^30 or no multiple of
+ * image_positions, window outside 1 .. 8, weight_bits above 2 * bits(N) + 64, or rows too narrow for N^2; MX_ERR_SIZE
+ * outside the narrow geometry (limbs_per_lane 9 or 0, groups of up to 32 lanes) or beyond one grid; MX_ERR_WORKSPACE for a
+ * workspace below the query's size.  Everything is checked before anything is enqueued.  Results are canonical residues
+ * in [0, N^2), NOT fresh ciphertexts. */
+int64_t mx_conv_nsquare_workspace_bytes(int n_bits, int64_t n_local, int64_t n_shared, int limbs_per_lane, int window);
+int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_local, int64_t n_shared,
+                        int limbs2, const int32_t* d_index, const uint32_t* d_weights, int terms, int weight_bits,
+                        const int64_t* d_origin, int64_t n_positions, int64_t image_positions, uint32_t* d_out,
+                        int64_t n_rows, int limbs_per_lane, int window, void* d_workspace, int64_t workspace_bytes,
+                        void* stream);
+/* The kernel instances mx_conv_nsquare_run can select: (lanes per element, limbs per lane) pairs, at most max_entries
+ * written; returns their number. */
+int mx_conv_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 /* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
  *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
  * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of

@@ -6,6 +6,7 @@
 #include "mx_bipair.hpp"
 #include "mx_multiexp_n2.hpp"
 #include "mx_matmul_n2.hpp"
+#include "mx_conv_n2.hpp"
 #include "mx_pack_n2.hpp"
 #include "mx_fixedbase_n2.hpp"
 
@@ -1172,4 +1173,84 @@ extern "C" int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
   a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk;
   return mxmm::launch_matmul(g.K, a, n_rows * tile_blocks, s);
+}
+
+// ---- encrypted convolutions of ciphertext grids with a public kernel (mx_conv_n2.hpp) --------------------------------
+namespace mxcv { int launch_conv(int K, const mx::ConvN2Args& a, int64_t nblocks, hipStream_t s); }
+
+extern "C" int mx_conv_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int64_t mx_conv_nsquare_workspace_bytes(int n_bits, int64_t n_local, int64_t n_shared, int limbs_per_lane,
+                                                   int window) {
+  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > ((int64_t)1 << 36) || n_shared > ((int64_t)1 << 31))
+    return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  // the table pass runs one group per table in one grid: at most 2^31 wavefronts — which also keeps the byte count
+  // (below 2^37 tables of at most 2^19 bytes) inside 64 bits
+  const int gpw = 64 / g.K;
+  if ((n_local + n_shared + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
+  return mx_multiexp_nsquare_workspace_bytes(n_bits, n_local + n_shared, limbs_per_lane, window);
+}
+
+extern "C" int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_local, int64_t n_shared,
+                                   int limbs2, const int32_t* d_index, const uint32_t* d_weights, int terms,
+                                   int weight_bits, const int64_t* d_origin, int64_t n_positions, int64_t image_positions,
+                                   uint32_t* d_out, int64_t n_rows, int limbs_per_lane, int window, void* d_ws,
+                                   int64_t ws_bytes, void* stream) {
+  if (!plan || !plan->d_plan || !d_out || !d_ws || !d_origin || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > ((int64_t)1 << 36) || n_shared > ((int64_t)1 << 31))
+    return MX_ERR_ARG;
+  if (n_positions < 1 || n_positions > ((int64_t)1 << 30) || image_positions < 1 || n_positions % image_positions != 0) return MX_ERR_ARG;
+  if (n_rows <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
+  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  const int bits = plan->n_bits;
+  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
+  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  Geometry g;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  const int gpw = 64 / g.K;
+  const int64_t pos_blocks = (n_positions + gpw - 1) / gpw;
+  if (n_rows > ((int64_t)1 << 31) / pos_blocks - 1) return MX_ERR_SIZE;       // more wavefronts than one grid holds
+  const int64_t n_tables = n_local + n_shared;
+  const int64_t need = mx_conv_nsquare_workspace_bytes(bits, n_local, n_shared, LIMBS_PER_LANE, window);
+  if (need < 0) return (int)need;
+  if (need > ws_bytes) return MX_ERR_WORKSPACE;
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  const u32* consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
+  if (d_inputs) {
+    mx::MultiexpN2Args t{};
+    t.inputs = d_inputs;
+    t.tables = (u32*)d_ws;
+    t.consts = consts;
+    t.n_inputs = n_tables;
+    t.window = window;
+    t.limbsn = plan->limbs_n; t.limbs2 = limbs2; t.nblk = g.nblk; t.ksplit = bits - 1;
+    MX_TRY(mxm::launch_multiexp(g.K, true, t, (n_tables + gpw - 1) / gpw, s));
+  }
+  mx::ConvN2Args a{};
+  a.tables = (const u32*)d_ws;
+  a.consts = consts;
+  a.index = d_index;
+  a.weights = d_weights;
+  a.origin = (const mx::i64*)d_origin;
+  a.out = d_out;
+  a.n_local = n_local; a.n_shared = n_shared; a.rows = n_rows;
+  a.image_positions = image_positions;
+  a.positions = (int)n_positions; a.pos_blocks = (int)pos_blocks;
+  a.terms = terms;
+  a.wwords = (weight_bits + 31) / 32;
+  a.window = window;
+  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk;
+  return mxcv::launch_conv(g.K, a, n_rows * pos_blocks, s);
 }

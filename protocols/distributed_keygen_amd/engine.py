@@ -1087,6 +1087,60 @@ class Engine:
         flat = self._download_ints(self._freshened(self._matmul_run_t(x_t, len(samples), n, plan), fixed_base))
         return [flat[b * plan.n_rows : (b + 1) * plan.n_rows] for b in range(len(samples))]
 
+    # ------------------------------------------------------------------ encrypted convolutions with a public kernel
+    def _conv_plan(self, n: int, shape, weights, bias, stride, padding, dilation, window: int = 0, table_budget=None):
+        from . import conv_plan as cp
+        from . import multiexp_plan as mp
+
+        _check_modulus(n)
+        return cp.plan_conv(weights, shape, n, bias, lambda a, b, c, d, w: self.multiexp_nsquare_shape(n, a, b, c, d, w),
+                            stride=stride, padding=padding, dilation=dilation,
+                            table_budget=mp.TABLE_BUDGET_BYTES if table_budget is None else int(table_budget), window=int(window))
+
+    def conv2d_nsquare_t(self, x_t, shape, weights, n: int, bias: Optional[Sequence[int]] = None, stride=1, padding=0,
+                         dilation=1, window: int = 0, table_budget: Optional[int] = None):
+        """Y[b][o][y][x] = (1 + (bias_o mod n) n) * prod_(c,i,j) X[b][c][y sh - ph + i dh][x sw - pw + j dw]^w[o][c][i][j]
+        mod n^2: B grids of ciphertexts under ONE public kernel, on the device (csrc/mx_conv_n2.hpp).
+        Cross-correlation, the convention of torch.nn.functional.conv2d; a tap outside the grid contributes 1.
+
+        ``x_t``: ``[B * C * H * W, limbs2]`` rows of residues below n^2 with ``shape = (B, C, H, W)``; ``weights``:
+        ``[O][C][kh][kw]`` signed ints — PUBLIC values: the kernel skips their zero digits; ``bias``: one plaintext per
+        kernel or None; ``stride``, ``padding`` (zeros) and ``dilation``: an int or a pair (rows, columns).  A negative tap
+        uses the inverses of its channel (one product tree per call; ValueError like ``pow`` if a pixel has none), a zero
+        tap gives 1 even on a zero input.  ``window`` > 0 overrides the library's window, ``table_budget`` the bytes of
+        tables one tile (whole images, or a band of output rows of one image) may take.  Returns ``[B * O * H' * W',
+        limbs2]`` canonical residues on the current stream — not fresh ciphertexts.  The planning is
+        conv_plan.plan_conv: once per call, whatever B and H' W'."""
+        n = int(n)
+        return self._conv_run_t(x_t, n, self._conv_plan(n, tuple(shape), weights, bias, stride, padding, dilation, window, table_budget))
+
+    def _conv_run_t(self, x_t, n: int, plan):
+        from . import conv_plan as cp
+
+        limbs2 = x_t.shape[1]
+        _check_rows_n2(n, limbs2)
+        b, c, h, w = plan.shape
+        if x_t.shape[0] != b * c * h * w:
+            raise ValueError("x_t must hold B * C * H * W rows")
+        return cp.execute_conv(plan, _ConvBackend(self, n, limbs2, n.bit_length()), x_t.contiguous())
+
+    @_int_args
+    def ciphertext_conv2d_batch(self, x, weights, n: int, bias: Optional[Sequence[int]] = None, stride=1, padding=0,
+                                dilation=1, fixed_base=None) -> List[List[List[List[int]]]]:
+        """The encrypted convolution of every grid x[b] ([C][H][W] ciphertexts) with the public kernel ``weights``
+        ([O][C][kh][kw]): nested lists [B][O][H'][W'] of the values conv2d_nsquare_t describes."""
+        shape, flat = _grid_shape(x)
+        n2, limbs2 = _nsquare(n)
+        plan = self._conv_plan(n, shape, weights, bias, stride, padding, dilation)      # every refusal of the kernel: before any launch
+        if flat:
+            x_t = self._upload_ints(flat, limbs2, n2)
+        else:
+            x_t = self.torch.empty((0, limbs2), dtype=self.torch.int32, device=self.device)
+        vals = self._download_ints(self._freshened(self._conv_run_t(x_t, n, plan), fixed_base)) if shape[0] and plan.n_rows else []
+        o, oh, ow = plan.n_rows, plan.out_h, plan.out_w
+        return [[[vals[((b * o + j) * oh + y) * ow : ((b * o + j) * oh + y + 1) * ow] for y in range(oh)] for j in range(o)]
+                for b in range(shape[0])]
+
     # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
     def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
         """out[j] = prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 on the device (csrc/mx_pack_n2.hpp):
@@ -1998,17 +2052,28 @@ class _MatmulBackend:
     def concat(self, parts):
         return self._empty() if not parts else (parts[0] if len(parts) == 1 else self.torch.cat(parts, dim=0))
 
+    def _launch_arrays(self, launch):
+        """index and weights of `launch` on the device, uploaded once per call."""
+        if id(launch) not in self._arrays:
+            rows = launch.index.shape[0]
+            self._arrays[id(launch)] = (self.eng.to_device(launch.index.view(np.uint32)),
+                                        self.eng.to_device(launch.weights.reshape(rows, -1)))
+        return self._arrays[id(launch)]
+
+    def _table_rows(self, tables_t, n_tables):
+        """The table inputs of a launch, contiguous and of the count the launch names (None stays None)."""
+        if tables_t is not None:
+            tables_t = tables_t.contiguous()
+            if tables_t.shape[0] != n_tables:
+                raise ValueError("table rows do not match the launch")
+        return tables_t
+
     def run_matmul(self, tables_t, n_cols, n_shared, tile, launch, window):
         eng = self.eng
         rows, terms = launch.index.shape
-        if id(launch) not in self._arrays:
-            self._arrays[id(launch)] = (eng.to_device(launch.index.view(np.uint32)), eng.to_device(launch.weights.reshape(rows, -1)))
-        idx_t, w_t = self._arrays[id(launch)]
+        idx_t, w_t = self._launch_arrays(launch)
         out_t = self._empty(tile * rows)
-        if tables_t is not None:
-            tables_t = tables_t.contiguous()
-            if tables_t.shape[0] != n_cols * tile + n_shared:
-                raise ValueError("table rows do not match the launch")
+        tables_t = self._table_rows(tables_t, n_cols * tile + n_shared)
         eng._call("mx_matmul_nsquare_run", self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_cols, n_shared,
                   tile, self.limbs2, idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, out_t.data_ptr(), rows, 0, window,
                   workspace=("mx_matmul_nsquare_workspace_bytes", self.n_bits, n_cols, n_shared, tile, 0, window), plans=(self.plan,))
@@ -2031,6 +2096,98 @@ class _MatmulBackend:
         if column_major:
             sel = sel.permute(1, 0, 2)
         return sel.reshape(-1, self.limbs2)
+
+
+class _ConvBackend(_MatmulBackend):
+    """conv_plan.execute_conv over device rows of one Engine and modulus: the padded grids are one tensor
+    [image, padded row, grid, padded column, limbs2], so the tables of a tile of whole images or of a band of rows are a
+    slice of it.  The second pass of split kernels is _MatmulBackend.run_matmul."""
+
+    def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
+        super().__init__(eng, n, limbs2, n_bits)
+        self._origins: Dict[int, Any] = {}
+
+    def grids(self, inputs_t, shape, x_ch, inverted, padding):
+        torch = self.torch
+        b, c, h, w = shape
+        ph, pw = padding
+        x = inputs_t.view(b, c, h, w, self.limbs2)
+        parts = []
+        if x_ch:
+            parts.append(x.index_select(1, self._index(x_ch)))
+        if inverted:
+            parts.append(self.invert(x.index_select(1, self._index(inverted)).contiguous()))
+        real = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        out = torch.zeros((b, h + 2 * ph, real.shape[1], w + 2 * pw, self.limbs2), dtype=torch.int32, device=self.eng.device)
+        out[..., 0] = 1                                                       # a padded pixel: the ciphertext 1 of 0
+        out[:, ph : ph + h, :, pw : pw + w] = real.permute(0, 2, 1, 3, 4)
+        return out
+
+    def window(self, grids_t, m0, m1, r0, r1):
+        return grids_t[m0:m1, r0:r1].reshape(-1, self.limbs2)
+
+    def run_conv(self, tables_t, n_local, n_shared, launch, window, origin, image_positions):
+        eng = self.eng
+        rows, terms = launch.index.shape
+        idx_t, w_t = self._launch_arrays(launch)
+        positions = len(origin)
+        key = origin.__array_interface__["data"][0]            # a ragged tile's origins are a prefix of the full tile's
+        if key not in self._origins or self._origins[key].numel() < positions:
+            self._origins[key] = self.torch.from_numpy(np.ascontiguousarray(origin)).to(eng.device)
+        org_t = self._origins[key]
+        out_t = self._empty(positions * rows)
+        tables_t = self._table_rows(tables_t, n_local + n_shared)
+        eng._call("mx_conv_nsquare_run", self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_local, n_shared,
+                  self.limbs2, idx_t.data_ptr(), w_t.data_ptr(), terms, launch.weight_bits, org_t.data_ptr(), positions,
+                  image_positions, out_t.data_ptr(), rows, 0, window,
+                  workspace=("mx_conv_nsquare_workspace_bytes", self.n_bits, n_local, n_shared, 0, window), plans=(self.plan,))
+        return out_t
+
+    def select_conv(self, outs, outs2, picks, images, image_positions, as_columns):
+        torch = self.torch
+        if not picks:
+            return self._empty()
+        if not as_columns and len(outs) == 1 and picks == [(1, 0, r) for r in range(outs[0].shape[0] // (images * image_positions))]:
+            return outs[0]                                       # one launch whose rows are the kernels: the result as it stands
+        views = [o.view(images, -1, image_positions, self.limbs2) for o in outs]
+        views += [o.view(images, image_positions, -1, self.limbs2).permute(0, 2, 1, 3) for o in outs2]
+        first = [0]
+        for v in views:
+            first.append(first[-1] + v.shape[1])
+        if any(pk is None for pk in picks):
+            one = torch.zeros((images, 1, image_positions, self.limbs2), dtype=torch.int32, device=self.eng.device)
+            one[..., 0] = 1
+            views.append(one)
+        pool = views[0] if len(views) == 1 else torch.cat(views, dim=1)
+        at = lambda pk: first[-1] if pk is None else first[(len(outs) if pk[0] == 2 else 0) + pk[1]] + pk[2]
+        sel = pool.index_select(1, self._index([at(pk) for pk in picks]))
+        if as_columns:
+            sel = sel.permute(1, 0, 2, 3)
+        return sel.reshape(-1, self.limbs2)
+
+    def assemble(self, tiles, batch, n_rows, out_h, out_w):
+        if not tiles:
+            return self._empty()
+        if len(tiles) == 1:
+            return tiles[0][1]
+        out = self._empty(batch * n_rows * out_h * out_w).view(batch, n_rows, out_h, out_w, self.limbs2)
+        for (m0, m1, y0, y1), rows_t in tiles:
+            out[m0:m1, :, y0:y1] = rows_t.view(m1 - m0, n_rows, y1 - y0, out_w, self.limbs2)
+        return out.view(-1, self.limbs2)
+
+
+def _grid_shape(x) -> Tuple[Tuple[int, int, int, int], List[Any]]:
+    """((B, C, H, W), the entries in row-major order) of a nesting x[b][c][y][x]; ValueError if it is ragged.  A grid of no
+    channels has no extent of its own: it is taken as 1 x 1."""
+    x = [[[list(r) for r in ch] for ch in img] for img in x]
+    b = len(x)
+    c = len(x[0]) if b else 0
+    h = len(x[0][0]) if c else 1
+    w = len(x[0][0][0]) if c and h else 1
+    for img in x:
+        if len(img) != c or any(len(ch) != h for ch in img) or any(len(r) != w for ch in img for r in ch):
+            raise ValueError("the grids must all have the same shape [C][H][W]")
+    return (b, c, h, w), [v for img in x for ch in img for r in ch for v in r]
 
 
 def _check_modulus(mod: int) -> None:

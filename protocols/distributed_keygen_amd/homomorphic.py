@@ -10,7 +10,10 @@ them to many ciphertexts at once:
   * ``linear_map``: the encrypted W x + b (dense rows or sparse ``{index: weight}`` rows, optional plaintext bias);
   * ``matmul``: the same public W applied to a BATCH of ciphertext vectors (encrypted scoring, linear layers): W is
     planned and uploaded once, and the kernel reads every weight row once per wavefront of samples.  The weights are
-    public plaintexts — the kernel's control flow depends on them.
+    public plaintexts — the kernel's control flow depends on them;
+  * ``conv2d`` / ``conv1d``: a public kernel slid over grids (or series) of ciphertexts — FIR filters and moving sums
+    over an encrypted time series, a convolution layer over an encrypted image.  Every pixel gets one table however
+    many windows cover it.  Cross-correlation, as ``torch.nn.functional.conv2d``; the kernel is public.
 
 Ciphertexts are ints or objects with ``get_value()`` (the reference's ``PaillierCiphertext``); for objects the modulus
 comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` is called once per distinct object.  The
@@ -124,3 +127,39 @@ def matmul(x: Sequence[Sequence[Any]], weights: Sequence[Any], n: Optional[int] 
     vals = [flat[b * width : (b + 1) * width] for b in range(len(samples))]
     weights = weights if hasattr(weights, "shape") else list(weights)
     return _engine(engine).ciphertext_matmul_batch(vals, weights, n, bias=bias, **_fresh(randomizer, n, len(samples) * len(weights)))
+
+
+def conv2d(x: Sequence[Any], weights: Any, n: Optional[int] = None, bias: Optional[Sequence[int]] = None, stride: Any = 1,
+           padding: Any = 0, dilation: Any = 1, engine: Any = None, randomizer: Any = None) -> List[List[List[List[int]]]]:
+    """The encrypted convolution of every grid x[b] ([C][H][W] ciphertexts) with the public kernel ``weights``
+    ([O][C][kh][kw] signed ints) and the public ``bias`` ([O]):
+
+        Y[b][o][y][x] = (1 + (bias_o mod N) N) prod_(c,i,j) X[b][c][y sh - ph + i dh][x sw - pw + j dw]^(w[o][c][i][j])  mod N^2
+
+    as nested lists [B][O][H'][W'] with H' = (H + 2 ph - dh (kh - 1) - 1) // sh + 1.  ``stride``, ``padding`` (zeros: a tap
+    outside the grid contributes 1) and ``dilation`` are ints or pairs (rows, columns).  Cross-correlation — the kernel
+    is not flipped."""
+    grids = [[[list(r) for r in ch] for ch in img] for img in x]
+    flat, n = _values([c for img in grids for ch in img for r in ch for c in r], n)
+    it = iter(flat)
+    vals = [[[[next(it) for _ in r] for r in ch] for ch in img] for img in grids]
+    fresh = {}
+    if randomizer is not None:
+        from . import conv_plan as cp
+
+        rows = grids[0][0] if grids and grids[0] else [[None]]
+        kernel = cp.kernel_array(weights)
+        out_h, out_w = cp.output_hw(len(rows), len(rows[0]) if rows else 0, kernel.shape[2], kernel.shape[3], stride, padding, dilation)
+        fresh = _fresh(randomizer, n, len(grids) * kernel.shape[0] * out_h * out_w)
+    return _engine(engine).ciphertext_conv2d_batch(vals, weights, n, bias=bias, stride=stride, padding=padding,
+                                                   dilation=dilation, **fresh)
+
+
+def conv1d(x: Sequence[Any], weights: Any, n: Optional[int] = None, bias: Optional[Sequence[int]] = None, stride: int = 1,
+           padding: int = 0, dilation: int = 1, engine: Any = None, randomizer: Any = None) -> List[List[List[int]]]:
+    """conv2d for series: x[b] is [C][L] ciphertexts, ``weights`` [O][C][k]; the result is [B][O][L'].  The H = kh = 1
+    case with scalar stride, padding and dilation."""
+    y = conv2d([[[list(ch)] for ch in series] for series in x], [[[list(taps)] for taps in ker] for ker in weights], n=n,
+               bias=bias, stride=(1, int(stride)), padding=(0, int(padding)), dilation=(1, int(dilation)), engine=engine,
+               randomizer=randomizer)
+    return [[ch[0] for ch in img] for img in y]

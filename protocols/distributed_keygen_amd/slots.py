@@ -10,7 +10,10 @@ and encrypts P_j — k times fewer encryptions (63 times at key_length 2048 and 
 therefore on all slots at once: a public weight multiplies every slot, a sum adds slot by slot.  One public W over a batch
 of samples packed ACROSS slots (slot i = sample i, one ciphertext per feature) costs 1/k of the ciphertexts, of the kernel
 time and of the partial decryptions.  The result already has the layout ``packing.unpack`` reads, so the ciphertext-level
-``pack`` is not needed; a bias is encoded like a value, once per slot: ``encode([beta] * k, ...)``.
+``pack`` is not needed; a bias is encoded like a value, once per slot: ``encode([beta] * k, ...)``.  A convolution
+(``homomorphic.conv2d`` / ``conv1d``) acts on all slots at once in the same way — k images, one per slot, under one public
+kernel for the price of one; ``slot_bits_for(value_bits, weight_bits, terms=C * kh * kw, bias_bits=...)`` gives the head
+room an output needs.
 
 The layout is packing.py's and is decided there: value j k + i in bits [b i, b (i + 1)) of plaintext j, the last
 plaintext holding the remaining values with its missing slots at 0; signed values in [-2^(b-1), 2^(b-1)), unsigned in
