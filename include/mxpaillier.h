@@ -470,8 +470,9 @@ int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries
 /* ---- encrypted convolutions of ciphertext grids with a public kernel (ABI 4.4, additions) -------------------------
  *   d_out[m][j][q] = prod_{t < terms} T(d_index[j][t], b) ^ w[j][t]  mod N^2,   w[j][t] >= 0,  j < n_rows,
  *   b = m * image_positions + q < n_positions
- * — the shared-weight product above with the address rule of a sliding window (csrc/mx_conv_n2.hpp): the tables are the
- * PIXELS of the padded input grids, one table each however many windows cover it, and term t of position b reads
+ * — the shared-weight product above with the address rule of a sliding window (csrc/mx_matmul_n2.hpp, the same
+ * kernel): the tables are the PIXELS of the padded input grids, one table each however many windows cover it, and term
+ * t of position b reads
  *   T(i, b) = table i + d_origin[b]        for i >= 0  (i: the table of the tap at output position 0)
  *           = table n_local + (-1 - i)     for i <  0  (a shared table — the bias inputs 1 + (b_j mod N) N — read
  *                                                       without the origin)

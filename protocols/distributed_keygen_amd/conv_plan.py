@@ -1,4 +1,4 @@
-"""Host-side planning of encrypted convolutions modulo N^2 (csrc/mx_conv_n2.hpp).
+"""Host-side planning of encrypted convolutions modulo N^2 (csrc/mx_matmul_n2.hpp).
 
     Y[b][o][y][x] = (1 + (bias_o mod N) N) * prod_(c,i,j) X[b][c][y sh - ph + i dh][x sw - pw + j dw] ^ w[o][c][i][j]   mod N^2
 

@@ -6,7 +6,6 @@
 #include "mx_bipair.hpp"
 #include "mx_multiexp_n2.hpp"
 #include "mx_matmul_n2.hpp"
-#include "mx_conv_n2.hpp"
 #include "mx_pack_n2.hpp"
 #include "mx_fixedbase_n2.hpp"
 
@@ -815,6 +814,58 @@ int multiexp_window(int64_t n_inputs, int64_t n_outputs, int64_t terms, int weig
   }
   return best;
 }
+
+// What every launch of a homomorphic kernel starts from, after the entry point's own argument checks: the narrow
+// geometry of the plan's modulus, the plan's constant rows of that geometry and the groups per wavefront.  Refuses, in
+// this order, rows too narrow for N^2 (MX_ERR_ARG), a plan or modulus without the narrow geometry — or a
+// limbs_per_lane that is not the narrow one, where the entry point has not refused it as an argument before —
+// (MX_ERR_SIZE), and rows wider than the staging area (MX_ERR_ARG).
+struct NarrowLaunch {
+  Geometry g;
+  const u32* consts;
+  int gpw;
+  int64_t blocks(int64_t groups) const { return (groups + gpw - 1) / gpw; }
+};
+int narrow_launch(const mx_nsquare_plan* plan, int limbs2, int limbs_per_lane, NarrowLaunch& o) {
+  const int bits = plan->n_bits;
+  if (32 * (int64_t)limbs2 < 2 * (int64_t)bits) return MX_ERR_ARG;
+  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, o.g)) return MX_ERR_SIZE;
+  if (2 * o.g.K * o.g.L + 8 < limbs2 + 2) return MX_ERR_ARG;
+  o.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * n2_consts_bytes(plan->limbs_n));
+  o.gpw = 64 / o.g.K;
+  return MX_OK;
+}
+
+// split-K: outputs too few to give every SIMD of the device a wavefront have their terms cut into chunks that run on
+// groups of their own (a second launch multiplies the partial products together)
+int64_t splitk_chunk(const Geometry& g, int64_t n_outputs, int64_t terms) {
+  const int64_t target = (int64_t)device_cus() * 4 * (64 / g.K);
+  int64_t chunk = terms;
+  if (n_outputs > 0 && n_outputs < target && terms > 64) {
+    chunk = (terms * n_outputs + target - 1) / target;
+    if (chunk < 64) chunk = 64;
+  }
+  return chunk < 1 ? 1 : chunk;
+}
+
+// the table pass (multiexp_n2_table_kernel): one group per input row, tables into the workspace
+int launch_table_pass(const NarrowLaunch& o, const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_inputs,
+                      int limbs2, int window, void* d_ws, hipStream_t s) {
+  mx::MultiexpN2Args t{};
+  t.inputs = d_inputs;
+  t.tables = (u32*)d_ws;
+  t.consts = o.consts;
+  t.n_inputs = n_inputs;
+  t.window = window;
+  t.limbsn = plan->limbs_n; t.limbs2 = limbs2; t.nblk = o.g.nblk; t.ksplit = plan->n_bits - 1;
+  return mxm::launch_multiexp(o.g.K, true, t, o.blocks(n_inputs), s);
+}
+
+// words of a weight and windows of the schedule (none where there are no terms)
+void weight_fields(int terms, int weight_bits, int window, int& wwords, int& nwin) {
+  wwords = (weight_bits + 31) / 32;
+  nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
+}
 }  // namespace
 
 extern "C" int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
@@ -836,15 +887,7 @@ extern "C" int mx_multiexp_nsquare_shape(int n_bits, int64_t n_inputs, int64_t n
   *lanes = g.K;
   *limbs_per_lane_out = g.L;
   *window_out = window > 0 ? window : multiexp_window(n_inputs, n_outputs, terms, weight_bits);
-  // split-K: outputs too few to give every SIMD of the device a wavefront have their terms cut into chunks that run on
-  // groups of their own (a second launch multiplies the partial products together)
-  const int64_t target = (int64_t)device_cus() * 4 * (64 / g.K);
-  int64_t chunk = terms;
-  if (n_outputs > 0 && n_outputs < target && terms > 64) {
-    chunk = (terms * n_outputs + target - 1) / target;
-    if (chunk < 64) chunk = 64;
-  }
-  *chunk_terms = chunk < 1 ? 1 : chunk;
+  *chunk_terms = splitk_chunk(g, n_outputs, terms);
   return MX_OK;
 }
 
@@ -865,34 +908,28 @@ extern "C" int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32
   if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   const int bits = plan->n_bits;
-  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
   if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
   const int64_t need = mx_multiexp_nsquare_workspace_bytes(bits, n_inputs, LIMBS_PER_LANE, window);
   if (need < 0) return (int)need;
   if (need > ws_bytes) return MX_ERR_WORKSPACE;
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
-  mx::MultiexpN2Args a;
-  a.inputs = d_inputs;
+  mx::MultiexpN2Args a{};
   a.tables = (u32*)d_ws;
-  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.consts = o.consts;
   a.index = d_index;
   a.weights = d_weights;
   a.out = d_out;
   a.n_inputs = n_inputs; a.rows = n_outputs;
   a.terms = terms;
-  a.wwords = (weight_bits + 31) / 32;
   a.window = window;
-  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
   hipStream_t s = (hipStream_t)stream;
-  const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
   // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
-  if (d_inputs) MX_TRY(mxm::launch_multiexp(g.K, true, a, (n_inputs + gpw - 1) / gpw, s));
-  return mxm::launch_multiexp(g.K, false, a, (n_outputs + gpw - 1) / gpw, s);
+  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_inputs, limbs2, window, d_ws, s));
+  return mxm::launch_multiexp(o.g.K, false, a, o.blocks(n_outputs), s);
 }
 
 // ---- packing modulo N^2 (mx_pack_n2.hpp): many small plaintexts per ciphertext ---------------------------------------
@@ -908,23 +945,19 @@ extern "C" int mx_pack_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
   if (count < 1 || slots < 1 || slot_bits < 1 || limbs2 <= 0 || limbs_per_lane < 0) return MX_ERR_ARG;
   const int bits = plan->n_bits;
   if ((int64_t)slot_bits * slots > bits - 2) return MX_ERR_ARG;     // a packed plaintext must decrypt unambiguously
-  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
   mx::PackN2Args a;
   a.cts = d_cts;
-  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.consts = o.consts;
   a.out = d_out;
   a.count = count;
   a.outputs = (count + slots - 1) / slots;
   a.slots = slots; a.slot_bits = slot_bits;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = bits - 1;
   hipStream_t s = (hipStream_t)stream;
-  const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
-  return mxp::launch_pack(g.K, a, (a.outputs + gpw - 1) / gpw, s);
+  return mxp::launch_pack(o.g.K, a, o.blocks(a.outputs), s);
 }
 
 // ---- fixed-base exponentiation modulo N^2 (mx_fixedbase_n2.hpp): encryption and re-randomisation ------------------------
@@ -1000,24 +1033,20 @@ extern "C" int mx_fixedbase_nsquare_prepare(const mx_nsquare_plan* plan, const u
   if (!plan || !plan->d_plan || !d_base || !d_table || plan->limbs_n <= 0 || limbs2 <= 0 || limbs_per_lane < 0) return MX_ERR_ARG;
   const int bits = plan->n_bits;
   if (!fixedbase_args_ok(bits, exp_bits, window)) return MX_ERR_ARG;
-  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
-  if (table_bytes < fixedbase_table_bytes(g, exp_bits, window)) return MX_ERR_ARG;
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  if (table_bytes < fixedbase_table_bytes(o.g, exp_bits, window)) return MX_ERR_ARG;
   mx::FixedBaseN2Args a{};
   a.base = d_base;
   a.table = (u32*)d_table;
-  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.consts = o.consts;
   a.exp_bits = exp_bits; a.window = window; a.windows = (exp_bits + window - 1) / window;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = bits - 1;
   hipStream_t s = (hipStream_t)stream;
-  const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
-  MX_TRY(mxf::launch_fixedbase(g.K, 0, a, 1, s));
+  MX_TRY(mxf::launch_fixedbase(o.g.K, 0, a, 1, s));
   const int64_t fill = (int64_t)a.windows * ((1 << window) - 2);
-  if (fill > 0) return mxf::launch_fixedbase(g.K, 1, a, (fill + gpw - 1) / gpw, s);
+  if (fill > 0) return mxf::launch_fixedbase(o.g.K, 1, a, o.blocks(fill), s);
   return MX_OK;
 }
 
@@ -1029,35 +1058,31 @@ extern "C" int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void*
   if (mode != mx::FIXEDBASE_POWER && mode != mx::FIXEDBASE_ENCRYPT && mode != mx::FIXEDBASE_RANDOMIZE) return MX_ERR_ARG;
   const int bits = plan->n_bits;
   if (!fixedbase_args_ok(bits, exp_bits, window)) return MX_ERR_ARG;
-  if (32 * (int64_t)limbs2 < 2 * bits) return MX_ERR_ARG;           // rows too narrow for N^2
   if (mode != mx::FIXEDBASE_POWER) {
     if (!d_operand || operand_limbs <= 0) return MX_ERR_ARG;
     const int64_t need = mode == mx::FIXEDBASE_ENCRYPT ? bits : 2 * bits;
     if (32 * (int64_t)operand_limbs < need) return MX_ERR_ARG;       // rows too narrow for N (ENCRYPT) or N^2
   }
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
-  if (mode != mx::FIXEDBASE_POWER && 2 * g.K * g.L + 8 < operand_limbs + 2) return MX_ERR_ARG;
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  if (mode != mx::FIXEDBASE_POWER && 2 * o.g.K * o.g.L + 8 < operand_limbs + 2) return MX_ERR_ARG;
   mx::FixedBaseN2Args a{};
   a.table = (u32*)d_table;
-  a.consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
+  a.consts = o.consts;
   a.exps = d_exps;
   a.operand = d_operand;
   a.out = d_out;
   a.count = count;
   a.exp_bits = exp_bits; a.ewords = (exp_bits + 31) / 32; a.window = window; a.windows = (exp_bits + window - 1) / window;
   a.mode = mode; a.oplimbs = mode == mx::FIXEDBASE_POWER ? 0 : operand_limbs;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk; a.ksplit = bits - 1;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = bits - 1;
   hipStream_t s = (hipStream_t)stream;
-  const int gpw = 64 / g.K;
   MxKernelTimer timer(s);
-  return mxf::launch_fixedbase(g.K, 2, a, (count + gpw - 1) / gpw, s);
+  return mxf::launch_fixedbase(o.g.K, 2, a, o.blocks(count), s);
 }
 
 // ---- encrypted matrix products over a batch of ciphertext vectors (mx_matmul_n2.hpp) ---------------------------------
-namespace mxmm { int launch_matmul(int K, const mx::MatmulN2Args& a, int64_t nblocks, hipStream_t s); }
+namespace mxmm { int launch_shared(int K, const mx::SharedN2Args& a, int64_t nblocks, hipStream_t s); }
 
 extern "C" int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
   return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
@@ -1092,15 +1117,7 @@ extern "C" int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_row
   if (tile > (int64_t)1 << 30) tile = (int64_t)1 << 30;
   if (tile < 1) tile = 1;
   *tile_batch = tile;
-  // split-K by the rule of mx_multiexp_nsquare_shape, on the outputs of one tile
-  const int64_t target = (int64_t)device_cus() * 4 * (64 / g.K);
-  const int64_t n_outputs = n_rows * tile;
-  int64_t chunk = terms;
-  if (n_outputs > 0 && n_outputs < target && terms > 64) {
-    chunk = (terms * n_outputs + target - 1) / target;
-    if (chunk < 64) chunk = 64;
-  }
-  *chunk_terms = chunk < 1 ? 1 : chunk;
+  *chunk_terms = splitk_chunk(g, n_rows * tile, terms);      // on the outputs of one tile
   return MX_OK;
 }
 
@@ -1131,53 +1148,40 @@ extern "C" int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   const int bits = plan->n_bits;
-  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
   if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
-  const int gpw = 64 / g.K;
-  const int64_t tile_blocks = (tile_batch + gpw - 1) / gpw;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  const int64_t tile_blocks = o.blocks(tile_batch);
   if (n_rows > ((int64_t)1 << 31) / tile_blocks - 1) return MX_ERR_SIZE;      // more wavefronts than one grid holds
   const int64_t n_tables = n_cols * tile_batch + n_shared;
-  if ((n_tables + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
+  if (o.blocks(n_tables) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
   const int64_t need = mx_matmul_nsquare_workspace_bytes(bits, n_cols, n_shared, tile_batch, LIMBS_PER_LANE, window);
   if (need < 0) return (int)need;
   if (need > ws_bytes) return MX_ERR_WORKSPACE;
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
-  const u32* consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
   hipStream_t s = (hipStream_t)stream;
   MxKernelTimer timer(s);
   // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs, tile and window)
-  if (d_inputs) {
-    mx::MultiexpN2Args t{};
-    t.inputs = d_inputs;
-    t.tables = (u32*)d_ws;
-    t.consts = consts;
-    t.n_inputs = n_tables;
-    t.window = window;
-    t.limbsn = plan->limbs_n; t.limbs2 = limbs2; t.nblk = g.nblk; t.ksplit = bits - 1;
-    MX_TRY(mxm::launch_multiexp(g.K, true, t, (n_tables + gpw - 1) / gpw, s));
-  }
-  mx::MatmulN2Args a{};
+  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_tables, limbs2, window, d_ws, s));
+  // the shared-weight pass with the samples of the tile as positions: table column * tile + sample, out [tile][rows]
+  mx::SharedN2Args a{};
   a.tables = (const u32*)d_ws;
-  a.consts = consts;
+  a.consts = o.consts;
   a.index = d_index;
   a.weights = d_weights;
+  a.origin = nullptr;
   a.out = d_out;
-  a.n_cols = n_cols; a.n_shared = n_shared; a.rows = n_rows;
-  a.tile = (int)tile_batch; a.tile_blocks = (int)tile_blocks;
+  a.n_local = n_cols * tile_batch; a.n_shared = n_shared; a.rows = n_rows;
+  a.stride = (int)tile_batch;
+  a.image_positions = 1;
+  a.positions = (int)tile_batch; a.pos_blocks = (int)tile_blocks;
   a.terms = terms;
-  a.wwords = (weight_bits + 31) / 32;
   a.window = window;
-  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk;
-  return mxmm::launch_matmul(g.K, a, n_rows * tile_blocks, s);
+  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
+  return mxmm::launch_shared(o.g.K, a, n_rows * tile_blocks, s);
 }
 
-// ---- encrypted convolutions of ciphertext grids with a public kernel (mx_conv_n2.hpp) --------------------------------
-namespace mxcv { int launch_conv(int K, const mx::ConvN2Args& a, int64_t nblocks, hipStream_t s); }
-
+// ---- encrypted convolutions of ciphertext grids with a public kernel (mx_matmul_n2.hpp) ------------------------------
 extern "C" int mx_conv_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
   return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
 }
@@ -1210,47 +1214,33 @@ extern "C" int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
   if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   const int bits = plan->n_bits;
-  if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;                 // rows too narrow for N^2
   if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
-  Geometry g;
-  if (!(plan->geometries & 1) || !multiexp_geometry(bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  if (2 * g.K * g.L + 8 < limbs2 + 2) return MX_ERR_ARG;             // row wider than the staging area
-  const int gpw = 64 / g.K;
-  const int64_t pos_blocks = (n_positions + gpw - 1) / gpw;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  const int64_t pos_blocks = o.blocks(n_positions);
   if (n_rows > ((int64_t)1 << 31) / pos_blocks - 1) return MX_ERR_SIZE;       // more wavefronts than one grid holds
-  const int64_t n_tables = n_local + n_shared;
   const int64_t need = mx_conv_nsquare_workspace_bytes(bits, n_local, n_shared, LIMBS_PER_LANE, window);
   if (need < 0) return (int)need;
   if (need > ws_bytes) return MX_ERR_WORKSPACE;
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
-  const u32* consts = (const u32*)((const char*)plan->d_plan + geo_index(LIMBS_PER_LANE) * cb);
   hipStream_t s = (hipStream_t)stream;
   MxKernelTimer timer(s);
   // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
-  if (d_inputs) {
-    mx::MultiexpN2Args t{};
-    t.inputs = d_inputs;
-    t.tables = (u32*)d_ws;
-    t.consts = consts;
-    t.n_inputs = n_tables;
-    t.window = window;
-    t.limbsn = plan->limbs_n; t.limbs2 = limbs2; t.nblk = g.nblk; t.ksplit = bits - 1;
-    MX_TRY(mxm::launch_multiexp(g.K, true, t, (n_tables + gpw - 1) / gpw, s));
-  }
-  mx::ConvN2Args a{};
+  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_local + n_shared, limbs2, window, d_ws, s));
+  // the shared-weight pass: the table of the tap at position 0 + the position's origin, out [image][rows][position]
+  mx::SharedN2Args a{};
   a.tables = (const u32*)d_ws;
-  a.consts = consts;
+  a.consts = o.consts;
   a.index = d_index;
   a.weights = d_weights;
   a.origin = (const mx::i64*)d_origin;
   a.out = d_out;
   a.n_local = n_local; a.n_shared = n_shared; a.rows = n_rows;
-  a.image_positions = image_positions;
+  a.stride = 1;
+  a.image_positions = (int)image_positions;      // divides n_positions <= 2^30
   a.positions = (int)n_positions; a.pos_blocks = (int)pos_blocks;
   a.terms = terms;
-  a.wwords = (weight_bits + 31) / 32;
   a.window = window;
-  a.nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = g.nblk;
-  return mxcv::launch_conv(g.K, a, n_rows * pos_blocks, s);
+  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
+  return mxmm::launch_shared(o.g.K, a, n_rows * pos_blocks, s);
 }

@@ -11,7 +11,7 @@
 //   run pass (fixedbase_n2_run_kernel): one group of lanes per output.  acc = T[0][d_0], then one pair product by
 //     T[i][d_i] for every further window — NO squaring — with d_i read from the exponent's words (bits at exp_bits and
 //     above are masked, not trusted).  The entry of window i + 1 is requested before the product of window i runs.  Then
-//     the factor of the mode, the product by E = (1, 0) and the epilogue of powmod_n2_kernel: canonical residues.
+//     the factor of the mode, the product by E = (1, 0) and the epilogue (pair_store): canonical residues.
 //       POWER      f_r = 1
 //       ENCRYPT    f_r = 1 + m_r N, m_r < N.  In pair form value(X0, X1) = rho (X0 + X1 N), so (0, m) has the value
 //                  rho m N and ONE PAIR PRODUCT by K1 (the value R) gives m N; adding the domain's one gives 1 + m N.
@@ -46,15 +46,6 @@ struct FixedBaseN2Args {
 template <int K, int L>
 constexpr size_t fixedbase_n2_lds_bytes() { return powmod_n2_lds_bytes<K, L>(false); }
 
-template <int K, int L, class M_t>
-__device__ __forceinline__ u32* fixedbase_n2_setup(M_t& M, u32* smem, int gw, const FixedBaseN2Args& A) {
-  MultiexpN2Args sa{};                                    // the set-up reads the constants, limbsn and nblk only
-  sa.consts = A.consts;
-  sa.limbsn = A.limbsn;
-  sa.nblk = A.nblk;
-  return multiexp_n2_setup<K, L>(M, smem, gw, sa);
-}
-
 // One workgroup; every group of the wavefront walks the same chain and the first one stores.
 template <int K, int L, int W>
 __global__ void __launch_bounds__(64, 2) fixedbase_n2_chain_kernel(FixedBaseN2Args A) {
@@ -63,32 +54,15 @@ __global__ void __launch_bounds__(64, 2) fixedbase_n2_chain_kernel(FixedBaseN2Ar
   extern __shared__ u32 smem[];
   const int gw = threadIdx.x / K;
   M_t M;
-  u32* cp_lds = fixedbase_n2_setup<K, L>(M, smem, gw, A);
+  u32* cp_lds = pair_setup<K, L>(M, smem, gw, A.consts, A.limbsn, A.nblk);
   PairArith<K, L, W> P(M, cp_lds);
   const int p = M.p;
   u32* wide = smem + gw * M_t::LDS_WORDS;
   __syncthreads();
   for (int k = p; k < WIDE; k += K) wide[k] = (k < A.limbs2) ? A.base[k] : 0u;
   __syncthreads();
-  u32 lo[L], hi[L], zero[L];
-#pragma unroll
-  for (int j = 0; j < L; ++j) {
-    const int bit = W * (p * L + j);
-    const int room = A.ksplit - bit;
-    lo[j] = room <= 0 ? 0u : extract_field(wide, bit, room < W ? room : W);
-    const int hbit = A.ksplit + bit;
-    hi[j] = (hbit + W + 32 <= 32 * WIDE) ? extract_field(wide, hbit, W) : 0u;
-    zero[j] = 0u;
-  }
   u32 x0[L], x1[L], t0[L], t1[L];
-  M.load(t0, A.consts + 3 * A.limbsn, A.limbsn);
-  M.load(t1, A.consts + 4 * A.limbsn, A.limbsn);
-  P.mul(x0, x1, lo, zero, t0, t1);
-  M.load(t0, A.consts + 5 * A.limbsn, A.limbsn);
-  M.load(t1, A.consts + 6 * A.limbsn, A.limbsn);
-  P.mul(t0, t1, hi, zero, t0, t1);
-  M.add(x0, x0, t0);
-  M.add(x1, x1, t1);
+  pair_convert<W>(M, P, wide, A.consts, A.limbsn, A.ksplit, x0, x1);
   M.load(t0, A.consts + 1 * A.limbsn, A.limbsn);          // the domain's one
   M.load(t1, A.consts + 2 * A.limbsn, A.limbsn);
   const i64 entry_words = (i64)2 * L * K;
@@ -122,7 +96,7 @@ __global__ void __launch_bounds__(64, 2) fixedbase_n2_fill_kernel(FixedBaseN2Arg
   const int i = (int)(e / per);
   const u32 d = 2u + (u32)(e - (i64)i * per);
   M_t M;
-  u32* cp_lds = fixedbase_n2_setup<K, L>(M, smem, gw, A);
+  u32* cp_lds = pair_setup<K, L>(M, smem, gw, A.consts, A.limbsn, A.nblk);
   PairArith<K, L, W> P(M, cp_lds);
   const int p = M.p;
   const i64 entry_words = (i64)2 * L * K;
@@ -167,7 +141,6 @@ __device__ __forceinline__ u32 fixedbase_digit(const u32* e, int ewords, int exp
 template <int K, int L, int W>
 __global__ void __launch_bounds__(64, 2) fixedbase_n2_run_kernel(FixedBaseN2Args A) {
   using M_t = Mont<K, L, W, true>;
-  constexpr int S = M_t::S;
   constexpr int GPW = 64 / K;
   constexpr int WIDE = M_t::LDS_WORDS;
   extern __shared__ u32 smem[];
@@ -175,7 +148,7 @@ __global__ void __launch_bounds__(64, 2) fixedbase_n2_run_kernel(FixedBaseN2Args
   const i64 raw = (i64)blockIdx.x * GPW + gw;
   const i64 r = raw < A.count ? raw : A.count - 1;        // surplus groups redo the last output and store nothing
   M_t M;
-  u32* cp_lds = fixedbase_n2_setup<K, L>(M, smem, gw, A);
+  u32* cp_lds = pair_setup<K, L>(M, smem, gw, A.consts, A.limbsn, A.nblk);
   PairArith<K, L, W> P(M, cp_lds);
   const int p = M.p;
   u32* wide = smem + gw * M_t::LDS_WORDS;
@@ -212,7 +185,8 @@ __global__ void __launch_bounds__(64, 2) fixedbase_n2_run_kernel(FixedBaseN2Args
     __syncthreads();
     for (int k = p; k < WIDE; k += K) wide[k] = (k < A.oplimbs) ? src[k] : 0u;
     __syncthreads();
-    // RANDOMIZE: the two halves of c = c_lo + 2^k c_hi; ENCRYPT: the whole message as one digit (no split)
+    // RANDOMIZE: the two halves of c = c_lo + 2^k c_hi; ENCRYPT: the whole message as one digit (no split) — the split
+    // point, the digit that carries lo and the second term all depend on the mode, so this is not pair_convert
     const int ks = enc ? 32 * WIDE : A.ksplit;
     u32 lo[L], hi[L], zero[L];
 #pragma unroll
@@ -244,55 +218,7 @@ __global__ void __launch_bounds__(64, 2) fixedbase_n2_run_kernel(FixedBaseN2Args
     M.add(x1, x1, t1);
     P.mul(acc0, acc1, acc0, acc1, x0, x1);
   }
-  // the last product, by E = (1, 0): the N-adic digits of the residue (mx_powmod_n2.hpp)
-  {
-    u32 e0[L], e1[L];
-    M.set_small(e0, 1u);
-    M.set_small(e1, 0u);
-    P.mul(acc0, acc1, acc0, acc1, e0, e1);
-  }
-  // ---- epilogue of powmod_n2_kernel: digits into [0, N), then z = Y0 + Y1 * N by a plain product
-  {
-    u64 t[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) t[j] = acc0[j];
-    M.normalize_full(acc0, t);
-    const u32 carry = M.cond_sub(acc0);
-#pragma unroll
-    for (int j = 0; j < L; ++j) t[j] = acc1[j];
-    if (p == 0) t[0] += carry;
-    M.normalize_full(acc1, t);
-    M.cond_sub(acc1);
-  }
-  u32 hi[L];
-  __syncthreads();
-  M.template mulx<M_t::F_INIT | M_t::F_PLAIN>(hi, acc1, M.n, acc1, M.n, acc0, nullptr, wide, A.nblk);
-  {
-    u64 t[L];
-#pragma unroll
-    for (int j = 0; j < L; ++j) t[j] = hi[j];
-    M.normalize_full(hi, t);
-  }
-  const int it = A.nblk * L;
-#pragma unroll
-  for (int j = 0; j < L; ++j) wide[it + p * L + j] = hi[j];
-  if (p == 0) { wide[it + S] = 0; wide[it + S + 1] = 0; wide[it + S + 2] = 0; wide[it + S + 3] = 0; }
-  __syncthreads();
-  const bool valid = raw < A.count;
-  u32* dst = A.out + r * A.limbs2;
-  const int nl = it + S;
-  for (int k = p; k < A.limbs2; k += K) {
-    const int bit = 32 * k;
-    const int g = bit / W, off = bit - g * W;
-    u32 o = 0;
-    if (g < nl) {
-      u64 v = (u64)wide[g] >> off;
-      v |= (u64)wide[g + 1] << (W - off);
-      if (2 * W - off < 32) v |= (u64)wide[g + 2] << (2 * W - off);
-      o = (u32)v;
-    }
-    if (valid) dst[k] = o;
-  }
+  pair_store<K, W>(M, P, acc0, acc1, wide, A.nblk, A.out + r * A.limbs2, A.limbs2, raw < A.count);
 }
 
 }  // namespace mx

@@ -31,6 +31,9 @@ constexpr size_t pack_n2_lds_bytes() { return powmod_n2_lds_bytes<K, L>(false); 
 
 // Two wavefronts per SIMD: the accumulator pair stays live across the conversion's two products, and bounded to three
 // (168 VGPRs) the compiler spilled 288-312 B per lane.  A launch of 10^5 values at key_length 2048 is ~200 wavefronts.
+// The conversion and the epilogue below are this kernel's own copies of pair_convert and pair_store (mx_powmod_n2.hpp):
+// built on the shared functions the kernel kept its registers but measured 5.5 % slower (18.2 -> 19.2 ms for the chain of
+// 64 slots of 32 bits at key_length 2048, profiles/r12_fold_probes_ab.txt), so only the set-up is shared here.
 template <int K, int L, int W>
 __global__ void __launch_bounds__(64, 2) pack_n2_kernel(PackN2Args A) {
   using M_t = Mont<K, L, W, true>;
@@ -43,14 +46,7 @@ __global__ void __launch_bounds__(64, 2) pack_n2_kernel(PackN2Args A) {
   const i64 raw = (i64)blockIdx.x * GPW + gw;
   const i64 r = raw < A.outputs ? raw : A.outputs - 1;   // surplus groups redo the last output and store nothing
   M_t M;
-  u32* cp_lds;
-  {
-    MultiexpN2Args sa{};                                  // the set-up reads the constants, limbsn and nblk only
-    sa.consts = A.consts;
-    sa.limbsn = A.limbsn;
-    sa.nblk = A.nblk;
-    cp_lds = multiexp_n2_setup<K, L>(M, smem, gw, sa);
-  }
+  u32* cp_lds = pair_setup<K, L>(M, smem, gw, A.consts, A.limbsn, A.nblk);
   PairArith<K, L, W> P(M, cp_lds);
   const int p = M.p;
   u32* wide = smem + gw * M_t::LDS_WORDS;

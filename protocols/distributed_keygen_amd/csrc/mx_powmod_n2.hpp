@@ -190,6 +190,114 @@ __device__ __forceinline__ u32 extract_field(const u32* words, int bitpos, int n
   return (u32)(v >> off) & (nbits >= 32 ? 0xFFFFFFFFu : ((1u << nbits) - 1u));
 }
 
+// ---- set-up, conversion and epilogue of the homomorphic kernels: the shared-weight kernel (mx_matmul_n2.hpp), the
+// fixed-base kernels (mx_fixedbase_n2.hpp) and the pack kernel's set-up.  powmod_n2_kernel and the two-wavefront kernels
+// keep their own: theirs are interleaved with the tape and the scratch slots.  So do the multiexp kernels and, but for
+// the set-up, the pack kernel: on these functions they measured slower (notes in mx_multiexp_n2.hpp, mx_pack_n2.hpp).  `consts` are the plan's constant rows of the geometry, [8][limbsn]: N, ONE0, ONE1,
+// K1_0, K1_1, K2_0, K2_1, C'.
+
+// Set-up: the group's Montgomery state and C' in LDS (one copy per workgroup); returns the LDS address of C'.
+template <int K, int L, class M_t>
+__device__ __forceinline__ u32* pair_setup(M_t& M, u32* smem, int gw, const u32* consts, int limbsn, int nblk) {
+  constexpr int GPW = 64 / K;
+  M.init(smem + gw * M_t::LDS_WORDS, nblk);
+  M.load(M.n, consts, limbsn);
+  M.setup_modulus();
+  u32* cp_lds = smem + GPW * M_t::LDS_WORDS;
+  u32 v[L];
+  M.load(v, consts + 7 * limbsn, limbsn);
+  if (gw == 0) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) cp_lds[M.p * L + j] = v[j];
+  }
+  __syncthreads();
+  return cp_lds;
+}
+
+// Conversion: the residue x < N^2 staged in the group's LDS area `wide` (LDS_WORDS words, zero padded) into pair form,
+// x = (x_lo, 0) * K1 + (x_hi, 0) * K2 with x = x_lo + 2^ksplit x_hi as powmod_n2_kernel's prologue splits it.  The
+// constant pairs are loaded where they are used (keeping them all in registers spilled).
+template <int W, int L, class M_t>
+__device__ __forceinline__ void pair_convert(M_t& M, PairArithT<M_t>& P, const u32* wide, const u32* consts, int limbsn,
+                                             int ksplit, u32 (&x0)[L], u32 (&x1)[L]) {
+  constexpr int WIDE = M_t::LDS_WORDS;
+  u32 lo[L], hi[L], zero[L];
+#pragma unroll
+  for (int j = 0; j < L; ++j) {
+    const int bit = W * (M.p * L + j);
+    const int room = ksplit - bit;
+    lo[j] = room <= 0 ? 0u : extract_field(wide, bit, room < W ? room : W);
+    const int hbit = ksplit + bit;
+    hi[j] = (hbit + W + 32 <= 32 * WIDE) ? extract_field(wide, hbit, W) : 0u;
+    zero[j] = 0u;
+  }
+  u32 t0[L], t1[L];
+  M.load(t0, consts + 3 * limbsn, limbsn);
+  M.load(t1, consts + 4 * limbsn, limbsn);
+  P.mul(x0, x1, lo, zero, t0, t1);
+  M.load(t0, consts + 5 * limbsn, limbsn);
+  M.load(t1, consts + 6 * limbsn, limbsn);
+  P.mul(t0, t1, hi, zero, t0, t1);
+  M.add(x0, x0, t0);
+  M.add(x1, x1, t1);
+}
+
+// Epilogue: the accumulator pair into the canonical residue in [0, N^2) at dst[0 .. limbs2).  The last product, by
+// E = (1, 0), leaves the N-adic digits of the residue; both are normalised into [0, N), z = Y0 + Y1 * N is a plain
+// product, and its W-bit limbs are repacked into 32-bit words through the group's LDS area.  Every group runs all of
+// it (barriers); only `valid` ones store.
+template <int K, int W, int L, class M_t>
+__device__ __forceinline__ void pair_store(M_t& M, PairArithT<M_t>& P, u32 (&acc0)[L], u32 (&acc1)[L], u32* wide, int nblk,
+                                           u32* dst, int limbs2, bool valid) {
+  constexpr int S = M_t::S;
+  const int p = M.p;
+  {
+    u32 e0[L], e1[L];
+    M.set_small(e0, 1u);
+    M.set_small(e1, 0u);
+    P.mul(acc0, acc1, acc0, acc1, e0, e1);
+  }
+  {
+    u64 t[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) t[j] = acc0[j];
+    M.normalize_full(acc0, t);
+    const u32 carry = M.cond_sub(acc0);
+#pragma unroll
+    for (int j = 0; j < L; ++j) t[j] = acc1[j];
+    if (p == 0) t[0] += carry;
+    M.normalize_full(acc1, t);
+    M.cond_sub(acc1);
+  }
+  u32 hi[L];
+  __syncthreads();
+  M.template mulx<M_t::F_INIT | M_t::F_PLAIN>(hi, acc1, M.n, acc1, M.n, acc0, nullptr, wide, nblk);
+  {
+    u64 t[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) t[j] = hi[j];
+    M.normalize_full(hi, t);
+  }
+  const int it = nblk * L;
+#pragma unroll
+  for (int j = 0; j < L; ++j) wide[it + p * L + j] = hi[j];
+  if (p == 0) { wide[it + S] = 0; wide[it + S + 1] = 0; wide[it + S + 2] = 0; wide[it + S + 3] = 0; }
+  __syncthreads();
+  const int nl = it + S;
+  for (int k = p; k < limbs2; k += K) {
+    const int bit = 32 * k;
+    const int g = bit / W, off = bit - g * W;
+    u32 o = 0;
+    if (g < nl) {
+      u64 v = (u64)wide[g] >> off;
+      v |= (u64)wide[g + 1] << (W - off);
+      if (2 * W - off < 32) v |= (u64)wide[g + 2] << (2 * W - off);
+      o = (u32)v;
+    }
+    if (valid) dst[k] = o;
+  }
+}
+
 #ifdef MX_DEV_PRIVATE_PAD_WORDS
 // Developer build only (tools/build_variant.py -DMX_DEV_PRIVATE_PAD_WORDS=n, tools/concurrency_census.py): every lane of the
 // one-wavefront pair kernel keeps a private array of n words in scratch memory, writes a pattern that names its

@@ -1100,7 +1100,7 @@ class Engine:
     def conv2d_nsquare_t(self, x_t, shape, weights, n: int, bias: Optional[Sequence[int]] = None, stride=1, padding=0,
                          dilation=1, window: int = 0, table_budget: Optional[int] = None):
         """Y[b][o][y][x] = (1 + (bias_o mod n) n) * prod_(c,i,j) X[b][c][y sh - ph + i dh][x sw - pw + j dw]^w[o][c][i][j]
-        mod n^2: B grids of ciphertexts under ONE public kernel, on the device (csrc/mx_conv_n2.hpp).
+        mod n^2: B grids of ciphertexts under ONE public kernel, on the device (csrc/mx_matmul_n2.hpp).
         Cross-correlation, the convention of torch.nn.functional.conv2d; a tap outside the grid contributes 1.
 
         ``x_t``: ``[B * C * H * W, limbs2]`` rows of residues below n^2 with ``shape = (B, C, H, W)``; ``weights``:
@@ -1952,8 +1952,8 @@ class Engine:
         return [list(map(bool, arr[g])) for g in range(groups)]
 
 
-class _MultiexpBackend:
-    """multiexp_plan.execute over device rows of one Engine and modulus."""
+class _N2Backend:
+    """What the planners' backends share: device rows [*, limbs2] of one Engine and modulus."""
 
     def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
         self.eng, self.n, self.limbs2, self.n_bits = eng, n, limbs2, n_bits
@@ -1963,14 +1963,21 @@ class _MultiexpBackend:
     def _index(self, positions):
         return self.torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.eng.device)
 
+    def _empty(self, rows: int = 0):
+        return self.torch.empty((rows, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
+
+    def bias_rows(self, residues):
+        return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
+
+
+class _MultiexpBackend(_N2Backend):
+    """multiexp_plan.execute over device rows of one Engine and modulus."""
+
     def take(self, rows_t, positions):
         return rows_t.index_select(0, self._index(positions)).contiguous()
 
     def invert(self, rows_t):
         return self.eng.modinv_t(rows_t, self.n * self.n)
-
-    def bias_rows(self, residues):
-        return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
 
     def gather(self, inputs_t, inv_t, bias_t, parts):
         pools = [inputs_t] + [t for t in (inv_t, bias_t) if t is not None]
@@ -1985,9 +1992,9 @@ class _MultiexpBackend:
         return self.take(pool, [base[kind] + k for kind, k in parts])
 
     def run(self, tables_t, n_tables, launch, window):
-        eng, torch = self.eng, self.torch
+        eng = self.eng
         rows, terms = launch.index.shape
-        out_t = torch.empty((rows, self.limbs2), dtype=torch.int32, device=eng.device)
+        out_t = self._empty(rows)
         idx_t = eng.to_device(launch.index.view(np.uint32))
         w_t = eng.to_device(launch.weights.reshape(rows, -1))
         eng._call("mx_multiexp_nsquare_run", self.plan.desc, tables_t.data_ptr() if tables_t is not None else None, n_tables, self.limbs2,
@@ -2014,28 +2021,20 @@ class _MultiexpBackend:
                 outs.append(t)
             index.append(first[id(t)] + r)
         if not index:
-            return torch.empty((0, self.limbs2), dtype=torch.int32, device=self.eng.device)
+            return self._empty()
         pool = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
         return self.take(pool, index)
 
     rows_of = assemble = _pick          # the two names multiexp_plan.execute calls
 
 
-class _MatmulBackend:
+class _MatmulBackend(_N2Backend):
     """multiexp_plan.execute_matmul over device rows of one Engine and modulus.  A column block is a tensor
     [columns, samples, limbs2]; the launch arrays go to the device once per call."""
 
     def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
-        self.eng, self.n, self.limbs2, self.n_bits = eng, n, limbs2, n_bits
-        self.torch = eng.torch
-        self.plan = eng.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+        super().__init__(eng, n, limbs2, n_bits)
         self._arrays: Dict[int, Tuple[Any, Any]] = {}
-
-    def _index(self, positions):
-        return self.torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.eng.device)
-
-    def _empty(self, rows: int = 0):
-        return self.torch.empty((rows, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
 
     def columns(self, inputs_t, n_inputs, batch, cols):
         return inputs_t.view(batch, n_inputs, self.limbs2).index_select(1, self._index(cols)).permute(1, 0, 2).contiguous()
@@ -2045,9 +2044,6 @@ class _MatmulBackend:
 
     def tile(self, block_t, batch, lo, hi):
         return block_t[:, lo:hi, :].reshape(-1, self.limbs2)
-
-    def bias_rows(self, residues):
-        return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
 
     def concat(self, parts):
         return self._empty() if not parts else (parts[0] if len(parts) == 1 else self.torch.cat(parts, dim=0))

@@ -218,3 +218,50 @@ def test_randomizer_changes_the_ciphertexts_and_not_the_plaintexts(eng, round_tr
     assert [len(ys) for ys in fresh] == [8] * 4
     assert all(f != p for fs, ps in zip(fresh, plain) for f, p in zip(fs, ps))
     assert threshold_decrypt(eng, key, [v for ys in fresh for v in ys]) == [v for row in want for v in row]
+
+
+@pytest.mark.parametrize("case,tile,window", [("key128", 70, 1), ("key128", 70, 4), ("odd8000", 3, 4)])
+def test_matrix_product_and_convolution_entry_points_agree_on_the_one_kernel(eng, case, tile, window):
+    """One product through mx_matmul_nsquare_run (stride = tile, no origin array) and through mx_conv_nsquare_run
+    (index * tile, origin = 0 .. tile - 1, stride 1, one position per image): the same launch of the shared-weight
+    kernel said twice, so both results are bit-identical to each other and to pow.  Three table columns and a tile of
+    two or more samples make a dropped or misplaced stride visible; every row names the one shared table through a
+    negative index.  key_length 128 runs groups of one lane (a full and a ragged wavefront per row at 70 samples), the
+    8000-bit modulus groups of 32 (two per wavefront: one surplus group per row at 3 samples)."""
+    import numpy as np
+    import torch
+
+    from protocols.distributed_keygen_amd import limbs
+    from protocols.distributed_keygen_amd import multiexp_plan as mp
+    from protocols.distributed_keygen_amd.engine import _ConvBackend
+
+    rng = random.Random(f"one kernel {case} {tile} {window}")
+    n = key_n(128) if case == "key128" else odd_modulus(8000, rng)
+    n2 = n * n
+    cols, rows = 3, 3
+    lanes = ctypes.c_int()
+    assert eng.lib.mx_matmul_nsquare_shape(n.bit_length(), cols, rows, cols + 1, 16, tile, 1 << 40, 0, 0, lanes, ctypes.c_int(),
+                                           ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()) == 0
+    assert lanes.value == (1 if case == "key128" else 32)
+    x = [[rng.randrange(1, n2) for _ in range(tile)] for _ in range(cols)]          # x[column][sample]
+    shared = rng.randrange(1, n2)
+    orders = [[0, 1, 2, -1], [-1, 2, 0, 1], [1, -1, 2, 0]]                          # ~(-1) = shared table 0
+    W = [[rng.randrange(1, 1 << 16) for _ in range(cols + 1)] for _ in range(rows)]
+    W[1][2] = 0                                                                     # a zero weight among the terms
+    index = np.array(orders, dtype=np.int32)
+    weights = np.array(W, dtype=np.uint32).reshape(rows, cols + 1, 1)
+    as_matmul = mp.Launch(rows=list(range(rows)), index=index, weights=weights, weight_bits=16)
+    as_conv = mp.Launch(rows=list(range(rows)), index=np.where(index >= 0, index * tile, index).astype(np.int32),
+                        weights=weights, weight_bits=16)
+    jobs = [((x[i][b] if i >= 0 else shared), W[j][t], n2) for b in range(tile) for j in range(rows) for t, i in enumerate(orders[j])]
+    powers = hostpow.powmod_many(jobs)
+    want = [math.prod(powers[k : k + cols + 1]) % n2 for k in range(0, len(powers), cols + 1)]          # [sample][row]
+    limbs2 = limbs.limbs_for(n2)
+    be = _ConvBackend(eng, n, limbs2, n.bit_length())
+    tables_t = eng.to_device(limbs.pack_reduced([v for col in x for v in col] + [shared], limbs2, n2))
+    got_matmul = be.run_matmul(tables_t, cols, 1, tile, as_matmul, window)
+    got_conv = be.run_conv(tables_t, cols * tile, 1, as_conv, window, np.arange(tile, dtype=np.int64), 1)
+    assert got_matmul.shape == got_conv.shape == (tile * rows, limbs2)
+    assert torch.equal(got_matmul, got_conv)
+    assert limbs.unpack(eng.to_host(got_matmul)) == want
+    assert limbs.unpack(eng.to_host(got_conv)) == want

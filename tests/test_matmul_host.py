@@ -401,3 +401,20 @@ def test_abi_refuses_bad_arguments_without_a_launch():
     assert call(plan=_lib.NsquarePlan(d_plan=ptr, limbs_n=625, n_bits=20000, geometries=1), limbs2=1250) == -2
     assert call(rows=1 << 40) == -2                                                          # beyond one grid
     assert call(ws_bytes=1024) == -4
+
+
+@pytest.mark.parametrize("rows,terms,splits", [(4, 200000, True), (4, 513, True), (4, 64, False), (100000, 513, False)])
+def test_one_split_k_rule_for_the_linear_map_and_the_matrix_product(rows, terms, splits):
+    """For one sample in a tile of one, the matrix product's outputs are the linear map's: both shape queries must cut
+    the terms into the same chunks — few rows with more than 64 terms split, 64 terms or rows that fill the device do not."""
+    from protocols.distributed_keygen_amd import _lib
+
+    lib = _lib.lib()
+    for n_bits in (128, 2048):
+        k, l, w, k2, l2, w2 = (ctypes.c_int() for _ in range(6))
+        tile, chunk, chunk2 = (ctypes.c_int64() for _ in range(3))
+        assert lib.mx_matmul_nsquare_shape(n_bits, 32, rows, terms, 16, 1, 1 << 40, 0, 0, k, l, w, tile, chunk) == 0
+        assert lib.mx_multiexp_nsquare_shape(n_bits, 32, rows, terms, 16, 0, 0, k2, l2, w2, chunk2) == 0
+        assert tile.value == 1 and (k.value, l.value) == (k2.value, l2.value)
+        assert chunk.value == chunk2.value
+        assert (64 <= chunk.value < terms) if splits else chunk.value == terms
