@@ -4,7 +4,8 @@
 
 — cross-correlation, the convention of ``torch.nn.functional.conv2d``; a tap outside the grid contributes 1.  The kernels
 are weight rows shared by every output position, as the rows of ``multiexp_plan.plan_matmul`` are shared by every sample,
-and the same pieces are reused here (Launch, buckets, split-K whose second pass runs on mx_matmul_nsquare_run).  What
+and the same pieces are reused here (the refusals, bias_residues, sign_split, split_k and combine_launches, whose second
+pass runs on mx_matmul_nsquare_run, and the plan's two-pass fields, TwoPassPlan).  What
 differs is the table set: the tables are the PIXELS of the padded grids, one each however many windows cover it, and a
 term names the table of its tap at output position 0; the kernel adds the position's origin.  Everything is planned once
 per call, whatever B and H' W':
@@ -27,11 +28,12 @@ per call, whatever B and H' W':
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .multiexp_plan import TABLE_BUDGET_BYTES, Launch, Term, _bucket_launches, weight_bound
+from .multiexp_plan import (TABLE_BUDGET_BYTES, Term, TwoPassPlan, _bucket_launches, bias_residues, check_weights, combine_launches,
+                            sign_split, split_k, weight_bound)
 
 
 def _pair(v: Any, name: str, least: int) -> Tuple[int, int]:
@@ -82,7 +84,8 @@ def kernel_array(weights: Any) -> np.ndarray:
 
 
 @dataclass
-class ConvPlan:
+class ConvPlan(TwoPassPlan):
+    """Launch.index >= 0 in pass 1: the table of the tap at position 0; pass 2 runs on mx_matmul_nsquare_run."""
     shape: Tuple[int, int, int, int]      # (B, C, H, W) of the input
     n_rows: int                           # O, the kernels
     kernel: Tuple[int, int]
@@ -93,17 +96,9 @@ class ConvPlan:
     out_w: int
     x_ch: List[int]                       # channels with a grid of their own (a positive tap somewhere), ascending
     inverted: List[int]                   # channels whose inverses get a grid (a negative tap somewhere), ascending
-    bias: Dict[int, int]                  # kernel -> b mod N (non-zero); shared table k belongs to sorted(bias)[k]
-    window: int
-    chunk: int
     tile_images: int                      # images per tile (1 when an image is cut into bands)
     band_rows: int                        # output rows per tile (out_h when tiles hold whole images)
-    launches: List[Launch]                # pass 1: index >= 0: table of the tap at position 0, < 0: shared table -1 - index
     origin: np.ndarray                    # [tile_images * band_rows * out_w] int64: a ragged tile takes a prefix
-    pass1_rows: int
-    part_rows: List[int]                  # pass-1 rows that are pieces of split kernels = the table columns of pass 2
-    combine: List[Launch]                 # pass 2 (empty if no kernel was split), on mx_matmul_nsquare_run
-    result: List[Tuple[str, int]]         # per kernel: ("one", 0) | ("p1", pass-1 row) | ("p2", pass-2 row)
 
     @property
     def n_grids(self) -> int:
@@ -151,8 +146,7 @@ def plan_conv(weights: Any, shape: Sequence[int], n: int, bias: Optional[Sequenc
         raise ValueError(f"the kernel has {kc} channels, the grids have {C}")
     if kh < 1 or kw < 1:
         raise ValueError("the kernel must have at least one tap per channel")
-    if bias is not None and len(bias) != O:
-        raise ValueError(f"{len(bias)} bias values for {O} kernels")
+    bias_res = bias_residues(bias, O, n, "kernels")
     Hp, Wp = H + 2 * ph, W + 2 * pw
     span_h, span_w = dh * (kh - 1) + 1, dw * (kw - 1) + 1
     if O and B and (span_h > Hp or span_w > Wp):                 # (no grid: nothing to compare the kernel with)
@@ -167,23 +161,17 @@ def plan_conv(weights: Any, shape: Sequence[int], n: int, bias: Optional[Sequenc
             for i in range(kh):
                 for j in range(kw):
                     w = int(arr[o, c, i, j])
-                    if w == 0:
-                        continue
-                    if -bound >= w or w >= bound:
-                        raise ValueError(f"kernel {o}: |weight| >= 2^(bits(N^2) + 64)")
-                    (pos if w > 0 else neg).add(c)
-                    row.append((c, i, j, w))
+                    if w:
+                        (pos if w > 0 else neg).add(c)
+                        row.append((c, i, j, w))
+        check_weights([w for _, _, _, w in row], bound, "kernel", o)
         taps.append(row)
-    bias_res = {j: int(b) % n for j, b in enumerate(bias)} if bias is not None else {}
-    bias_res = {j: b for j, b in bias_res.items() if b}
     shared_of = {j: k for k, j in enumerate(sorted(bias_res))}
-    x_ch, inverted = sorted(pos), sorted(neg)
-    grid_of = {("x", c): g for g, c in enumerate(x_ch)}
-    grid_of.update({("inv", c): len(x_ch) + g for g, c in enumerate(inverted)})
+    x_ch, inverted, grid_of = sign_split(pos, neg)
     G = len(grid_of)
     term_rows: List[List[Term]] = []
     for o, row in enumerate(taps):
-        terms = [((i * dh * G + grid_of[("x" if w > 0 else "inv", c)]) * Wp + j * dw, abs(w)) for c, i, j, w in row]
+        terms = [((i * dh * G + grid_of[c if w > 0 else ~c]) * Wp + j * dw, abs(w)) for c, i, j, w in row]
         if o in shared_of:
             terms.append((-1 - shared_of[o], 1))
         term_rows.append(terms)
@@ -221,38 +209,15 @@ def plan_conv(weights: Any, shape: Sequence[int], n: int, bias: Optional[Sequenc
     _, chunk, _ = shape_fn(tile_images * rows_in(band_rows) * per_row + n_shared if out_h else n_shared,
                            O * tile_images * band_rows * out_w, max_terms, max_bits, win)
     chunk = max(1, int(chunk))
-    # split-K: pieces of a kernel are weight rows of their own
-    p1: List[List[Term]] = []
-    result: List[Tuple[str, int]] = []
-    split: List[List[int]] = []
-    for terms in term_rows:
-        if not terms:
-            result.append(("one", 0))
-            continue
-        ks = []
-        for lo in range(0, len(terms), chunk):
-            ks.append(len(p1))
-            p1.append(terms[lo : lo + chunk])
-        if len(ks) == 1:
-            result.append(("p1", ks[0]))
-        else:
-            result.append(("p2", len(split)))
-            split.append(ks)
-    launches = _bucket_launches(p1, list(range(len(p1))))
-    part_rows = [k for ks in split for k in ks]
-    combine: List[Launch] = []
-    if split:
-        local, at = [], 0
-        for ks in split:
-            local.append([(at + t, 1) for t in range(len(ks))])
-            at += len(ks)
-        combine = _bucket_launches(local, list(range(len(split))))
+    p1, result, split = split_k(term_rows, chunk)
     m, y, x = np.meshgrid(np.arange(tile_images, dtype=np.int64), np.arange(band_rows, dtype=np.int64),
                           np.arange(out_w, dtype=np.int64), indexing="ij")
     origin = ((m * rows_in(band_rows) + y * sh) * per_row + x * sw).reshape(-1) if out_h else np.zeros(0, dtype=np.int64)
-    plan = ConvPlan((B, C, H, W), O, (kh, kw), (sh, sw), (ph, pw), (dh, dw), out_h, out_w, x_ch, inverted, bias_res, win,
-                    chunk, tile_images, band_rows, launches, np.ascontiguousarray(origin, dtype=np.int64), len(p1),
-                    part_rows, combine, result)
+    plan = ConvPlan(bias=bias_res, window=win, chunk=chunk, launches=_bucket_launches(p1, list(range(len(p1)))),
+                    pass1_rows=len(p1), part_rows=[k for ks in split for k in ks], combine=combine_launches(split),
+                    result=result, shape=(B, C, H, W), n_rows=O, kernel=(kh, kw), stride=(sh, sw), padding=(ph, pw),
+                    dilation=(dh, dw), out_h=out_h, out_w=out_w, x_ch=x_ch, inverted=inverted, tile_images=tile_images,
+                    band_rows=band_rows, origin=np.ascontiguousarray(origin, dtype=np.int64))
     check_addresses(plan)
     return plan
 
@@ -292,10 +257,7 @@ def execute_conv(plan: ConvPlan, be: Any, inputs: Any) -> Any:
     shared = sorted(plan.bias)
     grids = be.grids(inputs, plan.shape, plan.x_ch, plan.inverted, plan.padding) if plan.n_grids else None
     bias_rows = be.bias_rows([plan.bias[j] for j in shared]) if shared else None
-    where1 = {rid: (1, k, r) for k, launch in enumerate(plan.launches) for r, rid in enumerate(launch.rows)}
-    where2 = {rid: (2, k, r) for k, launch in enumerate(plan.combine) for r, rid in enumerate(launch.rows)}
-    part_picks = [where1[m] for m in plan.part_rows]
-    picks = [None if kind == "one" else (where1[v] if kind == "p1" else where2[v]) for kind, v in plan.result]
+    part_picks, picks = plan.picks()
     done = []
     for m0, m1, y0, y1 in plan.tiles():
         images, ipos = m1 - m0, (y1 - y0) * plan.out_w

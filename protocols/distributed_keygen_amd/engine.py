@@ -274,6 +274,9 @@ class Engine:
         """ints -> device rows of their residues (limbs.pack_reduced), through a pageable copy."""
         return self.to_device(_limbs.pack_reduced(values, limbs, moduli))
 
+    def _empty_rows(self, limbs: int, rows: int = 0):
+        return self.torch.empty((rows, limbs), dtype=self.torch.int32, device=self.device)
+
     def _download_ints(self, rows_t) -> List[int]:
         """Device rows -> ints, through a pageable copy."""
         return _limbs.unpack(self.to_host(rows_t))
@@ -1030,7 +1033,7 @@ class Engine:
         _check_modulus(n)
         return mp.plan_matmul(weights, n_inputs, n, bias, batch,
                               lambda *a: self.matmul_nsquare_shape(n, *a),
-                              table_budget=mp.TABLE_BUDGET_BYTES if table_budget is None else int(table_budget), window=int(window))
+                              table_budget=_table_budget(table_budget), window=int(window))
 
     def matmul_nsquare_t(self, x_t, batch: int, weights, n: int, bias: Optional[Sequence[int]] = None, window: int = 0,
                          table_budget: Optional[int] = None):
@@ -1080,22 +1083,18 @@ class Engine:
         plan = self._matmul_plan(n, n_inputs, len(samples), weights, bias)         # every refusal of W and bias: before any launch
         if plan.n_rows == 0:
             return [[] for _ in samples]
-        if n_inputs:
-            x_t = self._upload_ints([c for smp in samples for c in smp], limbs2, n2)
-        else:
-            x_t = self.torch.empty((0, limbs2), dtype=self.torch.int32, device=self.device)
+        x_t = self._upload_ints([c for smp in samples for c in smp], limbs2, n2) if n_inputs else self._empty_rows(limbs2)
         flat = self._download_ints(self._freshened(self._matmul_run_t(x_t, len(samples), n, plan), fixed_base))
         return [flat[b * plan.n_rows : (b + 1) * plan.n_rows] for b in range(len(samples))]
 
     # ------------------------------------------------------------------ encrypted convolutions with a public kernel
     def _conv_plan(self, n: int, shape, weights, bias, stride, padding, dilation, window: int = 0, table_budget=None):
         from . import conv_plan as cp
-        from . import multiexp_plan as mp
 
         _check_modulus(n)
         return cp.plan_conv(weights, shape, n, bias, lambda a, b, c, d, w: self.multiexp_nsquare_shape(n, a, b, c, d, w),
                             stride=stride, padding=padding, dilation=dilation,
-                            table_budget=mp.TABLE_BUDGET_BYTES if table_budget is None else int(table_budget), window=int(window))
+                            table_budget=_table_budget(table_budget), window=int(window))
 
     def conv2d_nsquare_t(self, x_t, shape, weights, n: int, bias: Optional[Sequence[int]] = None, stride=1, padding=0,
                          dilation=1, window: int = 0, table_budget: Optional[int] = None):
@@ -1132,10 +1131,7 @@ class Engine:
         shape, flat = _grid_shape(x)
         n2, limbs2 = _nsquare(n)
         plan = self._conv_plan(n, shape, weights, bias, stride, padding, dilation)      # every refusal of the kernel: before any launch
-        if flat:
-            x_t = self._upload_ints(flat, limbs2, n2)
-        else:
-            x_t = self.torch.empty((0, limbs2), dtype=self.torch.int32, device=self.device)
+        x_t = self._upload_ints(flat, limbs2, n2) if flat else self._empty_rows(limbs2)
         vals = self._download_ints(self._freshened(self._conv_run_t(x_t, n, plan), fixed_base)) if shape[0] and plan.n_rows else []
         o, oh, ow = plan.n_rows, plan.out_h, plan.out_w
         return [[[vals[((b * o + j) * oh + y) * ow : ((b * o + j) * oh + y + 1) * ow] for y in range(oh)] for j in range(o)]
@@ -1964,10 +1960,24 @@ class _N2Backend:
         return self.torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.eng.device)
 
     def _empty(self, rows: int = 0):
-        return self.torch.empty((rows, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
+        return self.eng._empty_rows(self.limbs2, rows)
 
     def bias_rows(self, residues):
         return self.eng._upload_ints([1 + b * self.n for b in residues], self.limbs2, self.n * self.n)
+
+    def _pooled_select(self, views, picks, dim, one_shape):
+        """For picks = [(view, entry) or None]: the entries along `dim` of the views laid one behind the other; None picks
+        the value one, a block of `one_shape` (1 along `dim`) laid behind them."""
+        torch = self.torch
+        first = [0]
+        for v in views:
+            first.append(first[-1] + v.shape[dim])
+        if None in picks:
+            one = torch.zeros(one_shape, dtype=torch.int32, device=self.eng.device)
+            one[..., 0] = 1
+            views = views + [one]
+        pool = views[0] if len(views) == 1 else torch.cat(views, dim=dim)
+        return pool.index_select(dim, self._index([first[-1] if pk is None else first[pk[0]] + pk[1] for pk in picks]))
 
 
 class _MultiexpBackend(_N2Backend):
@@ -2003,27 +2013,14 @@ class _MultiexpBackend(_N2Backend):
         return out_t
 
     def _pick(self, picks):
-        torch = self.torch
-        outs, first, index = [], {}, []
-        one = None
-        for pk in picks:
-            if pk is None:
-                if one is None:
-                    one = torch.zeros((1, self.limbs2), dtype=torch.int32, device=self.eng.device)
-                    one[0, 0] = 1
-                    first[id(one)] = sum(t.shape[0] for t in outs)
-                    outs.append(one)
-                index.append(first[id(one)])
-                continue
-            t, r = pk
-            if id(t) not in first:
-                first[id(t)] = sum(u.shape[0] for u in outs)
-                outs.append(t)
-            index.append(first[id(t)] + r)
-        if not index:
+        if not picks:
             return self._empty()
-        pool = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
-        return self.take(pool, index)
+        views, pos = [], {}
+        for pk in picks:
+            if pk is not None and id(pk[0]) not in pos:
+                pos[id(pk[0])] = len(views)
+                views.append(pk[0])
+        return self._pooled_select(views, [pk and (pos[id(pk[0])], pk[1]) for pk in picks], 0, (1, self.limbs2))
 
     rows_of = assemble = _pick          # the two names multiexp_plan.execute calls
 
@@ -2076,19 +2073,9 @@ class _MatmulBackend(_N2Backend):
         return out_t
 
     def select(self, outs, picks, tile, column_major):
-        torch = self.torch
         if not picks:
             return self._empty()
-        views = [o.view(tile, -1, self.limbs2) for o in outs]
-        first = [0]
-        for v in views:
-            first.append(first[-1] + v.shape[1])
-        if any(pk is None for pk in picks):
-            one = torch.zeros((tile, 1, self.limbs2), dtype=torch.int32, device=self.eng.device)
-            one[:, 0, 0] = 1
-            views.append(one)
-        pool = views[0] if len(views) == 1 else torch.cat(views, dim=1)
-        sel = pool.index_select(1, self._index([first[-1] if pk is None else first[pk[0]] + pk[1] for pk in picks]))
+        sel = self._pooled_select([o.view(tile, -1, self.limbs2) for o in outs], picks, 1, (tile, 1, self.limbs2))
         if column_major:
             sel = sel.permute(1, 0, 2)
         return sel.reshape(-1, self.limbs2)
@@ -2140,23 +2127,14 @@ class _ConvBackend(_MatmulBackend):
         return out_t
 
     def select_conv(self, outs, outs2, picks, images, image_positions, as_columns):
-        torch = self.torch
         if not picks:
             return self._empty()
         if not as_columns and len(outs) == 1 and picks == [(1, 0, r) for r in range(outs[0].shape[0] // (images * image_positions))]:
             return outs[0]                                       # one launch whose rows are the kernels: the result as it stands
         views = [o.view(images, -1, image_positions, self.limbs2) for o in outs]
         views += [o.view(images, image_positions, -1, self.limbs2).permute(0, 2, 1, 3) for o in outs2]
-        first = [0]
-        for v in views:
-            first.append(first[-1] + v.shape[1])
-        if any(pk is None for pk in picks):
-            one = torch.zeros((images, 1, image_positions, self.limbs2), dtype=torch.int32, device=self.eng.device)
-            one[..., 0] = 1
-            views.append(one)
-        pool = views[0] if len(views) == 1 else torch.cat(views, dim=1)
-        at = lambda pk: first[-1] if pk is None else first[(len(outs) if pk[0] == 2 else 0) + pk[1]] + pk[2]
-        sel = pool.index_select(1, self._index([at(pk) for pk in picks]))
+        at = [pk and (pk[1] + (len(outs) if pk[0] == 2 else 0), pk[2]) for pk in picks]
+        sel = self._pooled_select(views, at, 1, (images, 1, image_positions, self.limbs2))
         if as_columns:
             sel = sel.permute(1, 0, 2, 3)
         return sel.reshape(-1, self.limbs2)
@@ -2184,6 +2162,13 @@ def _grid_shape(x) -> Tuple[Tuple[int, int, int, int], List[Any]]:
         if len(img) != c or any(len(ch) != h for ch in img) or any(len(r) != w for ch in img for r in ch):
             raise ValueError("the grids must all have the same shape [C][H][W]")
     return (b, c, h, w), [v for img in x for ch in img for r in ch for v in r]
+
+
+def _table_budget(table_budget: Optional[int]) -> int:
+    """The bytes of tables one stage or tile may take: the planners' default unless the caller names one."""
+    from . import multiexp_plan as mp
+
+    return mp.TABLE_BUDGET_BYTES if table_budget is None else int(table_budget)
 
 
 def _check_modulus(mod: int) -> None:

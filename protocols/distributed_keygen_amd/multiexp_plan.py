@@ -21,12 +21,17 @@ A call is turned into launches of ``mx_multiexp_nsquare_run``, which takes non-n
 
 ``plan_matmul`` / ``execute_matmul`` (at the end) are the batched form, csrc/mx_matmul_n2.hpp: one public W applied to a
 batch of ciphertext vectors, planned once per call whatever the batch.
+
+The rules that the three planners (plan_multiexp, plan_matmul, conv_plan.plan_conv) follow alike have one home each, here:
+``check_weights`` and ``bias_residues`` (the refusals and the bias), ``sign_split`` (which users get an inverted table),
+``split_k`` / ``combine_launches`` (the pieces of a long row and the pass that multiplies them) and ``TwoPassPlan`` (the
+fields of a plan of shared weight rows, and where in its launches every result lies).
 """
 
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
@@ -41,6 +46,33 @@ Term = Tuple[int, int]          # (input index, weight)
 def weight_bound(n: int) -> int:
     """Smallest |weight| that is refused for the modulus N."""
     return 1 << ((n * n).bit_length() + WEIGHT_MARGIN_BITS)
+
+
+def check_weights(ws: Sequence[int], bound: int, what: str, k: int) -> None:
+    """ValueError if a weight of row / kernel `k` is not inside (-bound, bound)."""
+    if ws and (min(ws) <= -bound or max(ws) >= bound):
+        raise ValueError(f"{what} {k}: |weight| >= 2^(bits(N^2) + {WEIGHT_MARGIN_BITS})")
+
+
+def bias_residues(bias: Optional[Sequence[int]], count: int, n: int, what: str) -> Dict[int, int]:
+    """output -> b mod N for the non-zero residues of a bias of `count` values (None: no bias).  ValueError for another
+    length."""
+    if bias is None:
+        return {}
+    if len(bias) != count:
+        raise ValueError(f"{len(bias)} bias values for {count} {what}")
+    residues = ((j, int(b) % n) for j, b in enumerate(bias))
+    return {j: b for j, b in residues if b}
+
+
+def sign_split(pos: Set[int], neg: Set[int]) -> Tuple[List[int], List[int], Dict[int, int]]:
+    """(plain, inverted, slot) for the users (columns, channels) met with a positive and with a negative weight: the
+    plain tables come first, then the inverted ones, each ascending; ``slot[i]`` is the table of user i as it is and
+    ``slot[~i]`` that of its inverse."""
+    plain, inverted = sorted(pos), sorted(neg)
+    slot = {i: c for c, i in enumerate(plain)}
+    slot.update({~i: len(plain) + c for c, i in enumerate(inverted)})
+    return plain, inverted, slot
 
 
 def normalize_rows(weights: Sequence[Any], n_inputs: int, n: int) -> List[List[Term]]:
@@ -60,13 +92,8 @@ def normalize_rows(weights: Sequence[Any], n_inputs: int, n: int) -> List[List[T
             if len(vals) != n_inputs:
                 raise ValueError(f"row {r} has {len(vals)} weights for {n_inputs} inputs")
             items = [(i, int(w)) for i, w in enumerate(vals)]
-        out = []
-        for i, w in items:
-            if w == 0:
-                continue
-            if -bound >= w or w >= bound:
-                raise ValueError(f"row {r}: |weight| >= 2^(bits(N^2) + {WEIGHT_MARGIN_BITS})")
-            out.append((i, w))
+        out = [(i, w) for i, w in items if w]
+        check_weights([w for _, w in out], bound, "row", r)
         rows.append(out)
     return rows
 
@@ -134,6 +161,39 @@ def _bucket_launches(rows: List[List[Term]], ids: List[int]) -> List[Launch]:
     return out
 
 
+def split_k(term_rows: List[List[Any]], chunk: int) -> Tuple[List[List[Any]], List[Tuple[str, int]], List[List[int]]]:
+    """(pass-1 rows, result, split): a row of more than `chunk` terms is cut into pieces, which are pass-1 rows of their
+    own; ``result`` says per row where its value is — ("one", 0) for a row of no terms, ("p1", pass-1 row), or
+    ("p2", r) for the r-th split row, whose pieces are the pass-1 rows ``split[r]``."""
+    p1: List[List[Any]] = []
+    result: List[Tuple[str, int]] = []
+    split: List[List[int]] = []
+    for terms in term_rows:
+        if not terms:
+            result.append(("one", 0))
+            continue
+        ks = []
+        for lo in range(0, len(terms), chunk):
+            ks.append(len(p1))
+            p1.append(terms[lo : lo + chunk])
+        if len(ks) == 1:
+            result.append(("p1", ks[0]))
+        else:
+            result.append(("p2", len(split)))
+            split.append(ks)
+    return p1, result, split
+
+
+def combine_launches(split: List[List[int]]) -> List[Launch]:
+    """The second pass over ``part_rows = [k for ks in split for k in ks]`` as its tables: pass-2 row r multiplies the
+    pieces of split row r with weight 1 (run with window 1: no squarings)."""
+    local, at = [], 0
+    for ks in split:
+        local.append([(at + t, 1) for t in range(len(ks))])
+        at += len(ks)
+    return _bucket_launches(local, list(range(len(split))))
+
+
 def plan_multiexp(rows: List[List[Term]], n_inputs: int, n: int, bias: Optional[Sequence[int]],
                   shape: Callable[[int, int, int, int], Tuple[int, int, int]], table_budget: int = TABLE_BUDGET_BYTES,
                   window: int = 0) -> Plan:
@@ -141,10 +201,7 @@ def plan_multiexp(rows: List[List[Term]], n_inputs: int, n: int, bias: Optional[
     weight_bits) -> (window, chunk_terms, table_bytes_per_input_per_entry)` is the library's choice
     (mx_multiexp_nsquare_shape); `window` > 0 overrides the window of the first pass."""
     n_out = len(rows)
-    if bias is not None and len(bias) != n_out:
-        raise ValueError(f"{len(bias)} bias values for {n_out} outputs")
-    bias_res = {j: int(b) % n for j, b in enumerate(bias)} if bias is not None else {}
-    bias_res = {j: b for j, b in bias_res.items() if b}
+    bias_res = bias_residues(bias, n_out, n, "outputs")
     inverted = sorted({i for row in rows for i, w in row if w < 0})
     # pass-1 terms over SOURCES (global source keys; tables are numbered per stage below)
     src_rows: List[List[Tuple[Tuple[str, int], int]]] = []
@@ -160,25 +217,7 @@ def plan_multiexp(rows: List[List[Term]], n_inputs: int, n: int, bias: Optional[
     if window:
         win = window
     chunk = max(1, chunk)
-    # split-K
-    p1: List[List[Tuple[Tuple[str, int], int]]] = []
-    owner: List[int] = []
-    result: List[Tuple[str, int]] = []
-    pieces: Dict[int, List[int]] = {}
-    for j, terms in enumerate(src_rows):
-        if not terms:
-            result.append(("one", 0))
-            continue
-        ks = []
-        for lo in range(0, len(terms), chunk):
-            ks.append(len(p1))
-            p1.append(terms[lo : lo + chunk])
-            owner.append(j)
-        if len(ks) == 1:
-            result.append(("p1", ks[0]))
-        else:
-            pieces[j] = ks
-            result.append(("p2", -1))
+    p1, result, split = split_k(src_rows, chunk)
     # stages: consecutive pass-1 rows whose distinct sources fit the budget
     per_source = entry_bytes << win
     max_sources = max(1, table_budget // max(1, per_source))
@@ -201,17 +240,8 @@ def plan_multiexp(rows: List[List[Term]], n_inputs: int, n: int, bias: Optional[
         stage.launches = _bucket_launches(local, members)
         stages.append(stage)
     combine_from = len(stages)
-    if pieces:
-        outs = sorted(pieces)
-        stage = Stage(sources=[("part", m) for j in outs for m in pieces[j]], window=1)
-        local, pos = [], 0
-        for j in outs:
-            local.append([(pos + t, 1) for t in range(len(pieces[j]))])
-            pos += len(pieces[j])
-        stage.launches = _bucket_launches(local, list(range(len(outs))))
-        stages.append(stage)
-        row_of = {j: r for r, j in enumerate(outs)}
-        result = [("p2", row_of[j]) if kind == "p2" else (kind, v) for j, (kind, v) in enumerate(result)]
+    if split:
+        stages.append(Stage(sources=[("part", m) for ks in split for m in ks], window=1, launches=combine_launches(split)))
     return Plan(n_out, stages, len(p1), combine_from, result, inverted, bias_res)
 
 
@@ -249,13 +279,10 @@ def plan_dense(block: np.ndarray, n: int, bias: Optional[Sequence[int]],
     plan_multiexp would launch anyway up to a few padding terms: at least 7/8 of every row non-zero, tables within the
     budget.  None otherwise."""
     rows, cols = block.shape
-    if bias is not None and len(bias) != rows:
-        raise ValueError(f"{len(bias)} bias values for {rows} outputs")
     nnz = np.count_nonzero(block, axis=1)
     if int(nnz.min()) * 8 < cols * 7:
-        return None
-    bias_res = {j: int(b) % n for j, b in enumerate(bias)} if bias is not None else {}
-    bias_res = {j: b for j, b in bias_res.items() if b}
+        return None                                               # (plan_multiexp then refuses a bias of the wrong length)
+    bias_res = bias_residues(bias, rows, n, "outputs")
     pos_cols = np.flatnonzero((block > 0).any(axis=0))
     neg_cols = np.flatnonzero((block < 0).any(axis=0))
     bias_rows = sorted(bias_res)
@@ -381,28 +408,42 @@ def execute(plan: Plan, be: Any, inputs: Any) -> Any:
 #   * the bias is one SHARED table per row with a non-zero bias: index -1 - k in the launch arrays, stored once per tile
 #     behind the per-sample tables (the kernel reads it without the sample's offset);
 #   * tiles of `tile_batch` samples under the table budget, the last one ragged;
-#   * split-K: pieces of a row's term list are extra weight rows, and the second pass is itself a shared-weight
-#     product (weights 1, window 1) whose table columns are the split rows' pieces of every sample;
+#   * split-K (split_k): pieces of a row's term list are extra weight rows, and the second pass (combine_launches) is
+#     itself a shared-weight product (weights 1, window 1) whose table columns are the split rows' pieces of every sample;
 #   * buckets of weight rows of similar length, as _bucket_launches makes them.
 #
-# The launch arrays have one leading entry per weight row (times pieces) and are reused by every tile.
+# The launch arrays have one leading entry per weight row (times pieces) and are reused by every tile.  conv_plan.py
+# plans its kernels the same way; what the two plans share is TwoPassPlan.
 
 @dataclass
-class MatmulPlan:
-    n_rows: int
-    n_inputs: int
-    x_cols: List[int]                     # input columns with a table of their own (a positive weight somewhere), ascending
-    inverted: List[int]                   # input columns whose inverses get a table column (a negative weight somewhere)
+class TwoPassPlan:
+    """The launches of shared weight rows (the rows of a matrix, the kernels of a convolution), as split_k and
+    combine_launches make them."""
     bias: Dict[int, int]                  # row -> b mod N (non-zero); shared table k belongs to sorted(bias)[k]
     window: int
-    tile_batch: int
     chunk: int
-    launches: List[Launch]                # pass 1: Launch.rows are pass-1 weight rows; index >= 0: table column
-                                          # (x_cols, then inverted), index < 0: shared table -1 - index
+    launches: List[Launch]                # pass 1: Launch.rows are pass-1 rows; index < 0: shared table -1 - index
     pass1_rows: int
     part_rows: List[int]                  # pass-1 rows that are pieces of split rows = the table columns of pass 2
     combine: List[Launch]                 # pass 2 (empty if no row was split): Launch.rows are pass-2 rows
     result: List[Tuple[str, int]]         # per weight row: ("one", 0) | ("p1", pass-1 row) | ("p2", pass-2 row)
+
+    def picks(self) -> Tuple[List[Tuple[int, int, int]], List[Optional[Tuple[int, int, int]]]]:
+        """(part_picks, picks): where the tables of pass 2 and the results lie, as (pass, launch of that pass, row of
+        the launch); None is a result that is one."""
+        where = {("p1", rid): (1, k, r) for k, launch in enumerate(self.launches) for r, rid in enumerate(launch.rows)}
+        where.update({("p2", rid): (2, k, r) for k, launch in enumerate(self.combine) for r, rid in enumerate(launch.rows)})
+        return [where["p1", m] for m in self.part_rows], [None if kind == "one" else where[kind, v] for kind, v in self.result]
+
+
+@dataclass
+class MatmulPlan(TwoPassPlan):
+    """Launch.index >= 0 in pass 1: a table column (x_cols, then inverted)."""
+    n_rows: int
+    n_inputs: int
+    x_cols: List[int]                     # input columns with a table of their own (a positive weight somewhere), ascending
+    inverted: List[int]                   # input columns whose inverses get a table column (a negative weight somewhere)
+    tile_batch: int
 
     @property
     def n_cols(self) -> int:
@@ -433,22 +474,17 @@ def plan_matmul(weights: Sequence[Any], n_inputs: int, n: int, bias: Optional[Se
     bounds or a bias of the wrong length."""
     weights = weights if isinstance(weights, np.ndarray) else list(weights)
     n_rows = len(weights)
-    if bias is not None and len(bias) != n_rows:
-        raise ValueError(f"{len(bias)} bias values for {n_rows} outputs")
+    bias_res = bias_residues(bias, n_rows, n, "outputs")
     rows = _matmul_rows(weights, n_inputs, n)
-    bias_res = {j: int(b) % n for j, b in enumerate(bias)} if bias is not None else {}
-    bias_res = {j: b for j, b in bias_res.items() if b}
     shared_of = {j: k for k, j in enumerate(sorted(bias_res))}
     pos, neg = set(), set()
     for cols, ws in rows:
         for i, w in zip(cols, ws):
             (pos if w > 0 else neg).add(i)
-    x_cols, inverted = sorted(pos), sorted(neg)
-    x_of = {i: c for c, i in enumerate(x_cols)}
-    inv_of = {i: len(x_cols) + c for c, i in enumerate(inverted)}
+    x_cols, inverted, slot = sign_split(pos, neg)
     term_rows: List[List[Term]] = []
     for j, (cols, ws) in enumerate(rows):
-        terms = [(x_of[i], w) if w > 0 else (inv_of[i], -w) for i, w in zip(cols, ws)]
+        terms = [(slot[i], w) if w > 0 else (slot[~i], -w) for i, w in zip(cols, ws)]
         if j in shared_of:
             terms.append((-1 - shared_of[j], 1))
         term_rows.append(terms)
@@ -456,34 +492,10 @@ def plan_matmul(weights: Sequence[Any], n_inputs: int, n: int, bias: Optional[Se
     max_bits = max((w.bit_length() for r in term_rows for _, w in r), default=0)
     win, tile, chunk = shape(len(x_cols) + len(inverted), n_rows, max_terms, max_bits, int(batch), int(table_budget), int(window))
     tile, chunk = max(1, int(tile)), max(1, int(chunk))
-    # split-K: pieces of a row are weight rows of their own
-    p1: List[List[Term]] = []
-    result: List[Tuple[str, int]] = []
-    split: List[List[int]] = []
-    for terms in term_rows:
-        if not terms:
-            result.append(("one", 0))
-            continue
-        ks = []
-        for lo in range(0, len(terms), chunk):
-            ks.append(len(p1))
-            p1.append(terms[lo : lo + chunk])
-        if len(ks) == 1:
-            result.append(("p1", ks[0]))
-        else:
-            result.append(("p2", len(split)))
-            split.append(ks)
-    launches = _bucket_launches(p1, list(range(len(p1))))
-    part_rows = [k for ks in split for k in ks]
-    combine: List[Launch] = []
-    if split:
-        local, at = [], 0
-        for ks in split:
-            local.append([(at + t, 1) for t in range(len(ks))])
-            at += len(ks)
-        combine = _bucket_launches(local, list(range(len(split))))
-    return MatmulPlan(n_rows, n_inputs, x_cols, inverted, bias_res, int(win), tile, chunk, launches, len(p1), part_rows,
-                      combine, result)
+    p1, result, split = split_k(term_rows, chunk)
+    return MatmulPlan(bias=bias_res, window=int(win), chunk=chunk, launches=_bucket_launches(p1, list(range(len(p1)))),
+                      pass1_rows=len(p1), part_rows=[k for ks in split for k in ks], combine=combine_launches(split),
+                      result=result, n_rows=n_rows, n_inputs=n_inputs, x_cols=x_cols, inverted=inverted, tile_batch=tile)
 
 
 def execute_matmul(plan: MatmulPlan, be: Any, inputs: Any, batch: int) -> Any:
@@ -505,10 +517,8 @@ def execute_matmul(plan: MatmulPlan, be: Any, inputs: Any, batch: int) -> Any:
     x_block = be.columns(inputs, plan.n_inputs, batch, plan.x_cols) if plan.x_cols else None
     inv_block = be.invert(be.columns(inputs, plan.n_inputs, batch, plan.inverted)) if plan.inverted else None
     bias_rows = be.bias_rows([plan.bias[j] for j in shared]) if shared else None
-    where1 = {rid: (k, r) for k, launch in enumerate(plan.launches) for r, rid in enumerate(launch.rows)}
-    where2 = {rid: (len(plan.launches) + k, r) for k, launch in enumerate(plan.combine) for r, rid in enumerate(launch.rows)}
-    part_picks = [where1[m] for m in plan.part_rows]
-    picks = [None if kind == "one" else (where1[v] if kind == "p1" else where2[v]) for kind, v in plan.result]
+    # `select` takes the results of both passes as one list, pass 1 first
+    part_picks, picks = ([pk and (pk[1] + (len(plan.launches) if pk[0] == 2 else 0), pk[2]) for pk in pks] for pks in plan.picks())
     results = []
     for lo in range(0, batch, plan.tile_batch):
         hi = min(batch, lo + plan.tile_batch)

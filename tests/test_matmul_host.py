@@ -406,8 +406,11 @@ def test_abi_refuses_bad_arguments_without_a_launch():
 @pytest.mark.parametrize("rows,terms,splits", [(4, 200000, True), (4, 513, True), (4, 64, False), (100000, 513, False)])
 def test_one_split_k_rule_for_the_linear_map_and_the_matrix_product(rows, terms, splits):
     """For one sample in a tile of one, the matrix product's outputs are the linear map's: both shape queries must cut
-    the terms into the same chunks — few rows with more than 64 terms split, 64 terms or rows that fill the device do not."""
+    the terms into the same chunks — few rows with more than 64 terms split, 64 terms or rows that fill the device do not.
+    The convolution planner is the third: one 1 x `terms` kernel over `rows` positions of one image (a tile of its own
+    under a budget that holds it) is cut at the same chunk, into the pieces and results of the one split-K rule."""
     from protocols.distributed_keygen_amd import _lib
+    from protocols.distributed_keygen_amd import conv_plan as cp
 
     lib = _lib.lib()
     for n_bits in (128, 2048):
@@ -418,3 +421,15 @@ def test_one_split_k_rule_for_the_linear_map_and_the_matrix_product(rows, terms,
         assert tile.value == 1 and (k.value, l.value) == (k2.value, l2.value)
         assert chunk.value == chunk2.value
         assert (64 <= chunk.value < terms) if splits else chunk.value == terms
+
+        def conv_shape(n_tables, n_outputs, n_terms, bits, win):
+            kc, lc, wc, cc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+            assert lib.mx_multiexp_nsquare_shape(n_bits, n_tables, n_outputs, n_terms, bits, 0, win, kc, lc, wc, cc) == 0
+            return wc.value, cc.value, 2 * kc.value * lc.value * 4
+
+        plan = cp.plan_conv([[[[1 << 15] * terms]]], (1, 1, rows, terms), (1 << n_bits) - 1, None, conv_shape, table_budget=1 << 62)
+        assert (plan.tile_images, plan.band_rows, plan.out_w) == (1, rows, 1) and plan.chunk == chunk.value
+        pieces = -(-terms // chunk.value)
+        assert plan.pass1_rows == pieces and all(l.index.shape[1] <= chunk.value for l in plan.launches)
+        assert plan.result == [("p2", 0) if splits else ("p1", 0)]
+        assert plan.part_rows == (list(range(pieces)) if splits else []) and bool(plan.combine) == splits
