@@ -506,6 +506,45 @@ int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, i
  * written; returns their number. */
 int mx_conv_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- encrypted histograms: sums of ciphertexts by a public bin index (ABI 4.4, additions) ------------------------
+ *   H[s] = prod_{i : segment(i) == s} c_i  mod N^2          (an empty segment gives 1)
+ * — weight-1 products only (csrc/mx_hist_n2.hpp): no weights, windows, squarings or inversions, so a ciphertext
+ * without an inverse modulo N^2 is a legal input.  Three steps, all on the pair arithmetic of the plan's modulus:
+ *   convert:    one group of lanes per ciphertext writes its pair-form ROW (*row_bytes = 2 * lanes * limbs_per_lane * 4
+ *               bytes, the layout of one table entry of the multi-exponentiation) once; row n_samples is the value one.
+ *   accumulate: one group of lanes per PIECE: d_index[piece][0 .. chunk) names `chunk` rows, whose product is the
+ *               piece.  Every piece of a launch has the same `chunk`: the caller cuts a segment of len terms into
+ *               ceil(len / chunk) pieces and pads the last one with n_rows, the index of the one row.
+ *   combine:    the same entry point over the piece rows of the level before: with pair_form_out != 0 a run writes its
+ *               n_pieces products in pair form, followed by the one row, i.e. exactly the d_rows (n_rows = n_pieces) of
+ *               the next run.  The last run (pair_form_out == 0) writes canonical residues in [0, N^2), n_pieces rows
+ *               of limbs2 words, NOT fresh ciphertexts.
+ *   d_inputs: [n_samples][limbs2] residues < N^2;  d_rows: [n_rows + 1] pair-form rows (the last one the one row);
+ *   d_index:  [n_pieces][chunk] int32 in [0, n_rows] — device memory the library cannot read before the launch: the
+ *             kernel clamps every index into the row set, so a wrong array gives wrong values, never an access outside
+ *             d_rows;  chunk 1 .. 65536.
+ * The shape query: the geometry, the row size and the library's chunk for n_segments segments of total_terms terms
+ * (enough pieces to fill the device, at least 16 and at most 4096 terms each, and never more than the mean segment length
+ * total_terms / n_segments rounded up — segments are padded to whole pieces; `chunk` > 0 overrides it); n_samples is
+ * informative.  mx_histogram_nsquare_workspace_bytes: the bytes of a row set of n_rows rows and its one
+ * row — the size of d_rows (rows_bytes) for a conversion of n_rows samples and of d_out (out_bytes) for a run with
+ * pair_form_out over n_rows pieces; a run without it needs n_pieces * limbs2 * 4 bytes.
+ * MX_ERR_ARG for a null pointer, a zero or negative size, a chunk outside 1 .. 65536 (0 .. 65536 in the shape query),
+ * a limbs_per_lane other than 9 or 0, or rows too narrow for N^2; MX_ERR_SIZE outside the narrow geometry (groups of up
+ * to 32 lanes) or beyond one grid; MX_ERR_WORKSPACE for rows_bytes / out_bytes below the sizes above.  Everything is
+ * checked before anything is enqueued. */
+int mx_histogram_nsquare_shape(int n_bits, int64_t n_samples, int64_t n_segments, int64_t total_terms, int limbs_per_lane,
+                               int chunk, int* lanes, int* limbs_per_lane_out, int* chunk_out, int64_t* row_bytes);
+int64_t mx_histogram_nsquare_workspace_bytes(int n_bits, int64_t n_rows, int limbs_per_lane);
+int mx_histogram_nsquare_convert(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_samples, int limbs2,
+                                 uint32_t* d_rows, int64_t rows_bytes, int limbs_per_lane, void* stream);
+int mx_histogram_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, const int32_t* d_index,
+                             int64_t n_pieces, int chunk, uint32_t* d_out, int pair_form_out, int limbs2,
+                             int64_t out_bytes, int limbs_per_lane, void* stream);
+/* The kernel instances mx_histogram_nsquare_convert / _run can select: (lanes per element, limbs per lane) pairs, at
+ * most max_entries written; returns their number. */
+int mx_histogram_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 /* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
  *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
  * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of

@@ -107,6 +107,11 @@ SYMBOLS = {
     "mx_conv_nsquare_workspace_bytes": (c_int64, [c_int, c_int64, c_int64, c_int, c_int]),
     "mx_conv_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_conv_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_histogram_nsquare_shape": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_int, *[POINTER(c_int)] * 3, POINTER(c_int64)]),
+    "mx_histogram_nsquare_workspace_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "mx_histogram_nsquare_convert": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "mx_histogram_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "mx_histogram_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_slots_encode": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),

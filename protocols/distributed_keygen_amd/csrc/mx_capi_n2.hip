@@ -8,6 +8,7 @@
 #include "mx_matmul_n2.hpp"
 #include "mx_pack_n2.hpp"
 #include "mx_fixedbase_n2.hpp"
+#include "mx_hist_n2.hpp"
 
 // ---- modexp modulo N^2 through pairs modulo N --------------------------------------------------
 namespace {
@@ -1243,4 +1244,105 @@ extern "C" int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
   weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
   a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
   return mxmm::launch_shared(o.g.K, a, n_rows * pos_blocks, s);
+}
+
+// ---- encrypted histograms: sums of ciphertexts by a public bin index (mx_hist_n2.hpp) --------------------------------
+namespace mxh { int launch_hist(int K, bool convert, const mx::HistN2Args& a, int64_t nblocks, hipStream_t s); }
+namespace {
+constexpr int MX_HIST_MAX_CHUNK = 1 << 16;
+constexpr int MX_HIST_MIN_AUTO_CHUNK = 16, MX_HIST_MAX_AUTO_CHUNK = 4096;
+// Terms per piece.  Enough pieces to give every SIMD of the device its three wavefronts (the kernel's launch bound),
+// but pieces of at least 16 terms (a piece costs a launch slot and a row of output), at most 4096 — and, last, never
+// longer than the mean segment rounded up: every segment is padded to whole pieces, so with many short segments
+// (grouped statistics over many categories) a longer chunk would multiply by the one row more often than by a term.
+int hist_chunk(const Geometry& g, int64_t n_segments, int64_t total_terms) {
+  const int64_t target = (int64_t)device_cus() * 4 * 3 * (64 / g.K);
+  int64_t chunk = (total_terms + target - 1) / target;
+  if (chunk < MX_HIST_MIN_AUTO_CHUNK) chunk = MX_HIST_MIN_AUTO_CHUNK;
+  if (chunk > MX_HIST_MAX_AUTO_CHUNK) chunk = MX_HIST_MAX_AUTO_CHUNK;
+  const int64_t mean = n_segments > 0 ? (total_terms + n_segments - 1) / n_segments : total_terms;
+  if (chunk > mean) chunk = mean;
+  return (int)(chunk < 1 ? 1 : chunk);
+}
+int64_t hist_row_bytes(const Geometry& g) { return (int64_t)2 * g.K * g.L * 4; }
+}  // namespace
+
+extern "C" int mx_histogram_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int mx_histogram_nsquare_shape(int n_bits, int64_t n_samples, int64_t n_segments, int64_t total_terms,
+                                          int limbs_per_lane, int chunk, int* lanes, int* limbs_per_lane_out,
+                                          int* chunk_out, int64_t* row_bytes) {
+  if (!lanes || !limbs_per_lane_out || !chunk_out || !row_bytes) return MX_ERR_ARG;
+  if (n_samples < 0 || n_segments < 0 || total_terms < 0 || chunk < 0 || chunk > MX_HIST_MAX_CHUNK) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  *lanes = g.K;
+  *limbs_per_lane_out = g.L;
+  *chunk_out = chunk > 0 ? chunk : hist_chunk(g, n_segments, total_terms);
+  *row_bytes = hist_row_bytes(g);
+  return MX_OK;
+}
+
+extern "C" int64_t mx_histogram_nsquare_workspace_bytes(int n_bits, int64_t n_rows, int limbs_per_lane) {
+  Geometry g;
+  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) - 1) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  return align256((n_rows + 1) * hist_row_bytes(g));
+}
+
+extern "C" int mx_histogram_nsquare_convert(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_samples, int limbs2,
+                                            uint32_t* d_rows, int64_t rows_bytes, int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_inputs || !d_rows || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_samples <= 0 || n_samples >= ((int64_t)1 << 31) - 1 || limbs2 <= 0) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  const int64_t need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_samples, LIMBS_PER_LANE);
+  if (need < 0) return (int)need;
+  if (need > rows_bytes) return MX_ERR_WORKSPACE;
+  mx::HistN2Args a{};
+  a.inputs = d_inputs;
+  a.rows_out = d_rows;
+  a.consts = o.consts;
+  a.n_samples = n_samples;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = plan->n_bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  return mxh::launch_hist(o.g.K, true, a, o.blocks(n_samples + 1), s);       // one more group: the one row
+}
+
+extern "C" int mx_histogram_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, const int32_t* d_index,
+                                        int64_t n_pieces, int chunk, uint32_t* d_out, int pair_form_out, int limbs2,
+                                        int64_t out_bytes, int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_rows || !d_index || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) - 1 || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
+  if (chunk < 1 || chunk > MX_HIST_MAX_CHUNK) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  const int64_t groups = n_pieces + (pair_form_out ? 1 : 0);                  // one more group: the one row of the next level
+  if (o.blocks(groups) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;             // more wavefronts than one grid holds
+  int64_t need;
+  if (pair_form_out) {
+    need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_pieces, LIMBS_PER_LANE);
+    if (need < 0) return (int)need;
+  } else {
+    need = n_pieces * (int64_t)limbs2 * 4;
+  }
+  if (need > out_bytes) return MX_ERR_WORKSPACE;
+  mx::HistN2Args a{};
+  a.rows = d_rows;
+  a.consts = o.consts;
+  a.index = d_index;
+  a.out = d_out;
+  a.n_rows = n_rows; a.pieces = n_pieces;
+  a.chunk = chunk; a.pair_out = pair_form_out ? 1 : 0;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = plan->n_bits - 1;
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  return mxh::launch_hist(o.g.K, false, a, o.blocks(groups), s);
 }

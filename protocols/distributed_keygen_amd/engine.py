@@ -1137,6 +1137,64 @@ class Engine:
         return [[[vals[((b * o + j) * oh + y) * ow : ((b * o + j) * oh + y + 1) * ow] for y in range(oh)] for j in range(o)]
                 for b in range(shape[0])]
 
+    # ------------------------------------------------------------------ encrypted histograms by a public bin index
+    def histogram_nsquare_shape(self, n: int, n_samples: int, n_segments: int, total_terms: int,
+                                chunk: int = 0) -> Tuple[int, int, int, int]:
+        """(lanes, limbs per lane, terms per piece, row bytes per sample) of mx_histogram_nsquare_shape."""
+        k, l, c, row_bytes = self._query("mx_histogram_nsquare_shape", int(n).bit_length(), int(n_samples), int(n_segments),
+                                         int(total_terms), 0, int(chunk), outs=_INTS[:3] + (_ctypes.c_int64,))
+        return k, l, c, int(row_bytes)
+
+    def histogram_nsquare_t(self, cts_t, bins_t, n_bins: int, n: int, chunk: int = 0, table_budget_bytes: int = 0):
+        """H[f][b] = prod_{i : bins[f][i] == b} cts[i]  mod n^2 on the device (csrc/mx_hist_n2.hpp): the
+        sums of ciphertexts by a PUBLIC bin index, weight-1 products only — no inverse is needed, of any input.
+
+        ``cts_t``: ``[n_samples, limbs2]`` rows of residues below n^2; ``bins_t``: an integer tensor ``[F, n_samples]``
+        with values in [0, n_bins), or -1 for a sample that is not in this feature's histogram (a missing value, a sample
+        outside the node).  Returns ``[F * n_bins, limbs2]`` canonical residues on the current stream (row f * n_bins + b;
+        an empty bin is 1) — not fresh ciphertexts — and never leaves the device.  ``chunk`` > 0 overrides the terms per
+        piece, ``table_budget_bytes`` > 0 the bytes one stage of samples may take for its rows and index arrays
+        (hist_plan.TABLE_BUDGET_BYTES): for tests and probes.  ValueError, before any launch, for bins of another
+        shape or dtype, a bin outside [-1, n_bins) (one reduction on the device), n_bins < 1, or a modulus the pair kernel
+        refuses.  The planning (sorting, pieces, levels, stages, slices) is hist_plan.py."""
+        from . import hist_plan as hp
+
+        n, n_bins, chunk = int(n), int(n_bins), int(chunk)
+        _check_modulus(n)
+        n_samples, limbs2 = cts_t.shape
+        _check_rows_n2(n, limbs2)
+        if not 0 <= chunk <= hp.MAX_CHUNK:
+            raise ValueError(f"chunk must lie in [0, {hp.MAX_CHUNK}]")
+        bins_t = hp.as_bins(bins_t, n_samples, self.device)
+        hp.check_bins(bins_t, n_samples, n_bins)
+        return self._histogram_run_t(cts_t, bins_t, n_bins, n, chunk, int(table_budget_bytes))
+
+    def _histogram_run_t(self, cts_t, bins_t, n_bins: int, n: int, chunk: int = 0, table_budget_bytes: int = 0):
+        """histogram_nsquare_t for a device bin tensor that check_bins has passed (on either side of the upload)."""
+        from . import hist_plan as hp
+
+        with self.torch.cuda.device(self.device):
+            return hp.histogram(_HistogramBackend(self, n, cts_t.shape[1], n.bit_length()), cts_t.contiguous(), bins_t, n_bins,
+                                chunk, table_budget_bytes)
+
+    @_int_args
+    def ciphertext_histogram_batch(self, cts: Sequence[int], bins, n_bins: int, n: int, fixed_base=None) -> List[List[int]]:
+        """[[prod(c_i for i with bins[f][i] == b) mod n^2 for b in range(n_bins)] for f] — the histogram of the
+        ciphertexts by every feature's public bin index (nested lists, a numpy array or a torch tensor ``[F][len(cts)]``
+        with values in [0, n_bins), or -1: not in this feature's histogram).  An empty bin gives 1."""
+        from . import hist_plan as hp
+
+        n2, limbs2 = _nsquare(n)
+        vals = cts if isinstance(cts, (list, tuple)) else list(cts)
+        bins_t = hp.as_bins(bins, len(vals))
+        hp.check_bins(bins_t, len(vals), n_bins)                    # every refusal: before anything is uploaded
+        feats = bins_t.shape[0]
+        if feats == 0:
+            return []
+        x_t = self._upload_ints(vals, limbs2, n2) if vals else self._empty_rows(limbs2)
+        flat = self._download_ints(self._freshened(self._histogram_run_t(x_t, bins_t.to(self.device), n_bins, n), fixed_base))
+        return [flat[f * n_bins : (f + 1) * n_bins] for f in range(feats)]
+
     # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
     def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
         """out[j] = prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 on the device (csrc/mx_pack_n2.hpp):
@@ -2148,6 +2206,51 @@ class _ConvBackend(_MatmulBackend):
         for (m0, m1, y0, y1), rows_t in tiles:
             out[m0:m1, :, y0:y1] = rows_t.view(m1 - m0, n_rows, y1 - y0, out_w, self.limbs2)
         return out.view(-1, self.limbs2)
+
+
+class _HistogramBackend(_N2Backend):
+    """hist_plan.histogram over device rows of one Engine and modulus.  A row set is a tensor [rows + 1 or more,
+    row words]: `rows` pair-form rows, then the one row (and whatever the library's size query rounds up to)."""
+
+    def __init__(self, eng: "Engine", n: int, limbs2: int, n_bits: int) -> None:
+        super().__init__(eng, n, limbs2, n_bits)
+        self.row_bytes = eng.histogram_nsquare_shape(n, 0, 0, 0)[3]
+
+    def chunk(self, n_rows, n_segments, total_terms, chunk):
+        return self.eng.histogram_nsquare_shape(self.n, n_rows, n_segments, total_terms, chunk)[2]
+
+    def _row_set(self, rows):
+        need = _lib.check(self.eng.lib.mx_histogram_nsquare_workspace_bytes(self.n_bits, rows, 0), "mx_histogram_nsquare_workspace_bytes")
+        return self.torch.empty((-(-need // self.row_bytes), self.row_bytes // 4), dtype=self.torch.int32, device=self.eng.device)
+
+    def convert(self, cts_t, lo, hi):
+        rows_t = self._row_set(hi - lo)
+        self.eng._call("mx_histogram_nsquare_convert", self.plan.desc, cts_t[lo:hi].data_ptr(), hi - lo, self.limbs2,
+                       rows_t.data_ptr(), rows_t.numel() * 4, 0, plans=(self.plan,))
+        return rows_t
+
+    def run(self, rows_t, n_rows, index_t, pair_out):
+        pieces, chunk = index_t.shape
+        out_t = self._row_set(pieces) if pair_out else self._empty(pieces)
+        index_t = index_t.contiguous()
+        self.eng._call("mx_histogram_nsquare_run", self.plan.desc, rows_t.data_ptr(), n_rows, index_t.data_ptr(), pieces, chunk,
+                       out_t.data_ptr(), int(bool(pair_out)), self.limbs2, out_t.numel() * 4, 0, plans=(self.plan,))
+        return out_t
+
+    def join(self, row_sets, rows):
+        out_t = self._row_set(len(row_sets) * rows)
+        for t, part in enumerate(row_sets):
+            out_t[t * rows : (t + 1) * rows] = part[:rows]
+        out_t[len(row_sets) * rows] = row_sets[0][rows]
+        return out_t
+
+    def concat(self, results):
+        return results[0] if len(results) == 1 else self.torch.cat(results, dim=0)
+
+    def ones(self, count):
+        one = self.torch.zeros((count, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
+        one[:, 0] = 1
+        return one
 
 
 def _grid_shape(x) -> Tuple[Tuple[int, int, int, int], List[Any]]:

@@ -13,7 +13,10 @@ them to many ciphertexts at once:
     public plaintexts — the kernel's control flow depends on them;
   * ``conv2d`` / ``conv1d``: a public kernel slid over grids (or series) of ciphertexts — FIR filters and moving sums
     over an encrypted time series, a convolution layer over an encrypted image.  Every pixel gets one table however
-    many windows cover it.  Cross-correlation, as ``torch.nn.functional.conv2d``; the kernel is public.
+    many windows cover it.  Cross-correlation, as ``torch.nn.functional.conv2d``; the kernel is public;
+  * ``histogram``: the product of the ciphertexts of every (feature, bin) for a PUBLIC bin index per feature and
+    sample — the per-feature, per-bin sums of encrypted gradients that gradient-boosted trees are built on, grouped
+    encrypted statistics by public categories.  Weight-1 products only: no ciphertext needs an inverse.
 
 Ciphertexts are ints or objects with ``get_value()`` (the reference's ``PaillierCiphertext``); for objects the modulus
 comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` is called once per distinct object.  The
@@ -163,3 +166,19 @@ def conv1d(x: Sequence[Any], weights: Any, n: Optional[int] = None, bias: Option
                bias=bias, stride=(1, int(stride)), padding=(0, int(padding)), dilation=(1, int(dilation)), engine=engine,
                randomizer=randomizer)
     return [[ch[0] for ch in img] for img in y]
+
+
+def histogram(cts: Sequence[Any], bins: Any, n_bins: int, n: Optional[int] = None, engine: Any = None,
+              randomizer: Any = None) -> List[List[int]]:
+    """[[prod(c_i for i with bins[f][i] == b) mod N^2 for b in range(n_bins)] for every feature f] — the sum of the
+    plaintexts of every bin (an empty bin gives 1, an encryption of 0).  ``bins`` (nested lists, a numpy array or a
+    torch tensor ``[F][len(cts)]``) is PUBLIC: values in [0, n_bins), or -1 for a sample that is not in this feature's
+    histogram.  ValueError for anything else, before anything is launched; shape and dtype before a ciphertext is read
+    (the values of ``bins`` are checked once, by the engine)."""
+    from . import hist_plan as hp
+
+    count = len(cts)
+    bins_t = hp.as_bins(bins, count)
+    hp.check_bins(bins_t, count, n_bins, values=False)
+    vals, n = _values(cts, n)
+    return _engine(engine).ciphertext_histogram_batch(vals, bins_t, int(n_bins), n, **_fresh(randomizer, n, bins_t.shape[0] * int(n_bins)))
