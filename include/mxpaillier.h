@@ -545,6 +545,45 @@ int mx_histogram_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows
  * most max_entries written; returns their number. */
 int mx_histogram_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- encrypted prefix sums: running totals over series of ciphertexts (ABI 4.4, additions) -----------------------
+ *   out[index[piece][t]] = carry(piece) * prod_{u <= t} rows[index[piece][u]]  mod N^2      (inclusive)
+ *   out[index[piece][t]] = carry(piece) * prod_{u <  t} rows[index[piece][u]]  mod N^2      (exclusive != 0)
+ * — the accumulate step of the histogram with every intermediate product stored (csrc/mx_scan_n2.hpp): the same
+ * pair-form rows (mx_histogram_nsquare_convert writes them), the same index array, weight-1 products only, so a
+ * ciphertext without an inverse modulo N^2 is a legal input.
+ *   d_rows:   [n_rows + 1] pair-form rows, the last one the one row;
+ *   d_index:  [n_pieces][chunk] int32 in [0, n_rows]: one group of lanes per PIECE walks its `chunk` terms in order.
+ *             The product of a term is stored at the OUTPUT row of the term's own number, so every row should be named
+ *             once (a reverse scan is a reversed index array); a term that names n_rows, the padding of a piece,
+ *             stores nothing.  chunk 1 .. 65536;
+ *   carry:    d_carry_rows, a second row set of n_carry_rows rows and its one row, and d_carry_index[n_pieces] int32 in
+ *             [0, n_carry_rows]: what a piece starts from — the product of everything before it in its segment.  With
+ *             d_carry_rows null every piece starts from one, and n_carry_rows and d_carry_index are ignored;
+ *   d_out:    a row set of n_rows rows followed by the one row (out_bytes at least what
+ *             mx_histogram_nsquare_workspace_bytes gives for n_rows), i.e. the d_rows or d_carry_rows of another run or
+ *             the d_rows of the store.  A row that no term names is left as it was.
+ * mx_scan_nsquare_store writes the n_rows rows of a row set as canonical residues in [0, N^2), n_rows rows of limbs2
+ * words (out_bytes at least n_rows * limbs2 * 4), NOT fresh ciphertexts.  It is a pass of its own because the epilogue
+ * does not fit beside the accumulator inside the scan loop without spilling registers.
+ * Both index arrays are device memory the library cannot read before the launch: the kernel clamps every entry into its
+ * row set, so a wrong array gives wrong values, never an access outside d_rows, d_carry_rows or d_out.  The caller builds
+ * running totals over segments longer than one piece in levels: piece totals by mx_histogram_nsquare_run over the same
+ * index array, their exclusive scan by this entry point one level up, then the scan of the level with those carries.
+ * The geometry, the row size and the library's chunk are those of mx_histogram_nsquare_shape.
+ * MX_ERR_ARG for a null pointer (a null carry set is legal; with one, d_carry_index is required), a zero or negative
+ * size (n_carry_rows may be 0), a chunk outside 1 .. 65536, a limbs_per_lane other than 9 or 0, or rows too narrow for
+ * N^2; MX_ERR_SIZE outside the narrow geometry (groups of up to 32 lanes) or beyond one grid; MX_ERR_WORKSPACE for an
+ * out_bytes below the sizes above.  Everything is checked before anything is enqueued. */
+int mx_scan_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, const int32_t* d_index,
+                        int64_t n_pieces, int chunk, const uint32_t* d_carry_rows, int64_t n_carry_rows,
+                        const int32_t* d_carry_index, int exclusive, uint32_t* d_out, int limbs2, int64_t out_bytes,
+                        int limbs_per_lane, void* stream);
+int mx_scan_nsquare_store(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, uint32_t* d_out, int limbs2,
+                          int64_t out_bytes, int limbs_per_lane, void* stream);
+/* The kernel instances mx_scan_nsquare_run / _store can select: (lanes per element, limbs per lane) pairs, at most
+ * max_entries written; returns their number. */
+int mx_scan_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 /* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
  *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
  * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of

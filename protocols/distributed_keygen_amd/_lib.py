@@ -112,6 +112,9 @@ SYMBOLS = {
     "mx_histogram_nsquare_convert": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p]),
     "mx_histogram_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "mx_histogram_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_scan_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "mx_scan_nsquare_store": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "mx_scan_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_slots_encode": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),

@@ -9,6 +9,7 @@
 #include "mx_pack_n2.hpp"
 #include "mx_fixedbase_n2.hpp"
 #include "mx_hist_n2.hpp"
+#include "mx_scan_n2.hpp"
 
 // ---- modexp modulo N^2 through pairs modulo N --------------------------------------------------
 namespace {
@@ -1345,4 +1346,61 @@ extern "C" int mx_histogram_nsquare_run(const mx_nsquare_plan* plan, const uint3
   hipStream_t s = (hipStream_t)stream;
   MxKernelTimer timer(s);
   return mxh::launch_hist(o.g.K, false, a, o.blocks(groups), s);
+}
+
+// ---- encrypted prefix sums: running totals over series of ciphertexts (mx_scan_n2.hpp) -------------------------------
+namespace mxh { int launch_scan(int K, bool store, const mx::ScanN2Args& a, int64_t nblocks, hipStream_t s); }
+
+extern "C" int mx_scan_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
+  return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
+}
+
+extern "C" int mx_scan_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, const int32_t* d_index,
+                                   int64_t n_pieces, int chunk, const uint32_t* d_carry_rows, int64_t n_carry_rows,
+                                   const int32_t* d_carry_index, int exclusive, uint32_t* d_out, int limbs2, int64_t out_bytes,
+                                   int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_rows || !d_index || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1 || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
+  if (d_carry_rows && (!d_carry_index || n_carry_rows < 0 || n_carry_rows >= ((int64_t)1 << 31) - 1)) return MX_ERR_ARG;
+  if (chunk < 1 || chunk > MX_HIST_MAX_CHUNK) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  if (o.blocks(n_pieces + 1) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;       // more wavefronts than one grid holds
+  const int64_t need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_rows, LIMBS_PER_LANE);
+  if (need < 0) return (int)need;
+  if (need > out_bytes) return MX_ERR_WORKSPACE;
+  mx::ScanN2Args a{};
+  a.rows = d_rows;
+  a.carry_rows = d_carry_rows;
+  a.consts = o.consts;
+  a.index = d_index;
+  a.carry_index = d_carry_rows ? d_carry_index : nullptr;
+  a.out = d_out;
+  a.n_rows = n_rows; a.n_carry_rows = d_carry_rows ? n_carry_rows : 0; a.pieces = n_pieces;
+  a.chunk = chunk; a.exclusive = exclusive ? 1 : 0;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  return mxh::launch_scan(o.g.K, false, a, o.blocks(n_pieces + 1), s);         // one more group: the one row of the output set
+}
+
+extern "C" int mx_scan_nsquare_store(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, uint32_t* d_out,
+                                     int limbs2, int64_t out_bytes, int limbs_per_lane, void* stream) {
+  if (!plan || !plan->d_plan || !d_rows || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1 || limbs2 <= 0) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  NarrowLaunch o;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  if (o.blocks(n_rows) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
+  if (n_rows * (int64_t)limbs2 * 4 > out_bytes) return MX_ERR_WORKSPACE;
+  mx::ScanN2Args a{};
+  a.rows = d_rows;
+  a.consts = o.consts;
+  a.out = d_out;
+  a.n_rows = n_rows;
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
+  hipStream_t s = (hipStream_t)stream;
+  MxKernelTimer timer(s);
+  return mxh::launch_scan(o.g.K, true, a, o.blocks(n_rows), s);
 }

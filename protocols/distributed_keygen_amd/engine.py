@@ -1195,6 +1195,50 @@ class Engine:
         flat = self._download_ints(self._freshened(self._histogram_run_t(x_t, bins_t.to(self.device), n_bins, n), fixed_base))
         return [flat[f * n_bins : (f + 1) * n_bins] for f in range(feats)]
 
+    # ------------------------------------------------------------------ encrypted prefix sums over series of ciphertexts
+    def cumsum_nsquare_t(self, cts_t, lengths, n: int, exclusive: bool = False, reverse: bool = False, chunk: int = 0,
+                         table_budget_bytes: int = 0):
+        """out[j] = the product modulo n^2 of cts[first .. j] over the segment that holds j, on the device
+        (csrc/mx_scan_n2.hpp): the running totals of series of ciphertexts laid one behind the other.
+
+        ``cts_t``: ``[count, limbs2]`` rows of residues below n^2; ``lengths``: the PUBLIC lengths of the series (a
+        sequence, a numpy array or an integer tensor; they sum to count, 0 is legal; None: one series).  ``exclusive``
+        leaves cts[j] itself out (the first output of a series is 1), ``reverse`` runs every series from its end.
+        Returns ``[count, limbs2]`` canonical residues on the current stream — not fresh ciphertexts — and never leaves
+        the device.  Weight-1 products only: no input needs an inverse, and a 0 makes every later prefix of its series
+        0.  ``chunk`` > 0 overrides the rows per piece, ``table_budget_bytes`` > 0 the bytes one stage of elements may
+        take (scan_plan.TABLE_BUDGET_BYTES): for tests and probes.  ValueError, before any launch, for lengths that are
+        negative, not integers, not one-dimensional or do not sum to count, or a modulus the pair kernel refuses.  The
+        planning (pieces, levels, carries, stages) is scan_plan.py."""
+        from . import scan_plan as sp
+
+        n, chunk = int(n), int(chunk)
+        _check_modulus(n)
+        count, limbs2 = cts_t.shape
+        _check_rows_n2(n, limbs2)
+        if not 0 <= chunk <= sp.MAX_CHUNK:
+            raise ValueError(f"chunk must lie in [0, {sp.MAX_CHUNK}]")
+        lengths_t = sp.as_lengths(lengths, count, self.device)
+        with self.torch.cuda.device(self.device):
+            return sp.cumsum(_ScanBackend(self, n, limbs2, n.bit_length()), cts_t.contiguous(), lengths_t, bool(exclusive),
+                             bool(reverse), chunk, int(table_budget_bytes))
+
+    @_int_args
+    def ciphertext_cumsum_batch(self, cts: Sequence[int], lengths, n: int, exclusive: bool = False, reverse: bool = False,
+                                fixed_base=None) -> List[int]:
+        """[prod(cts[first .. j]) mod n^2 for every j] over the series of the given public lengths laid one behind the
+        other (None: one series) — cumsum_nsquare_t, ints to ints."""
+        from . import scan_plan as sp
+
+        n2, limbs2 = _nsquare(n)
+        vals = cts if isinstance(cts, (list, tuple)) else list(cts)
+        lengths_t = sp.as_lengths(lengths, len(vals))               # every refusal: before anything is uploaded
+        _check_modulus(n)
+        if not vals:
+            return []
+        x_t = self._upload_ints(vals, limbs2, n2)
+        return self._download_ints(self._freshened(self.cumsum_nsquare_t(x_t, lengths_t, n, exclusive, reverse), fixed_base))
+
     # ------------------------------------------------------------------ packing: many small plaintexts per ciphertext
     def pack_nsquare_t(self, cts_t, n: int, slot_bits: int, slots: int):
         """out[j] = prod_{i < slots} cts[j * slots + i]^(2^(slot_bits * i)) mod n^2 on the device (csrc/mx_pack_n2.hpp):
@@ -2251,6 +2295,36 @@ class _HistogramBackend(_N2Backend):
         one = self.torch.zeros((count, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
         one[:, 0] = 1
         return one
+
+
+class _ScanBackend(_HistogramBackend):
+    """scan_plan.cumsum over device rows: the histogram's row sets, conversion and accumulate run, and the two entries
+    of csrc/mx_scan_n2.hpp."""
+
+    def scan(self, rows_t, n_rows, index_t, carry, exclusive):
+        pieces, chunk = index_t.shape
+        out_t = self._row_set(n_rows)
+        index_t = index_t.contiguous()
+        carry_t, n_carry, carry_index_t = carry if carry is not None else (None, 0, None)
+        if carry_index_t is not None:
+            carry_index_t = carry_index_t.contiguous()
+        self.eng._call("mx_scan_nsquare_run", self.plan.desc, rows_t.data_ptr(), n_rows, index_t.data_ptr(), pieces, chunk,
+                       carry_t.data_ptr() if carry is not None else None, n_carry,
+                       carry_index_t.data_ptr() if carry is not None else None, int(bool(exclusive)), out_t.data_ptr(),
+                       self.limbs2, out_t.numel() * 4, 0, plans=(self.plan,))
+        return out_t
+
+    def store(self, rows_t, n_rows):
+        out_t = self._empty(n_rows)
+        self.eng._call("mx_scan_nsquare_store", self.plan.desc, rows_t.data_ptr(), n_rows, out_t.data_ptr(), self.limbs2,
+                       out_t.numel() * 4, 0, plans=(self.plan,))
+        return out_t
+
+    def pick(self, rows_t, n_rows, row):
+        out_t = self._row_set(1)
+        out_t[0] = rows_t[row]
+        out_t[1] = rows_t[n_rows]
+        return out_t
 
 
 def _grid_shape(x) -> Tuple[Tuple[int, int, int, int], List[Any]]:

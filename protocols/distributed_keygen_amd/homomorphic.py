@@ -16,11 +16,16 @@ them to many ciphertexts at once:
     many windows cover it.  Cross-correlation, as ``torch.nn.functional.conv2d``; the kernel is public;
   * ``histogram``: the product of the ciphertexts of every (feature, bin) for a PUBLIC bin index per feature and
     sample — the per-feature, per-bin sums of encrypted gradients that gradient-boosted trees are built on, grouped
-    encrypted statistics by public categories.  Weight-1 products only: no ciphertext needs an inverse.
+    encrypted statistics by public categories.  Weight-1 products only: no ciphertext needs an inverse;
+  * ``cumsum``: the running totals along series of ciphertexts, c_0 c_1 ... c_j for every j — the left and right
+    gradient sums of every split threshold straight from ``histogram`` output, cumulative distributions and running
+    totals over an encrypted time series, summed-area rows.  One product per element and level, exclusive and
+    reverse forms, no inverse of any input.
 
 Ciphertexts are ints or objects with ``get_value()`` (the reference's ``PaillierCiphertext``); for objects the modulus
 comes from ``.scheme.public_key.n`` unless ``n`` is given, and ``get_value()`` is called once per distinct object.  The
-results are ints: canonical residues in [0, N^2), NOT fresh ciphertexts — re-randomise them
+results are ints: canonical residues in [0, N^2), NOT fresh ciphertexts (every prefix of ``cumsum`` included) —
+re-randomise them
 (``Engine.randomize_batch``) before they leave the party.  ``engine`` is injected for tests; the default is the
 process-wide HIP engine.
 
@@ -182,3 +187,30 @@ def histogram(cts: Sequence[Any], bins: Any, n_bins: int, n: Optional[int] = Non
     hp.check_bins(bins_t, count, n_bins, values=False)
     vals, n = _values(cts, n)
     return _engine(engine).ciphertext_histogram_batch(vals, bins_t, int(n_bins), n, **_fresh(randomizer, n, bins_t.shape[0] * int(n_bins)))
+
+
+def cumsum(series: Sequence[Any], n: Optional[int] = None, exclusive: bool = False, reverse: bool = False, engine: Any = None,
+           randomizer: Any = None) -> List[Any]:
+    """The running totals of a series of ciphertexts: ``out[j] = c_0 * ... * c_j mod N^2``, the sum of the plaintexts up
+    to j.  ``series`` is a flat sequence of ciphertexts (a flat list comes back) or a sequence of sequences, every one a
+    series of its own (lists of the same ragged shape come back; an empty series gives an empty list).
+    ``exclusive=True`` leaves c_j out: ``out[0] = 1``, an encryption of 0.  ``reverse=True`` scans from the end:
+    ``out[j] = c_j * ... * c_last``.  No input needs an inverse; a 0 makes every later prefix of its series 0."""
+    series = list(series)
+    nested = [isinstance(s, (list, tuple)) for s in series]
+    if any(nested) and not all(nested):
+        raise ValueError("series must be ciphertexts or sequences of ciphertexts, not both")
+    is_nested = bool(series) and all(nested)
+    lengths = [len(s) for s in series] if is_nested else [len(series)]
+    flat = [c for s in series for c in s] if is_nested else series
+    if not flat:
+        return [[] for _ in series] if is_nested else []
+    vals, n = _values(flat, n)
+    out = _engine(engine).ciphertext_cumsum_batch(vals, lengths, n, exclusive=bool(exclusive), reverse=bool(reverse),
+                                                  **_fresh(randomizer, n, len(vals)))
+    if not is_nested:
+        return out
+    ends = [0]
+    for k in lengths:
+        ends.append(ends[-1] + k)
+    return [out[a:b] for a, b in zip(ends, ends[1:])]
