@@ -204,6 +204,15 @@ int mx_combine_prepare(mx_combine_plan* plan, const uint32_t* h_n, const uint32_
                        int limbs2, void* d_plan, int64_t plan_bytes, void* stream);
 int mx_combine_run(const mx_combine_plan* plan, const uint32_t* d_partials, uint32_t* d_out, int out_stride,
                    uint8_t* d_status, int n_partials, int64_t batch, void* stream);
+/* The plan's constant rows as the host builds them, without a device: 3 + MX_COMBINE_NP_MAX rows of limbs2 words, zero
+ * padded — N | N^2 | theta_inv * R1 mod N | R2^k mod N^2 for k = 1 .. MX_COMBINE_NP_MAX — with R1 = 2^(w l b1) and
+ * R2 = 2^(w l b2) the Montgomery radices of N and N^2 in the lane geometry of N^2 (mx_geometry of bits(N^2): lanes,
+ * l, w, b2; b1 = ceil((bits(N) + 4) / (w l))).  A run with n_partials <= MX_COMBINE_NP_MAX multiplies the raw rows
+ * and then by R2^n_partials: n_partials products modulo N^2; with more partials it converts every row (2 n_partials).
+ *   MX_ERR_WORKSPACE if rows_words is less than that many words; the other errors are those of the prepare call. */
+#define MX_COMBINE_NP_MAX 8
+int mx_combine_constants(const uint32_t* h_n, const uint32_t* h_theta_inv, int limbs, int limbs2, uint32_t* h_rows,
+                         int64_t rows_words);
 
 /* ---- biprimality verdict ---------------------------------------------------------------
  * d_pass[g*n_slots + k] = 1 iff  v_1 == +-prod_{i>=2} v_i (mod N_g) for test slot k, where

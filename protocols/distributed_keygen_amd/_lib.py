@@ -64,6 +64,7 @@ SYMBOLS = {
     "mx_combine_plan_bytes": (c_int64, [c_int, c_int]),
     "mx_combine_prepare": (c_int, [POINTER(CombinePlan), c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_combine_run": (c_int, [POINTER(CombinePlan), c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
+    "mx_combine_constants": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64]),
     "mx_biprime_verdict_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "mx_jacobi_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "mx_jacobi_dev_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),

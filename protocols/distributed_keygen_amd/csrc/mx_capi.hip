@@ -589,40 +589,78 @@ int launch_combine_k(const mx::CombineArgs& a, hipStream_t s) {
 }
 }  // namespace
 
-inline int64_t combine_plan_words(int limbs2) { return (int64_t)5 * limbs2; }
+// constant rows of a key, each limbs2 words:
+//   N | N^2 | theta_inv * R1 mod N | R2^k mod N^2 for k = 1 .. MX_COMBINE_NP_MAX
+// R1 = 2^(W*L*nblk1) and R2 = 2^(W*L*nblk2) are the Montgomery radices of N and N^2 in the lane geometry of N^2.
+// Row R2^np folds the np partials' way out of the Montgomery domain into one product (mx_combine.hpp); R2^2 is the
+// conversion constant of the route for more partials than the plan has rows for.
+constexpr int COMBINE_ROW_THETA = 2, COMBINE_ROW_RPOW = 3;
+inline int64_t combine_plan_words(int limbs2) { return (int64_t)(COMBINE_ROW_RPOW + MX_COMBINE_NP_MAX) * limbs2; }
 
 extern "C" int64_t mx_combine_plan_bytes(int limbs, int limbs2) {
   if (limbs <= 0 || limbs2 < limbs) return MX_ERR_ARG;
   return align256(combine_plan_words(limbs2) * 4);
 }
 
-// constants of a key, each limbs2 words: N | N^2 | R1 mod N | R2 mod N^2 | theta_inv
-extern "C" int mx_combine_prepare(mx_combine_plan* plan, const uint32_t* h_n, const uint32_t* h_theta_inv, int limbs,
-                                  int limbs2, void* d_plan, int64_t plan_bytes, void* stream) {
-  if (!plan || !h_n || !h_theta_inv || !d_plan) return MX_ERR_ARG;
+namespace {
+// the rows above into c (host), the bit lengths of N and N^2 into bits1 / bits2
+int combine_constants(std::vector<u32>& c, int& bits1, int& bits2, const uint32_t* h_n, const uint32_t* h_theta_inv, int limbs,
+                      int limbs2) {
+  if (!h_n || !h_theta_inv) return MX_ERR_ARG;
   if (limbs <= 0 || limbs2 < limbs) return MX_ERR_ARG;
   if (!(h_n[0] & 1u)) return MX_ERR_MODULUS;
-  int bits1 = bit_length(h_n, limbs);
+  bits1 = bit_length(h_n, limbs);
   if (bits1 < 2) return MX_ERR_MODULUS;
   std::vector<u32> n2((size_t)2 * limbs);
   mul_words(n2.data(), h_n, limbs, h_n, limbs);
-  int bits2 = bit_length(n2.data(), 2 * limbs);
+  bits2 = bit_length(n2.data(), 2 * limbs);
   if ((bits2 + 31) / 32 > limbs2) return MX_ERR_ARG;   // rows too narrow for N^2
   Geometry g2;
   if (!choose_geometry(bits2, g2)) return MX_ERR_SIZE;
   Geometry g1 = g2;
   g1.nblk = (bits1 + 4 + g1.W * g1.L - 1) / (g1.W * g1.L);
-  if (mx_combine_plan_bytes(limbs, limbs2) > plan_bytes) return MX_ERR_WORKSPACE;
-  std::vector<u32> c((size_t)5 * limbs2, 0u);
+  c.assign((size_t)combine_plan_words(limbs2), 0u);
   std::memcpy(&c[0], h_n, (size_t)limbs * 4);
   std::memcpy(&c[limbs2], n2.data(), (size_t)std::min(limbs2, 2 * limbs) * 4);
-  two_pow_mod(&c[(size_t)2 * limbs2], h_n, limbs, g1.W * g1.L * g1.nblk);
   {
-    std::vector<u32> n2p(limbs2, 0u);
-    std::memcpy(n2p.data(), n2.data(), (size_t)std::min(limbs2, 2 * limbs) * 4);
-    two_pow_mod(&c[(size_t)3 * limbs2], n2p.data(), limbs2, g2.W * g2.L * g2.nblk);
+    // theta_inv * R1 mod N: theta_inv reduced (a residue is expected, anything else is taken modulo N), then doubled
+    std::vector<u32> q(limbs), t(limbs + 1, 0u);
+    divmod_words(q.data(), t.data(), h_theta_inv, limbs, h_n, limbs);
+    shl_mod(t, h_n, limbs, g1.W * g1.L * g1.nblk);
+    std::memcpy(&c[(size_t)COMBINE_ROW_THETA * limbs2], t.data(), (size_t)limbs * 4);
   }
-  std::memcpy(&c[(size_t)4 * limbs2], h_theta_inv, (size_t)limbs * 4);
+  {
+    const u32* n2p = &c[limbs2];
+    const int m = g2.W * g2.L * g2.nblk;
+    std::vector<u32> x(limbs2 + 1, 0u);
+    two_pow_mod(x.data(), n2p, limbs2, m);
+    for (int k = 1; k <= MX_COMBINE_NP_MAX; ++k) {
+      if (k > 1) shl_mod(x, n2p, limbs2, m);
+      std::memcpy(&c[(size_t)(COMBINE_ROW_RPOW + k - 1) * limbs2], x.data(), (size_t)limbs2 * 4);
+    }
+  }
+  return MX_OK;
+}
+}  // namespace
+
+extern "C" int mx_combine_constants(const uint32_t* h_n, const uint32_t* h_theta_inv, int limbs, int limbs2, uint32_t* h_rows,
+                                    int64_t rows_words) {
+  if (!h_rows) return MX_ERR_ARG;
+  std::vector<u32> c;
+  int bits1 = 0, bits2 = 0;
+  MX_TRY(combine_constants(c, bits1, bits2, h_n, h_theta_inv, limbs, limbs2));
+  if ((int64_t)c.size() > rows_words) return MX_ERR_WORKSPACE;
+  std::memcpy(h_rows, c.data(), c.size() * 4);
+  return MX_OK;
+}
+
+extern "C" int mx_combine_prepare(mx_combine_plan* plan, const uint32_t* h_n, const uint32_t* h_theta_inv, int limbs,
+                                  int limbs2, void* d_plan, int64_t plan_bytes, void* stream) {
+  if (!plan || !d_plan) return MX_ERR_ARG;
+  std::vector<u32> c;
+  int bits1 = 0, bits2 = 0;
+  MX_TRY(combine_constants(c, bits1, bits2, h_n, h_theta_inv, limbs, limbs2));
+  if (mx_combine_plan_bytes(limbs, limbs2) > plan_bytes) return MX_ERR_WORKSPACE;
   MX_TRY(upload_words(d_plan, c.data(), c.size(), (hipStream_t)stream));
   plan->d_plan = d_plan;
   plan->plan_bytes = plan_bytes;
@@ -646,8 +684,10 @@ extern "C" int mx_combine_run(const mx_combine_plan* plan, const uint32_t* d_par
   const u32* w = (const u32*)plan->d_plan;
   mx::CombineArgs a;
   a.partials = d_partials; a.out = d_out; a.status = d_status;
-  a.n = w; a.n2 = w + limbs2; a.rmodn1 = w + 2 * (size_t)limbs2; a.rmodn2 = w + 3 * (size_t)limbs2;
-  a.theta_inv = w + 4 * (size_t)limbs2;
+  a.n = w; a.n2 = w + limbs2; a.theta_r1 = w + COMBINE_ROW_THETA * (size_t)limbs2;
+  // the plan's row for this many partials, or the two-conversion route through R2^2
+  a.direct = n_partials <= MX_COMBINE_NP_MAX;
+  a.rpow = w + (COMBINE_ROW_RPOW + (a.direct ? n_partials - 1 : 1)) * (size_t)limbs2;
   a.batch = batch; a.limbs = plan->limbs; a.limbs2 = limbs2; a.np = n_partials; a.out_stride = out_stride;
   a.nblk1 = g1.nblk; a.nblk2 = g2.nblk;
   hipStream_t s = (hipStream_t)stream;

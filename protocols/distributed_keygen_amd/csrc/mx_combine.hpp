@@ -8,6 +8,13 @@
 // are recorded: REDC gives r = (y + Q N) / R with Q = -y N^-1 mod R; N | y  <=>  r in {0, N},
 // and then y / N = (R - Q) mod R.  So the whole function is Montgomery products in the lane
 // geometry of N^2 — no long division anywhere.
+//
+// Everything that depends on the key only comes from the host with the plan (mx_combine_prepare): nothing is derived
+// from the modulus here but n0inv.  The product of the np partials takes np Montgomery products modulo N^2: the raw
+// rows are multiplied as they are — np - 1 products, each of which divides by R, leave x * R^-(np-1) — and one product
+// by the plan's constant R^np mod N^2 gives x itself, out of the Montgomery domain (no conversion of the rows into
+// it, no product by one to leave it).  The plan holds that constant for np <= MX_COMBINE_NP_MAX; for more partials the
+// kernel takes the general route with R^2 (every row converted, a last product by one: 2 np products).
 #pragma once
 #include "mx_mont.hpp"
 #include "mx_prio.hpp"
@@ -21,9 +28,9 @@ struct CombineArgs {
   unsigned char* status; // [batch] device, or null
   const u32* n;          // [limbs2] device, N zero padded
   const u32* n2;         // [limbs2] device, N^2
-  const u32* rmodn1;     // [limbs2] device, R1 mod N
-  const u32* rmodn2;     // [limbs2] device, R2 mod N^2
-  const u32* theta_inv;  // [limbs2] device
+  const u32* theta_r1;   // [limbs2] device, theta_inv * R1 mod N (theta_inv in the Montgomery domain of N)
+  const u32* rpow;       // [limbs2] device: direct ? R2^np mod N^2 : R2^2 mod N^2
+  int direct;            // the plan has the constant for this np (see above)
   long long batch;
   int limbs, limbs2, np, out_stride;
   int nblk1, nblk2;
@@ -46,20 +53,32 @@ __global__ void __launch_bounds__(64) combine_kernel(CombineArgs A) {
   M2.init(lds, A.nblk2);
   M2.load(M2.n, A.n2, A.limbs2);
   M2.setup_modulus();
-  u32 one2[L], r2sq[L];
-  M2.load(one2, A.rmodn2, A.limbs2);
-  M2.compute_r2(r2sq, one2);
+  const bool direct = A.direct != 0;
+  u32 cst[L];
+  M2.load(cst, A.rpow, A.limbs2);
   u32 x[L];
   M2.load(x, A.partials + elem * A.limbs2, A.limbs2);
-  M2.mul(x, x, r2sq);
+  if (!direct) M2.mul(x, x, cst);
   for (int i = 1; i < A.np; ++i) {
     u32 y[L];
     M2.load(y, A.partials + ((long long)i * A.batch + elem) * A.limbs2, A.limbs2);
-    M2.mul(y, y, r2sq);
+    if (!direct) M2.mul(y, y, cst);
     M2.mul(x, x, y);
   }
+  // the last product, by R^np (direct) or by one, leaves the residue itself, lazy (< 2 N^2): into [0, N^2)
   u32 xc[L];
-  M2.from_mont_canonical(xc, x);                 // x in [0, N^2)
+  {
+    u32 last[L];
+    M2.set_small(last, 1);
+#pragma unroll
+    for (int j = 0; j < L; ++j) last[j] = direct ? cst[j] : last[j];
+    M2.mul(x, x, last);
+    u64 t[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) t[j] = x[j];
+    M2.normalize_full(xc, t);
+    M2.cond_sub(xc);
+  }
   const bool x_zero = M2.is_zero(xc);
 
   // ---- y = x - 1 (for x >= 1): add 2^(W*S) - 1, drop the carry
@@ -104,11 +123,8 @@ __global__ void __launch_bounds__(64) combine_kernel(CombineArgs A) {
   }
 
   // ---- m = u * theta_inv mod N
-  u32 one1[L], r1sq[L], th[L], m[L];
-  M1.load(one1, A.rmodn1, A.limbs2);
-  M1.compute_r2(r1sq, one1);
-  M1.load(th, A.theta_inv, A.limbs2);
-  M1.mul(th, th, r1sq);                          // theta_inv * R1
+  u32 th[L], m[L];
+  M1.load(th, A.theta_r1, A.limbs2);             // theta_inv * R1 mod N
   M1.mul(m, u, th);                              // u * theta_inv (lazy)
   {
     u64 t[L];

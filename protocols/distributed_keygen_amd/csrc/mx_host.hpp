@@ -108,12 +108,9 @@ inline bool geq(const std::vector<u32>& a, const u32* b, int limbs) {   // a has
   return true;
 }
 
-// out[0..limbs) = 2^m mod n  (n odd, >= 3, m >= bit_length(n) - 1)
-inline void two_pow_mod(u32* out, const u32* n, int limbs, int m) {
-  int bits = bit_length(n, limbs);
-  std::vector<u32> x(limbs + 1, 0u);
-  x[(bits - 1) / 32] = 1u << ((bits - 1) % 32);   // 2^(bits-1) < n
-  for (int e = bits - 1; e < m; ++e) {
+// x <- x * 2^m mod n  (x has limbs+1 words and is below n; m doublings with a conditional subtraction each)
+inline void shl_mod(std::vector<u32>& x, const u32* n, int limbs, int m) {
+  for (int e = 0; e < m; ++e) {
     u32 carry = 0;
     for (int i = 0; i <= limbs; ++i) {
       u32 v = x[i];
@@ -130,6 +127,14 @@ inline void two_pow_mod(u32* out, const u32* n, int limbs, int m) {
       x[limbs] -= (u32)borrow;
     }
   }
+}
+
+// out[0..limbs) = 2^m mod n  (n odd, >= 3, m >= bit_length(n) - 1)
+inline void two_pow_mod(u32* out, const u32* n, int limbs, int m) {
+  int bits = bit_length(n, limbs);
+  std::vector<u32> x(limbs + 1, 0u);
+  x[(bits - 1) / 32] = 1u << ((bits - 1) % 32);   // 2^(bits-1) < n
+  shl_mod(x, n, limbs, m - (bits - 1));
   for (int i = 0; i < limbs; ++i) out[i] = x[i];
 }
 

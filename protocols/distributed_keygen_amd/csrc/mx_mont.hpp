@@ -252,7 +252,8 @@ struct Mont {
   static constexpr int slot_weight() {
     if (!SQUARE) return 1;
     constexpr int d = (J - I + L) % L;
-    if (d == 0 || (L % 2 == 0 && d == L / 2)) return 1;
+    if (d == 0) return 1;
+    if (L % 2 == 0 && d == L / 2) return (2 * I < L) ? 2 : 0;      // the half-way pairs: once, from the lower step
     return (2 * d < L) ? 2 : 0;
   }
 
@@ -400,11 +401,24 @@ struct Mont {
   //
   // F_SQUARE (b is a): the product part uses the symmetry a_u a_v = a_v a_u without moving any data.
   // At the unrolled step i of a block (multiplier limb u with u mod L == i) a lane only multiplies
-  // its slots j whose cyclic distance d = (j - i) mod L is <= L/2: with weight 2 for 0 < d < L/2 and
-  // weight 1 for d == 0 (and d == L/2 when L is even).  For u != v exactly one of the two orders
-  // has distance < L/2 (weight 2), or both have distance 0 or L/2 (weight 1 + 1); u == v is met once
-  // with weight 1 — so every term of a^2 gets its coefficient, the selection is the same in every
-  // lane (compile-time register indices), and floor(L/2)+1 instead of L product MACs are issued.
+  // its slots j whose cyclic distance d = (j - i) mod L is <= L/2: with weight 2 for 0 < d < L/2,
+  // weight 1 for d == 0 and, when L is even, weight 2 for d == L/2 in the steps i < L/2 only.
+  // Why every term a_u a_v gets its coefficient: the term with multiplier limb u = blk*L + i and
+  // multiplicand limb v = p*L + j (slot j of lane p) is met a second time, as a_v a_u, at step j of
+  // block p in slot i of lane blk — the same two limbs with i and j exchanged, whatever the blocks and
+  // lanes are, so the distance there is (i - j) mod L = L - d (0 for d == 0).
+  //   0 < d < L/2:  this order has weight 2, the other one (distance > L/2) weight 0;
+  //   d == L/2:     both orders have distance L/2, and j = i +- L/2 puts exactly one of the two steps
+  //                 i, j below L/2: that order has weight 2, the other weight 0;
+  //   d == 0, (blk, i) != (p, j):  both orders have weight 1;
+  //   u == v:       the two orders are one and the same meeting, weight 1.
+  // (A meeting that no step runs — block p >= nblk — is a zero term: a < R has no limb there; blk < nblk <= K.)
+  // Both meetings happen no later than step u + v, the step that reads the column of the term for its
+  // quotient digit (u, v <= u + v, and a meeting AT that step is in slot 0 of lane 0, which is multiplied
+  // in front of the digit), so the digits, and with them F_RECORD_Q, are those of the full product.
+  // The selection is the same in every lane (compile-time register indices).  Product MACs per step
+  // instead of L: (L + 1) / 2 for odd L; L/2 + 1 in the steps i < L/2 and L/2 in the others for even L
+  // (before, the d == L/2 pairs were met from both sides at weight 1: L/2 + 1 in every step).
   template <int F>
   // a and c are not const: their registers are passed through an empty asm once per block (see
   // below); values are unchanged.
