@@ -689,6 +689,35 @@ int mx_fixedbase_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entr
 int mx_chacha20_rows(const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, uint32_t* d_out, int64_t count,
                      int row_words, int bits, void* stream);
 
+/* ---- additive shares of the prime candidates and their Shamir sharings (ABI 4.4, additions) ------------------------
+ * The step of a key-generation round in front of the candidate moduli (`_generate_pq`, DK:718-853), for all candidates
+ * of the round at once (csrc/mx_share.hpp; tools/share_model.py is the model).
+ *
+ * mx_share_candidates: d_out[e] = 2^(L-1) + (d_random[e] << 2) + m4 with L = prime_length and m4 = 3 when first_party
+ *   is non-zero, else 0 (DK:874-875).  d_random is [count][ceil((L - 3) / 32)], rows of L - 3 random bits (zero above
+ *   them: what mx_chacha20_rows writes for bits = L - 3); d_out is [count][row_words], zero above bit L - 1.  One launch,
+ *   no workspace; count = 0 returns MX_OK without a launch.  MX_ERR_ARG for a null pointer, count < 0, prime_length < 8
+ *   or row_words < 1; MX_ERR_SIZE for prime_length > 32 * row_words.
+ *
+ * mx_shamir_share: d_out[j][e] = s[e] + sum_{k=1..degree} (D[k][e] mod P) * x_j^k mod P, canonical residues —
+ *   `ShamirVariable.share()` (UT:253-260) of every candidate: the values at the public points x_j = h_points[j] of a
+ *   polynomial of degree `degree` whose constant term is the secret and whose coefficients are the draws reduced modulo
+ *   P = h_mod.  d_secrets is [batch][limbs] with every row below P, or NULL for a sharing of zero; d_draws is
+ *   [degree][batch][cw] with cw = ceil((bits(P) + 64) / 32): draws of bits(P) + 64 bits (a coefficient is then uniform
+ *   on [0, P) up to a bias below 2^-64); d_out is [n_points][batch][limbs], the layout mx_lincomb_mod reads.  One
+ *   modulus per launch; control flow and addresses depend on the sizes alone.
+ *   MX_ERR_ARG for a null pointer (other than d_secrets), limbs, batch or degree < 1, n_points <= degree, or points that
+ *   are not distinct values in [1, 2^16); MX_ERR_MODULUS for an even P; MX_ERR_SIZE for a P beyond the engine's widest
+ *   modulus or degree > MX_SHARE_MAX_DEGREE (the coefficients of an element are kept in LDS); MX_ERR_WORKSPACE below
+ *   mx_share_workspace_bytes.  A refused call launches nothing. */
+#define MX_SHARE_MAX_DEGREE 24
+int mx_share_candidates(const uint32_t* d_random, uint32_t* d_out, int64_t count, int prime_length, int first_party,
+                        int row_words, void* stream);
+int64_t mx_share_workspace_bytes(int limbs, int n_points);
+int mx_shamir_share(const uint32_t* d_secrets, const uint32_t* d_draws, const uint32_t* h_points, int n_points, int degree,
+                    uint32_t* d_out, const uint32_t* h_mod, int limbs, int64_t batch, void* d_workspace,
+                    int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,9 @@ SYMBOLS = {
     "mx_fixedbase_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "mx_fixedbase_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_chacha20_rows": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "mx_share_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "mx_share_workspace_bytes": (c_int64, [c_int, c_int]),
+    "mx_shamir_share": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 

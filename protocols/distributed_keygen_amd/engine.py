@@ -1720,6 +1720,111 @@ class Engine:
         x = np.stack([_limbs.pack_reduced(col, limbs, prime) for col in columns])
         return self._download_ints(self.shamir_lincomb_t(self.to_device(x), coeffs, prime))
 
+    # ------------------------------------------------------------------ additive shares and their sharings (DK:718-853)
+    def prime_candidates_t(self, count: int, prime_length: int, first_party: bool, rng=None, random_t=None,
+                           row_words: Optional[int] = None):
+        """``[count, row_words]`` int32 rows of the additive shares 2^(L-1) + (r << 2) + m4 of a round's prime candidates
+        (`_generate_prime_candidate`, DK:874-875): L = `prime_length`, m4 = 3 for the first party and 0 for the others,
+        r a row of L - 3 random bits — ``random_t`` (``[count, ceil((L - 3) / 32)]``, zero above bit L - 3) or ONE call
+        ``rng.rows_t(self, count, L - 3)`` of a device_rng.DeviceRng.  ``row_words`` defaults to ceil(L / 32); wider rows
+        are zero-filled.  ValueError — nothing launched, no call number taken — for prime_length < 8, rows narrower than
+        L bits, neither or both of `rng` and `random_t`, or a `random_t` of another shape."""
+        from . import shamir as _shamir
+
+        count, prime_length = int(count), int(prime_length)
+        in_words, row_words = _shamir.check_candidate_args(count, prime_length, row_words)
+        if (rng is None) == (random_t is None):
+            raise ValueError("exactly one of rng and random_t expected")
+        if random_t is not None and (tuple(random_t.shape) != (count, in_words) or not random_t.is_contiguous()):
+            raise ValueError(f"random_t must be contiguous rows of the shape ({count}, {in_words})")
+        if random_t is None:
+            random_t = rng.rows_t(self, count, prime_length - 3)
+        out_t = self._empty_rows(row_words, count)
+        if count:
+            self._call("mx_share_candidates", random_t.data_ptr(), out_t.data_ptr(), count, prime_length, 1 if first_party else 0, row_words)
+        return out_t
+
+    def shamir_share_t(self, secrets_t, prime: int, degree: int, points: Sequence[int], batch: Optional[int] = None, rng=None,
+                       draws_t=None, out_t=None):
+        """Shamir sharings of a batch of secrets modulo `prime` (`ShamirVariable.share()`, utils.py:253-260, for every
+        candidate of a round): ``out[j][e] = secrets[e] + sum_{k=1..degree} a_k[e] * points[j]^k mod prime`` as int32 rows
+        ``[len(points), batch, limbs]`` of canonical residues — party j's rows contiguous, the layout shamir_lincomb_t
+        reads.  ``secrets_t``: ``[batch, limbs]`` rows below the prime, or None with ``batch=`` for a sharing of zero.
+
+        The coefficients are a_k[e] = D mod prime for draws D of bits(prime) + 64 bits: ``draws_t`` ``[degree, batch,
+        cw]`` with cw = ceil((bits(prime) + 64) / 32), or ONE call ``rng.rows_t(self, degree * batch, bits(prime) + 64,
+        cw)`` whose row (k - 1) * batch + e is the draw of coefficient k of element e.
+
+        ValueError — nothing launched, no call number taken — for degree < 1 (or above MX_SHARE_MAX_DEGREE), points that
+        are not distinct integers in [1, 2^16), fewer than degree + 1 points, an even prime, neither or both of `rng`
+        and `draws_t`, or rows of another shape."""
+        from . import shamir as _shamir
+
+        prime, degree = int(prime), int(degree)
+        points = _shamir.check_share_args(prime, degree, points)
+        if secrets_t is not None:
+            if secrets_t.dim() != 2 or (batch is not None and int(batch) != secrets_t.shape[0]):
+                raise ValueError("secrets_t must be [batch, limbs]")
+            batch, limbs = secrets_t.shape
+        else:
+            if batch is None:
+                raise ValueError("a sharing of zero needs batch=")
+            batch, limbs = int(batch), (_limbs.limbs_for(prime) if out_t is None else out_t.shape[-1])
+        if batch < 0 or limbs < _limbs.limbs_for(prime):
+            raise ValueError("rows narrower than the prime")
+        bits = prime.bit_length() + 64
+        cw = (bits + 31) // 32
+        if (rng is None) == (draws_t is None):
+            raise ValueError("exactly one of rng and draws_t expected")
+        if draws_t is not None and tuple(draws_t.shape) != (degree, batch, cw):
+            raise ValueError(f"draws_t must have the shape ({degree}, {batch}, {cw})")
+        if out_t is not None and tuple(out_t.shape) != (len(points), batch, limbs):
+            raise ValueError(f"out_t must have the shape ({len(points)}, {batch}, {limbs})")
+        if any(x is not None and not x.is_contiguous() for x in (secrets_t, draws_t, out_t)):
+            raise ValueError("contiguous rows expected")
+        if draws_t is None:
+            draws_t = rng.rows_t(self, degree * batch, bits, cw)
+        if out_t is None:
+            out_t = self.torch.empty((len(points), batch, limbs), dtype=self.torch.int32, device=self.device)
+        if batch:
+            h_mod = _limbs.pack_one(prime, limbs)
+            h_points = np.asarray(points, dtype="<u4")
+            self._call("mx_shamir_share", secrets_t.data_ptr() if secrets_t is not None else None, draws_t.data_ptr(),
+                       h_points.ctypes.data, len(points), degree, out_t.data_ptr(), h_mod.ctypes.data, limbs, batch,
+                       workspace=("mx_share_workspace_bytes", limbs, len(points)))
+        return out_t
+
+    def prime_candidates_batch(self, count: int, prime_length: int, first_party: bool, rng) -> List[int]:
+        """prime_candidates_t with the candidates as Python ints."""
+        return self._download_ints(self.prime_candidates_t(count, prime_length, first_party, rng=rng))
+
+    def shamir_share_batch(self, secrets: Optional[Sequence[int]], prime: int, degree: int, points: Sequence[int], rng,
+                           batch: Optional[int] = None) -> Dict[int, List[int]]:
+        """shamir_share_t over Python ints: ``{point: [share of every secret]}``; ``secrets=None`` with ``batch=`` shares
+        zero.  ValueError for a secret outside [0, prime)."""
+        from . import shamir as _shamir
+
+        prime = int(prime)
+        points = _shamir.check_share_args(prime, int(degree), points)
+        limbs = _limbs.limbs_for(prime)
+        secrets_t = None
+        if secrets is not None:
+            secrets = [int(s) for s in secrets]
+            if any(not 0 <= s < prime for s in secrets):
+                raise ValueError("secrets must lie in [0, prime)")
+            if batch is not None and int(batch) != len(secrets):
+                raise ValueError("batch differs from the number of secrets")
+            batch = len(secrets)
+            if batch:
+                secrets_t = self.to_device(_limbs.pack(secrets, limbs))
+        if batch is None:
+            raise ValueError("a sharing of zero needs batch=")
+        if not batch:
+            return {x: [] for x in points}
+        out_t = self.shamir_share_t(secrets_t, prime, degree, points, batch=batch, rng=rng)
+        vals = self._download_ints(out_t.view(len(points) * batch, limbs))
+        return {x: vals[j * batch : (j + 1) * batch] for j, x in enumerate(points)}
+
     @_int_args
     def shamir_reconstruct_sieve_batch(self, columns: Sequence[Sequence[int]], coeffs: Sequence[int], prime: int,
                                        primes: Sequence[int], keep_rows: bool = False):

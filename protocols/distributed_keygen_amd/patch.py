@@ -21,6 +21,10 @@ script uses at scripts/bench_batch_size.py:94-110):
       -> same rounds and messages, with the sieve, the v-calculation and the verdict of a round
          each executed as ONE launch over the round's candidates
 
+  DistributedPaillier._generate_pq                       :718-853      (only with ``share_rng=``)
+      -> same variables, labels, exchange and sums, with the additive shares of the round's candidates and their three
+         Shamir sharings drawn and computed on the device (shamir.generate_pq_batch) instead of one candidate at a time
+
 so ``DistributedPaillier.from_security_parameter()``, ``.decrypt()`` and ``.decrypt_sequence()``
 work unmodified.  ``uninstall()`` restores the originals.  The control plane (pools, message ids,
 share containers) is the reference's and is not re-implemented here.
@@ -98,8 +102,14 @@ def _gpu_key(key: Any, engine: Any) -> GpuPaillierSharedKey:
 
 
 def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = True, leaf: bool = False,
-            linger: float = 0.0, hw_queues: Optional[int] = None) -> None:
-    """``hw_queues``: the engine keeps several launches in flight (chunks of long sequences, the batches of co-located
+            linger: float = 0.0, hw_queues: Optional[int] = None, share_rng: Any = None) -> None:
+    """``share_rng``: a ``device_rng.DeviceRng``, off by default.  With one, ``_generate_pq`` draws this party's additive
+    shares of the prime candidates and the coefficients of their Shamir sharings on the device and computes all shares
+    of a round in ten launches (shamir.py's module docstring: what is drawn, the bias below 2^-64 of a coefficient, and
+    that everything is a deterministic expansion of the generator's key — read it and ``device_rng`` before use).
+    Without one the reference's own ``secrets``-based `_generate_pq` stays in place.
+
+    ``hw_queues``: the engine keeps several launches in flight (chunks of long sequences, the batches of co-located
     parties), which needs more HIP hardware queues than the runtime's default of 4; they can only be chosen before
     the process first touches the GPU.  Default (None): when install() is left to create the engine itself
     (``engine=None`` — the engine is then made on first use, so the runtime is not up yet) it asks for 16 through
@@ -131,6 +141,14 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
     PSK = psk_mod.PaillierSharedKey
     DP = dk_mod.DistributedPaillier
     check_limits(engine)
+    if share_rng is not None:
+        # the share containers and their exchange are the reference's own (utils.py:175-298, 507-553): looked up before
+        # anything is rebound, so that a package without them is refused with nothing installed
+        try:
+            utils_mod = importlib.import_module(package + ".utils")
+            utils_mod.ShamirVariable, utils_mod.exchange_shares
+        except (ImportError, AttributeError) as exc:
+            raise ValueError(f"share_rng needs {package}.utils with ShamirVariable and exchange_shares") from exc
     if hw_queues is None:
         hw_queues = 16 if engine is None else 0
     if hw_queues:
@@ -390,6 +408,50 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
                 biprime_rejected += 1
 
     setattr(DP, "compute_modulus", classmethod(compute_modulus))
+
+    # ------------------------------------------------------------------ _generate_pq, shared on the device (opt-in)
+    if share_rng is None:
+        return
+    ShamirVariable, exchange_shares = utils_mod.ShamirVariable, utils_mod.exchange_shares
+    _save(DP, "_generate_pq")
+
+    async def _generate_pq(cls: Any, pool, index, prime_length, party_indices, shamir_scheme_t, shamir_scheme_2t, session_id,
+                           batch_size: int = 1, msg_id: str = ""):
+        """DK:718-853 with the same variables and labels, the same ``exchange_shares`` call and message id (:836-837),
+        the same sums (:839-847) and return value.  The two candidate comprehensions (:790-808) and the three
+        ``.share(index)`` calls (:829-831) are one ``shamir.generate_pq_batch``; its results are stored the way those
+        calls leave them: the plaintexts, the share of every party, and ``_index`` (utils.py:259-260)."""
+        kinds = (("p", shamir_scheme_t), ("q", shamir_scheme_t), ("zero", shamir_scheme_2t))
+
+        def batched(name: str, owner: int, scheme: Any) -> Any:
+            return Batched(ShamirVariable(shamir=scheme, label=f"{name}_{owner}", owner=owner), batch_size=batch_size)
+
+        t = shamir_scheme_t.polynomial_degree
+        if shamir_scheme_2t.polynomial_degree != 2 * t or shamir_scheme_2t.modulus != shamir_scheme_t.modulus:
+            raise ValueError("the two Shamir schemes of a key generation share a modulus and have the degrees t and 2t")
+        p_additive, q_additive, shares = shamir.generate_pq_batch(
+            index, prime_length, shamir_scheme_t.modulus, shamir_scheme_t.number_of_parties, t, batch_size, share_rng, engine)
+        plaintexts = {"p": p_additive, "q": q_additive, "zero": [0] * batch_size}
+        group = []
+        for name, scheme in kinds:
+            own = batched(name, index, scheme)
+            own.set_plaintexts(plaintexts[name])
+            for j, column in shares[name].items():
+                own.set_share(j, column)
+            for variable in own.variables:
+                variable._index = index
+            group.append(own)
+        others = [j for j in party_indices.values() if j != index]
+        group.extend(batched(name, j, scheme) for name, scheme in kinds for j in others)
+        await exchange_shares(group, index, pool, party_indices,
+                              msg_id=msg_id or f"distributed_keygen_session#{session_id}_shamir")
+        sums = []
+        for name, _ in kinds:
+            members = [v for v in group if v.label.startswith(name + "_")]
+            sums.append(sum(members[1:], members[0]))
+        return sums[0], sums[1], sums[2], p_additive, q_additive
+
+    setattr(DP, "_generate_pq", classmethod(_generate_pq))
 
 
 def uninstall() -> None:
