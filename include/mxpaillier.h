@@ -141,7 +141,12 @@ typedef struct mx_nsquare_plan {
   int32_t ntape;          /* tape words */
   int32_t n_sqr;          /* pair squarings one exponentiation executes */
   int32_t n_mul;          /* pair multiplications one exponentiation executes */
-  int32_t geometries;     /* bit mask of the limbs_per_lane values with a kernel instance for this modulus: 1 = 9, 2 = 18, 4 = 3 */
+  int32_t geometries;     /* bits 0-7: mask of the limbs_per_lane values with a kernel instance for this modulus: 1 = 9, 2 = 18,
+                           * 4 = 3; 8 = the plan holds the constants of the five-wavefront latency form.  Bits 8-15: the pivot
+                           * (multiplier limbs on the L wavefronts, at most 192) those constants were built with;
+                           * mx_powmod_nsquare_run takes the form's pivot from here, not from MX_KNOB_BI_PIVOT, and refuses a
+                           * value that does not fit the geometry with MX_ERR_ARG.  0 there (a plan written by a library
+                           * before this field carried it): the pivot of the knob at the time of the run. */
   int32_t n_slot_reads;   /* pair slots (2 * limbs_per_lane words per lane) one exponentiation reads from ... */
   int32_t n_slot_writes;  /* ... and writes to the workspace: the kernel's HBM traffic model */
 } mx_nsquare_plan;

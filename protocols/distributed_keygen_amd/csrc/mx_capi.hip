@@ -1,4 +1,5 @@
 // extern "C" entry points of libmxpaillier.so (declared in include/mxpaillier.h).
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_powmod.hpp"
 #include "mx_sieve.hpp"
@@ -127,50 +128,34 @@ int launch_powmod_kl(const mx::PowmodArgs& a, int64_t nblocks, hipStream_t s) {
   using M_t = mx::Mont<K, L, LIMB_BITS, true>;
   size_t lds = (size_t)(64 / K) * M_t::LDS_WORDS * 4;
   MxKernelTimer timer(s);
-  if (a.nops > 0)
-    hipLaunchKernelGGL((mx::powmod_kernel<K, L, LIMB_BITS, true>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  else
-    hipLaunchKernelGGL((mx::powmod_kernel<K, L, LIMB_BITS, false>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return a.nops > 0 ? mx_launch(mx::powmod_kernel<K, L, LIMB_BITS, true>, nblocks, 64, lds, s, a)
+                    : mx_launch(mx::powmod_kernel<K, L, LIMB_BITS, false>, nblocks, 64, lds, s, a);
 }
 
-template <int K>
-int launch_powmod_k(const mx::PowmodArgs& a, int64_t nblocks, int limbs_per_lane, hipStream_t s) {
-  if (limbs_per_lane == LIMBS_PER_LANE_LAT) return mxl::launch_powmod_lat(K, a, nblocks, s);
-  if (limbs_per_lane == LIMBS_PER_LANE_WIDE) {
-    // the largest supported modulus (MAX_MOD_BITS) needs 32 wide lanes: no <64, 18> instance
-    if constexpr (K <= 32) return launch_powmod_kl<K, LIMBS_PER_LANE_WIDE>(a, nblocks, s);
-    return MX_ERR_SIZE;
-  }
-  return launch_powmod_kl<K, LIMBS_PER_LANE>(a, nblocks, s);
+// A kernel of the one-wavefront Montgomery form over `count` groups of K lanes: 64 / K groups per wavefront, each with
+// its LDS words.
+template <int K, int L, class Kern, class Args>
+int launch_groups(Kern kern, int64_t count, hipStream_t s, const Args& a) {
+  using M_t = mx::Mont<K, L, LIMB_BITS, true>;
+  const int gpw = 64 / K;
+  return mx_launch(kern, (count + gpw - 1) / gpw, 64, (size_t)gpw * M_t::LDS_WORDS * 4, s, a);
 }
 
 // R mod N of every group, on the device (mx_setup.hpp); always the narrow-L instance of the
 // geometry's K would give a different R, so the instance follows the geometry of the consumer
-template <int K, int L>
-int launch_rmodn_kl(const mx::RmodnArgs& a, hipStream_t s) {
-  using M_t = mx::Mont<K, L, LIMB_BITS, true>;
-  int gpw = 64 / K;
-  int64_t nblocks = (a.groups + gpw - 1) / gpw;
-  hipLaunchKernelGGL((mx::rmodn_kernel<K, L, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64),
-                     (size_t)gpw * M_t::LDS_WORDS * 4, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-
 int launch_rmodn(const Geometry& g, const u32* d_mods, u32* d_rmodn, int limbs, int64_t groups, hipStream_t s) {
   mx::RmodnArgs a;
   a.mods = d_mods; a.rmodn = d_rmodn; a.groups = groups; a.limbs = limbs; a.nblk = g.nblk;
   if (g.L == LIMBS_PER_LANE_LAT) return mxl::launch_rmodn_lat(g.K, a, s);
   const bool wide = g.L == LIMBS_PER_LANE_WIDE;
-  switch (g.K) {
-#define MX_CASE(KK) case KK: return wide ? launch_rmodn_kl<KK, LIMBS_PER_LANE_WIDE>(a, s) : launch_rmodn_kl<KK, LIMBS_PER_LANE>(a, s);
-    MX_CASE(1) MX_CASE(2) MX_CASE(4) MX_CASE(8) MX_CASE(16) MX_CASE(32)
-#undef MX_CASE
-    case 64: return wide ? MX_ERR_SIZE : launch_rmodn_kl<64, LIMBS_PER_LANE>(a, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(g.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    if (wide) {                                   // no <64, 18> instance
+      if constexpr (K <= 32) return launch_groups<K, LIMBS_PER_LANE_WIDE>(mx::rmodn_kernel<K, LIMBS_PER_LANE_WIDE, LIMB_BITS>, groups, s, a);
+      return MX_ERR_SIZE;
+    }
+    return launch_groups<K, LIMBS_PER_LANE>(mx::rmodn_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, groups, s, a);
+  });
 }
 
 // Common tail of the modexp entry points: moduli and exponents are device-resident
@@ -218,16 +203,16 @@ int powmod_launch(const uint32_t* d_bases, uint32_t* d_out, const u32* d_mods, c
       a.win = w;
     }
   }
-  switch (p.geo.K) {
-    case 1: return launch_powmod_k<1>(a, p.nblocks, p.geo.L, s);
-    case 2: return launch_powmod_k<2>(a, p.nblocks, p.geo.L, s);
-    case 4: return launch_powmod_k<4>(a, p.nblocks, p.geo.L, s);
-    case 8: return launch_powmod_k<8>(a, p.nblocks, p.geo.L, s);
-    case 16: return launch_powmod_k<16>(a, p.nblocks, p.geo.L, s);
-    case 32: return launch_powmod_k<32>(a, p.nblocks, p.geo.L, s);
-    case 64: return launch_powmod_k<64>(a, p.nblocks, p.geo.L, s);
-  }
-  return MX_ERR_SIZE;
+  if (p.geo.L == LIMBS_PER_LANE_LAT) return mxl::launch_powmod_lat(p.geo.K, a, p.nblocks, s);
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(p.geo.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    if (p.geo.L == LIMBS_PER_LANE_WIDE) {
+      // the largest supported modulus (MAX_MOD_BITS) needs 32 wide lanes: no <64, 18> instance
+      if constexpr (K <= 32) return launch_powmod_kl<K, LIMBS_PER_LANE_WIDE>(a, p.nblocks, s);
+      return MX_ERR_SIZE;
+    }
+    return launch_powmod_kl<K, LIMBS_PER_LANE>(a, p.nblocks, s);
+  });
 }
 
 // host operands: validate, upload, launch
@@ -464,9 +449,7 @@ int mx_powmod_launch_form(int mod_bits, int64_t batch, int64_t groups, int limbs
 
 int mx_spin(int64_t microseconds, void* stream) {
   if (microseconds < 0 || microseconds > 1000000) return MX_ERR_ARG;
-  hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(spin_kernel, 1, 64, 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull);
 }
 
 int mx_stream_create_cu_slice(int slice, int n_slices, int reserved, void** stream_out) {
@@ -566,29 +549,13 @@ extern "C" int mx_sieve(const uint32_t* d_cands, uint8_t* d_out, const uint32_t*
   // limbs a 64-bit column takes between two folds (mx_sieve.hpp): 2^32 ((chunk + 1) top + 1) < 2^64
   const int64_t chunk = (int64_t)(0xFFFFFFFEull / top) - 1;          // >= 1 for top < 2^31
   a.chunk = (int)std::min<int64_t>(chunk, limbs);
-  hipLaunchKernelGGL(mx::sieve_setup_kernel, dim3((unsigned)(p.np_pad / 64)), dim3(64), 0, s, a);
-  MX_HIP(hipGetLastError());
+  MX_TRY(mx_launch(mx::sieve_setup_kernel, p.np_pad / 64, 64, 0, s, a));
   int64_t nblocks = (batch + mx::SIEVE_C - 1) / mx::SIEVE_C;
   size_t lds = (size_t)limbs * mx::SIEVE_C * 4;
-  hipLaunchKernelGGL(mx::sieve_kernel, dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::sieve_kernel, nblocks, 64, lds, s, a);
 }
 
 // ---- share recombination -------------------------------------------------------------------
-namespace {
-template <int K>
-int launch_combine_k(const mx::CombineArgs& a, hipStream_t s) {
-  using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-  int gpw = 64 / K;
-  int64_t nblocks = (a.batch + gpw - 1) / gpw;
-  size_t lds = (size_t)gpw * M_t::LDS_WORDS * 4;
-  hipLaunchKernelGGL((mx::combine_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-}  // namespace
-
 // constant rows of a key, each limbs2 words:
 //   N | N^2 | theta_inv * R1 mod N | R2^k mod N^2 for k = 1 .. MX_COMBINE_NP_MAX
 // R1 = 2^(W*L*nblk1) and R2 = 2^(W*L*nblk2) are the Montgomery radices of N and N^2 in the lane geometry of N^2.
@@ -691,16 +658,10 @@ extern "C" int mx_combine_run(const mx_combine_plan* plan, const uint32_t* d_par
   a.batch = batch; a.limbs = plan->limbs; a.limbs2 = limbs2; a.np = n_partials; a.out_stride = out_stride;
   a.nblk1 = g1.nblk; a.nblk2 = g2.nblk;
   hipStream_t s = (hipStream_t)stream;
-  switch (g2.K) {
-    case 1: return launch_combine_k<1>(a, s);
-    case 2: return launch_combine_k<2>(a, s);
-    case 4: return launch_combine_k<4>(a, s);
-    case 8: return launch_combine_k<8>(a, s);
-    case 16: return launch_combine_k<16>(a, s);
-    case 32: return launch_combine_k<32>(a, s);
-    case 64: return launch_combine_k<64>(a, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(g2.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return launch_groups<K, LIMBS_PER_LANE>(mx::combine_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, a.batch, s, a);
+  });
 }
 
 // ---- one-shot form: prepare into the workspace, run
@@ -720,20 +681,6 @@ extern "C" int mx_combine(const uint32_t* d_partials, uint32_t* d_out, uint8_t* 
 }
 
 // ---- biprimality verdict -------------------------------------------------------------------
-namespace {
-template <int K>
-int launch_verdict_k(const mx::VerdictArgs& a, hipStream_t s) {
-  using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-  int gpw = 64 / K;
-  int64_t total = a.groups * a.n_slots;
-  int64_t nblocks = (total + gpw - 1) / gpw;
-  size_t lds = (size_t)gpw * M_t::LDS_WORDS * 4;
-  hipLaunchKernelGGL((mx::verdict_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-}  // namespace
-
 extern "C" int64_t mx_verdict_workspace_bytes(int limbs, int n_parties, int64_t groups, int64_t n_slots) {
   if (limbs <= 0 || n_parties <= 0 || groups <= 0 || n_slots <= 0) return MX_ERR_ARG;
   return 2 * align256((int64_t)groups * limbs * 4);
@@ -753,16 +700,10 @@ extern "C" int mx_biprime_verdict_dev(const uint32_t* d_v, uint8_t* d_pass, cons
   mx::VerdictArgs a;
   a.v = d_v; a.pass = d_pass; a.mods = d_mods; a.rmodn = (const u32*)d_ws;
   a.groups = groups; a.n_slots = n_slots; a.limbs = limbs; a.n_parties = n_parties; a.nblk = geo.nblk;
-  switch (geo.K) {
-    case 1: return launch_verdict_k<1>(a, s);
-    case 2: return launch_verdict_k<2>(a, s);
-    case 4: return launch_verdict_k<4>(a, s);
-    case 8: return launch_verdict_k<8>(a, s);
-    case 16: return launch_verdict_k<16>(a, s);
-    case 32: return launch_verdict_k<32>(a, s);
-    case 64: return launch_verdict_k<64>(a, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(geo.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return launch_groups<K, LIMBS_PER_LANE>(mx::verdict_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, a.groups * a.n_slots, s, a);
+  });
 }
 
 extern "C" int mx_biprime_verdict(const uint32_t* d_v, uint8_t* d_pass, const uint32_t* h_mods, int limbs,
@@ -792,17 +733,14 @@ template <int NL>
 int launch_jacobi(const mx::JacobiArgs& a, hipStream_t s) {
   int64_t nblocks = a.skip ? (a.count / a.per_group) * ((a.per_group + 63) / 64) : (a.count + 63) / 64;
   // dynamic LDS: 0 except for the 257-word instance, whose top limbs live there (mx_jacobi.hpp)
-  hipLaunchKernelGGL((mx::jacobi_kernel<NL>), dim3((unsigned)nblocks), dim3(64), mx::jacobi_lds_bytes<NL>(), s, a);
-  MX_HIP(hipGetLastError());
+  MX_TRY(mx_launch(mx::jacobi_kernel<NL>, nblocks, 64, mx::jacobi_lds_bytes<NL>(), s, a));
   // safety net for symbols the divstep kernel did not finish within its batch bound (mx_jacobi.hpp)
   constexpr size_t lds_fb = mx::jacobi_lds_bytes<NL, true>();
   if constexpr (lds_fb > 64 * 1024) {
     static bool allowed[MX_MAX_DEVICES] = {};
     MX_HIP(mx_allow_dynamic_lds(reinterpret_cast<const void*>(&mx::jacobi_fallback_kernel<NL>), (int)lds_fb, allowed));
   }
-  hipLaunchKernelGGL((mx::jacobi_fallback_kernel<NL>), dim3((unsigned)nblocks), dim3(64), lds_fb, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::jacobi_fallback_kernel<NL>, nblocks, 64, lds_fb, s, a);
 }
 }  // namespace
 
@@ -854,19 +792,6 @@ extern "C" int mx_jacobi(const uint32_t* d_values, int8_t* d_out, const uint32_t
 }
 
 // ---- modular multiplication ------------------------------------------------------------------
-namespace {
-template <int K>
-int launch_mulmod_k(const mx::MulmodArgs& a, hipStream_t s) {
-  using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-  int gpw = 64 / K;
-  int64_t nblocks = (a.batch + gpw - 1) / gpw;
-  size_t lds = (size_t)gpw * M_t::LDS_WORDS * 4;
-  hipLaunchKernelGGL((mx::mulmod_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-}  // namespace
-
 extern "C" int64_t mx_mulmod_workspace_bytes(int limbs) {
   if (limbs <= 0) return MX_ERR_ARG;
   return align256((int64_t)2 * limbs * 4);
@@ -889,34 +814,14 @@ extern "C" int mx_mulmod_shared(const uint32_t* d_a, const uint32_t* d_b, uint32
   mx::MulmodArgs a;
   a.a = d_a; a.b = d_b; a.out = d_out; a.mod = (const u32*)d_ws; a.rmodn = (const u32*)d_ws + limbs;
   a.batch = batch; a.limbs = limbs; a.nblk = geo.nblk;
-  switch (geo.K) {
-    case 1: return launch_mulmod_k<1>(a, s);
-    case 2: return launch_mulmod_k<2>(a, s);
-    case 4: return launch_mulmod_k<4>(a, s);
-    case 8: return launch_mulmod_k<8>(a, s);
-    case 16: return launch_mulmod_k<16>(a, s);
-    case 32: return launch_mulmod_k<32>(a, s);
-    case 64: return launch_mulmod_k<64>(a, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(geo.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return launch_groups<K, LIMBS_PER_LANE>(mx::mulmod_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, a.batch, s, a);
+  });
 }
 
 // ---- Shamir-field arithmetic of the candidate moduli ----------------------------------------------
 namespace {
-template <int K>
-int launch_field_k(const mx::FieldArgs& a, bool lincomb, hipStream_t s) {
-  using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-  int gpw = 64 / K;
-  int64_t nblocks = (a.batch + gpw - 1) / gpw;
-  size_t lds = (size_t)gpw * M_t::LDS_WORDS * 4;
-  if (lincomb)
-    hipLaunchKernelGGL((mx::lincomb_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  else
-    hipLaunchKernelGGL((mx::fma_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-
 int field_launch(mx::FieldArgs& a, bool lincomb, const uint32_t* h_mod, const uint32_t* h_extra, int extra_words,
                  int limbs, void* d_ws, int64_t ws_bytes, hipStream_t s) {
   if (!(h_mod[0] & 1u)) return MX_ERR_MODULUS;
@@ -933,16 +838,11 @@ int field_launch(mx::FieldArgs& a, bool lincomb, const uint32_t* h_mod, const ui
   a.mod = (const u32*)d_ws; a.rmodn = (const u32*)d_ws + limbs;
   if (lincomb) a.b = (const u32*)d_ws + 2 * limbs;
   a.limbs = limbs; a.nblk = geo.nblk;
-  switch (geo.K) {
-    case 1: return launch_field_k<1>(a, lincomb, s);
-    case 2: return launch_field_k<2>(a, lincomb, s);
-    case 4: return launch_field_k<4>(a, lincomb, s);
-    case 8: return launch_field_k<8>(a, lincomb, s);
-    case 16: return launch_field_k<16>(a, lincomb, s);
-    case 32: return launch_field_k<32>(a, lincomb, s);
-    case 64: return launch_field_k<64>(a, lincomb, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(geo.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return lincomb ? launch_groups<K, LIMBS_PER_LANE>(mx::lincomb_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, a.batch, s, a)
+                   : launch_groups<K, LIMBS_PER_LANE>(mx::fma_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, a.batch, s, a);
+  });
 }
 }  // namespace
 
@@ -971,9 +871,7 @@ extern "C" int mx_lincomb_mod(const uint32_t* d_x, const uint32_t* h_coeffs, uin
 namespace {
 template <int LPL>
 int launch_modinv(const mx::ModinvArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((mx::modinv_kernel<LPL>), dim3((unsigned)a.batch), dim3(64), 0, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::modinv_kernel<LPL>, a.batch, 64, 0, s, a);
 }
 }  // namespace
 
@@ -1013,8 +911,6 @@ extern "C" int mx_select_first(const uint32_t* d_rows, const int8_t* d_flags, ui
   mx::SelectArgs a;
   a.rows = d_rows; a.flags = (const signed char*)d_flags; a.out = d_out; a.counts = d_counts;
   a.groups = groups; a.group_size = group_size; a.keep = keep; a.limbs = limbs;
-  hipLaunchKernelGGL(mx::select_first_kernel, dim3((unsigned)groups), dim3(64), 0, (hipStream_t)stream, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::select_first_kernel, groups, 64, 0, (hipStream_t)stream, a);
 }
 

@@ -1,6 +1,7 @@
 // extern "C" entry points of the N^2-modulus modexp (second translation unit of libmxpaillier.so:
 // compiled in parallel with mx_capi.hip, the pair kernels are the most expensive to build).
 #include <cmath>
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_powmod_n2_split.hpp"
 #include "mx_bipair.hpp"
@@ -62,14 +63,6 @@ bool shape_n2(int n_bits, int window, int64_t batch, int limbs_per_lane, int wpg
   return true;
 }
 
-template <int K, int L>
-int launch_n2_kl(const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {
-  size_t lds = mx::powmod_n2_lds_bytes<K, L>();
-  hipLaunchKernelGGL((mx::powmod_n2_kernel<K, L, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-
 }  // namespace
 // wide-geometry instantiations live in mx_capi_n2w.hip, the two-wavefront kernels in mx_capi_n2s.hip (L = 3, 9) and
 // mx_capi_n2sw.hip (L = 18): translation units of their own, built in parallel
@@ -92,15 +85,10 @@ int launch_n2(const mx::PowmodN2Args& a, const N2Shape& p, int wpg, hipStream_t 
     return L == LIMBS_PER_LANE_WIDE ? mxs::launch_n2_split_wide(K, ts, a, nb, s) : mxs::launch_n2_split(K, L, ts, a, nb, s);
   }
   if (L == LIMBS_PER_LANE_WIDE) return mxw::launch_n2_wide(K, a, p.nblocks, s);
-  switch (K) {
-    case 1: return launch_n2_kl<1, LIMBS_PER_LANE>(a, p.nblocks, s);
-    case 2: return launch_n2_kl<2, LIMBS_PER_LANE>(a, p.nblocks, s);
-    case 4: return launch_n2_kl<4, LIMBS_PER_LANE>(a, p.nblocks, s);
-    case 8: return launch_n2_kl<8, LIMBS_PER_LANE>(a, p.nblocks, s);
-    case 16: return launch_n2_kl<16, LIMBS_PER_LANE>(a, p.nblocks, s);
-    case 32: return launch_n2_kl<32, LIMBS_PER_LANE>(a, p.nblocks, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32>(K, [&](auto k) {
+    constexpr int KK = decltype(k)::value;
+    return mx_launch(mx::powmod_n2_kernel<KK, LIMBS_PER_LANE, LIMB_BITS>, p.nblocks, 64, mx::powmod_n2_lds_bytes<KK, LIMBS_PER_LANE>(), s, a);
+  });
 }
 
 // Which instances run their tape modulo the friendly multiple of N (mx_powmod_n2.hpp): every 3-limb instance (its
@@ -225,20 +213,28 @@ double n2_estimate(int n_bits, int64_t batch, int lpl, int wpg, int* resident = 
   return *resident ? best : plain;
 }
 bool bipair_geometry(int n_bits, Geometry& gb);
-N2Choice n2_auto_shape(int n_bits, int64_t batch, int limbs_per_lane, int wpg) {
-  if (wpg == 4) return N2Choice{LIMBS_PER_LANE_LAT, 4, 0, 0};      // explicit: the five-wavefront latency form (mx_bipair.hpp)
-  N2Choice best{LIMBS_PER_LANE, 1, 0, 0};
+// The candidate shapes that the caller's limbs_per_lane and wavefronts per group (0: any) leave open, each given to
+// `estimate` (which may fill in the time-sliced fields of its candidate): the one with the lowest estimate above 0 into
+// `best`; false where no candidate has an instance.
+template <class F>
+bool n2_best_candidate(int limbs_per_lane, int wpg, N2Choice& best, F&& estimate) {
   double best_t = -1.0;
   for (int l : N2_LPLS) {
     if (limbs_per_lane && l != limbs_per_lane) continue;
     for (int w : {1, 2}) {
       if (wpg && w != wpg) continue;
-      int resident = 0, units = 0;
-      const double t = n2_estimate(n_bits, batch, l, w, &resident, &units);
-      if (t > 0 && (best_t < 0 || t < best_t)) { best_t = t; best = N2Choice{l, w, resident, units}; }
+      N2Choice c{l, w, 0, 0};
+      const double t = estimate(c);
+      if (t > 0 && (best_t < 0 || t < best_t)) { best_t = t; best = c; }
     }
   }
-  if (best_t < 0) best = N2Choice{limbs_per_lane ? limbs_per_lane : LIMBS_PER_LANE, wpg ? wpg : 1, 0, 0};   // reported as MX_ERR_SIZE by the caller
+  return best_t >= 0;
+}
+N2Choice n2_auto_shape(int n_bits, int64_t batch, int limbs_per_lane, int wpg) {
+  if (wpg == 4) return N2Choice{LIMBS_PER_LANE_LAT, 4, 0, 0};      // explicit: the five-wavefront latency form (mx_bipair.hpp)
+  N2Choice best{LIMBS_PER_LANE, 1, 0, 0};
+  if (!n2_best_candidate(limbs_per_lane, wpg, best, [&](N2Choice& c) { return n2_estimate(n_bits, batch, c.lpl, c.wpg, &c.resident, &c.units); }))
+    best = N2Choice{limbs_per_lane ? limbs_per_lane : LIMBS_PER_LANE, wpg ? wpg : 1, 0, 0};   // reported as MX_ERR_SIZE by the caller
   // Launches that the two-wavefront latency form would run with at most ONE workgroup of the five-wavefront form per compute
   // unit take that form where it exists (key_length 1024 / 2048 / 4096): both passes of every product on two wavefronts each,
   // 9.4 instead of 12.95 ms for 1 .. 512 ciphertexts at key_length 2048, 31.8 instead of 47 for 1 .. 256 at 4096
@@ -290,6 +286,28 @@ inline int64_t bipair_quot_bytes() { return align256((int64_t)mx::BP_QROWS * 3 *
 inline int64_t bipair_section_bytes(int limbs_n) { return n2_consts_bytes(limbs_n) + bipair_fold_bytes() + bipair_quot_bytes(); }
 inline int64_t bipair_section_offset(int limbs_n) { return N2_GEOS * n2_consts_bytes(limbs_n) + align256((int64_t)MAX_SLIDING_OPS * 4); }
 constexpr int N2_GEO_BIPAIR = 8;      // mx_nsquare_plan::geometries: the plan holds the constants of the five-wavefront form
+constexpr int N2_GEO_PIVOT_SHIFT = 8; // ... and, in bits 8-15, the pivot those constants were built with (0: a plan of an older library)
+
+// One resolved launch of the N^2 modexp: what the shape queries and mx_powmod_nsquare_run read their answers from.
+struct N2Launch {
+  N2Choice ch;            // limbs per lane, wavefronts per group, residents and units of the time-sliced form
+  N2Shape p;              // (five-wavefront form: the shape of the two-wavefront 3-limb form, whose slots and lanes it shares)
+  bool friendly = false;  // the instance runs its tape modulo the friendly multiple of N
+  Geometry bi;            // five-wavefront form only: its geometry, h_lo the pivot of the knob
+};
+// Refuses, in this order: a batch, limbs_per_lane or wavefronts_per_group that no launch takes (MX_ERR_ARG), then a
+// combination without an instance for this modulus (MX_ERR_SIZE).
+int resolve_n2(int n_bits, int64_t batch, int limbs_per_lane, int wpg, int window, N2Launch& r) {
+  if (batch <= 0) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
+  if (wpg < 0 || (wpg > 2 && wpg != 4)) return MX_ERR_ARG;
+  if (wpg == 4 && limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) return MX_ERR_SIZE;      // explicit only with 3 limbs
+  r.ch = n2_auto_shape(n_bits, batch, limbs_per_lane, wpg);
+  if (r.ch.wpg == 4 && !bipair_geometry(n_bits, r.bi)) return MX_ERR_SIZE;
+  if (!shape_n2(n_bits, window, batch, r.ch.lpl, r.ch.wpg, r.p)) return MX_ERR_SIZE;
+  r.friendly = r.ch.wpg == 4 || n2_friendly_instance(r.p.geo, r.ch.wpg, n_bits);
+  return MX_OK;
+}
 
 
 // The eight constant rows of one geometry (R = 2^m), each limbs_n words:
@@ -330,17 +348,9 @@ void n2_constants(u32* c, const u32* h_n, int limbs_n, int m, int k) {
   u32* nt = &c[(size_t)8 * limbs_n];
   mul_words(nt, h_n, limbs_n, &u, 1);                          // N~ = u N  (limbs_n + 1 words), = -1 mod 2^W
   for (int i = 0; i <= limbs_n; ++i) { if (++nt[i] != 0u) break; }      // + 1
-  // C2' = (u (1 - R)) mod N = (u * ((N + 1 - R mod N) mod N)) mod N      (rr = R mod N from above, != 0)
-  std::vector<u32> d(limbs_n), prod(limbs_n + 1), quo(limbs_n + 1), rem(limbs_n);
-  u64 br = 0, ca = 1;
-  for (int i = 0; i < limbs_n; ++i) {
-    u64 x = (u64)h_n[i] - rr[i] - br;
-    br = (x >> 63) & 1;
-    u64 e = (u64)(u32)x + ca;
-    d[i] = (u32)e;
-    ca = e >> 32;
-  }
-  mul_words(prod.data(), d.data(), limbs_n, &u, 1);
+  // C2' = (u (1 - R)) mod N = (u * ((N + 1 - R mod N) mod N)) mod N = (u C') mod N      (R mod N != 0)
+  std::vector<u32> prod(limbs_n + 1), quo(limbs_n + 1), rem(limbs_n);
+  mul_words(prod.data(), cp, limbs_n, &u, 1);
   divmod_words(quo.data(), rem.data(), prod.data(), limbs_n + 1, h_n, limbs_n);
   std::memcpy(&c[(size_t)8 * limbs_n + (limbs_n + 1)], rem.data(), (size_t)limbs_n * 4);
 }
@@ -348,19 +358,10 @@ void n2_constants(u32* c, const u32* h_n, int limbs_n, int m, int k) {
 
 extern "C" int mx_nsquare_launch_shape(int n_bits, int64_t batch, int limbs_per_lane, int wavefronts_per_group, int* k,
                                        int* l, int* w, int* blocks, int* wavefronts) {
-  if (!k || !l || !w || !blocks || !wavefronts || batch <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
-  if (wavefronts_per_group == 4) {                         // the five-wavefront latency form: explicit only (mx_bipair.hpp)
-    Geometry gb;
-    if ((limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) || !bipair_geometry(n_bits, gb)) return MX_ERR_SIZE;
-    *k = gb.K; *l = gb.L; *w = gb.W; *blocks = gb.nblk; *wavefronts = 4;
-    return MX_OK;
-  }
-  if (wavefronts_per_group < 0 || wavefronts_per_group > 2) return MX_ERR_ARG;
-  const N2Choice ch = n2_auto_shape(n_bits, batch, limbs_per_lane, wavefronts_per_group);
-  N2Shape p;
-  if (!shape_n2(n_bits, 1, batch, ch.lpl, ch.wpg, p)) return MX_ERR_SIZE;
-  *k = p.geo.K; *l = p.geo.L; *w = p.geo.W; *blocks = p.geo.nblk; *wavefronts = ch.wpg;
+  if (!k || !l || !w || !blocks || !wavefronts) return MX_ERR_ARG;
+  N2Launch r;
+  MX_TRY(resolve_n2(n_bits, batch, limbs_per_lane, wavefronts_per_group, 1, r));
+  *k = r.p.geo.K; *l = r.p.geo.L; *w = r.p.geo.W; *blocks = r.p.geo.nblk; *wavefronts = r.ch.wpg;
   return MX_OK;
 }
 
@@ -372,33 +373,29 @@ extern "C" int mx_nsquare_pieces_shape(int n_bits, int64_t total, int limbs_per_
                                        int* limbs_per_lane_out, int* wavefronts_per_group_out) {
   if (!limbs_per_lane_out || !wavefronts_per_group_out || total <= 0) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
-  if (wavefronts_per_group < 0 || wavefronts_per_group > 2) return MX_ERR_ARG;
-  double best_t = -1.0;
-  for (int l : N2_LPLS) {
-    if (limbs_per_lane && l != limbs_per_lane) continue;
-    for (int w : {1, 2}) {
-      if (wavefronts_per_group && w != wavefronts_per_group) continue;
-      double t = n2_estimate(n_bits, total, l, w);                // (no `resident` out-parameter: the plain launch)
-      // pieces of the wide two-wavefront form overlap better than one launch of their sum (4 x 5000 ciphertexts: 279 k/s
-      // against 257 k/s at 9 limbs per lane, where the estimates for one launch of 20 000 say 87 against 83 ms)
-      if (l == LIMBS_PER_LANE_WIDE && w == 2) t *= 0.93;
-      if (t > 0 && (best_t < 0 || t < best_t)) { best_t = t; *limbs_per_lane_out = l; *wavefronts_per_group_out = w; }
-    }
-  }
-  return best_t < 0 ? MX_ERR_SIZE : MX_OK;
+  if (wavefronts_per_group < 0 || wavefronts_per_group > 2) return MX_ERR_ARG;      // this entry alone: pieces never take the five-wavefront form
+  N2Choice best;
+  if (!n2_best_candidate(limbs_per_lane, wavefronts_per_group, best, [&](N2Choice& c) {
+        const double t = n2_estimate(n_bits, total, c.lpl, c.wpg);                  // (no `resident` out-parameter: the plain launch)
+        // pieces of the wide two-wavefront form overlap better than one launch of their sum (4 x 5000 ciphertexts: 279 k/s
+        // against 257 k/s at 9 limbs per lane, where the estimates for one launch of 20 000 say 87 against 83 ms)
+        return c.lpl == LIMBS_PER_LANE_WIDE && c.wpg == 2 ? t * 0.93 : t;
+      }))
+    return MX_ERR_SIZE;
+  *limbs_per_lane_out = best.lpl; *wavefronts_per_group_out = best.wpg;
+  return MX_OK;
 }
 
 extern "C" int mx_nsquare_launch_timesliced(int n_bits, int64_t batch, int limbs_per_lane, int wavefronts_per_group,
                                             int* resident_per_cu, int* units_per_group) {
-  if (!resident_per_cu || !units_per_group || batch <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
-  if (wavefronts_per_group == 4) { *resident_per_cu = 0; *units_per_group = 0; return MX_OK; }      // never time-sliced
-  if (wavefronts_per_group < 0 || wavefronts_per_group > 2) return MX_ERR_ARG;
-  const N2Choice ch = n2_auto_shape(n_bits, batch, limbs_per_lane, wavefronts_per_group);
-  N2Shape p;
-  if (!shape_n2(n_bits, 1, batch, ch.lpl, ch.wpg, p)) return MX_ERR_SIZE;
-  *resident_per_cu = ch.resident;
-  *units_per_group = ch.resident ? ch.units : 0;
+  if (!resident_per_cu || !units_per_group) return MX_ERR_ARG;
+  N2Launch r;
+  const int rc = resolve_n2(n_bits, batch, limbs_per_lane, wavefronts_per_group, 1, r);
+  // this entry alone: the five-wavefront form is never time-sliced, answered without looking whether the form exists
+  if (wavefronts_per_group == 4 && rc != MX_ERR_ARG) { *resident_per_cu = 0; *units_per_group = 0; return MX_OK; }
+  MX_TRY(rc);
+  *resident_per_cu = r.ch.resident;
+  *units_per_group = r.ch.resident ? r.ch.units : 0;
   return MX_OK;
 }
 
@@ -415,21 +412,12 @@ extern "C" int mx_nsquare_latency_form(int n_bits, int* lanes, int* positions, i
 
 extern "C" int mx_nsquare_launch_instance(int n_bits, int64_t batch, int limbs_per_lane, int wavefronts_per_group,
                                           int* k, int* l, int* wavefronts, int* friendly, int* timesliced) {
-  if (!k || !l || !wavefronts || !friendly || !timesliced || batch <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
-  if (wavefronts_per_group == 4) {
-    Geometry gb;
-    if ((limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) || !bipair_geometry(n_bits, gb)) return MX_ERR_SIZE;
-    *k = gb.K; *l = gb.L; *wavefronts = 4; *friendly = 1; *timesliced = 0;
-    return MX_OK;
-  }
-  if (wavefronts_per_group < 0 || wavefronts_per_group > 2) return MX_ERR_ARG;
-  const N2Choice ch = n2_auto_shape(n_bits, batch, limbs_per_lane, wavefronts_per_group);
-  N2Shape p;
-  if (!shape_n2(n_bits, 1, batch, ch.lpl, ch.wpg, p)) return MX_ERR_SIZE;
-  *k = p.geo.K; *l = p.geo.L; *wavefronts = ch.wpg;
-  *friendly = n2_friendly_instance(p.geo, ch.wpg, n_bits) ? 1 : 0;
-  *timesliced = ch.resident > 0 ? 1 : 0;
+  if (!k || !l || !wavefronts || !friendly || !timesliced) return MX_ERR_ARG;
+  N2Launch r;
+  MX_TRY(resolve_n2(n_bits, batch, limbs_per_lane, wavefronts_per_group, 1, r));
+  *k = r.p.geo.K; *l = r.p.geo.L; *wavefronts = r.ch.wpg;
+  *friendly = r.friendly ? 1 : 0;
+  *timesliced = r.ch.resident > 0 ? 1 : 0;
   return MX_OK;
 }
 
@@ -495,6 +483,43 @@ static int fixed_window_n2(int exp_bits) {
   return best;
 }
 
+// The section of the five-wavefront latency form (mx_bipair.hpp) at bp: constants for R' = 2^(W hL), the fold rows
+// (computed on the device from N by the bipartite form's setup kernel) and the quotients of the folds,
+// floor(2^(W (Pd + k)) / N).  h_lo: the pivot they were built with, 0 where the modulus has no such form.
+static int prepare_bipair_section(const u32* h_n, int limbs_n, int bits, char* bp, hipStream_t s, int& h_lo) {
+  h_lo = 0;
+  Geometry gb;
+  if (!bipair_geometry(bits, gb)) return MX_OK;
+  std::vector<u32> rows((size_t)n2_consts_words(limbs_n));
+  n2_constants(rows.data(), h_n, limbs_n, gb.W * gb.h_lo, bits - 1);
+  MX_TRY(upload_words(bp, rows.data(), rows.size(), s));
+  const int pd = gb.L * gb.nblk, pw = gb.L * gb.K;
+  std::vector<u32> quot((size_t)mx::BP_QROWS * pw, 0u);
+  for (int r = 0; r < mx::BP_QROWS; ++r) {
+    const int m = gb.W * (pd + r);                            // 2^m / N
+    const int la = m / 32 + 1;
+    std::vector<u32> num(la, 0u), q(la, 0u), rem(limbs_n, 0u);
+    num[m / 32] = 1u << (m % 32);
+    divmod_words(q.data(), rem.data(), num.data(), la, h_n, limbs_n);
+    for (int i = 0; i < pw; ++i) {                            // W-bit limb i of the quotient
+      const int bit = gb.W * i, w0 = bit >> 5, off = bit & 31;
+      u64 v = w0 < la ? q[w0] : 0u;
+      if (w0 + 1 < la) v |= (u64)q[w0 + 1] << 32;
+      quot[(size_t)r * pw + i] = (u32)(v >> off) & ((1u << gb.W) - 1u);
+    }
+    if (bit_length(q.data(), la) > gb.W * pw) return MX_ERR_SIZE;
+  }
+  char* qp = bp + n2_consts_bytes(limbs_n) + bipair_fold_bytes();
+  MX_TRY(upload_words(qp, quot.data(), quot.size(), s));
+  mx::BiSetupArgs sa;
+  sa.mods = (const u32*)bp;                                   // row 0 of the constants: N
+  sa.consts = (u32*)(bp + n2_consts_bytes(limbs_n));
+  sa.groups = 1; sa.limbs = limbs_n; sa.nblk = gb.nblk; sa.pd = pd; sa.h_lo = gb.h_lo;
+  MX_TRY(mxl::launch_bisetup(gb.K, sa, s));
+  h_lo = gb.h_lo;
+  return MX_OK;
+}
+
 extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_t* h_n, const uint32_t* h_exp,
                                             int limbs_n, int exp_limbs, int flags, void* d_plan, int64_t plan_bytes,
                                             void* stream) {
@@ -525,6 +550,11 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
     if (op == mx::N2_STORE) n_writes += 1;
     if (op == mx::N2_MUL || op == mx::N2_MULC || op == mx::N2_ADD || op == mx::N2_LOAD) n_reads += 1;
   };
+  if (ebits > 0) {            // x = (x_lo, 0) * K1 + (x_hi, 0) * K2, the first row of the table of either schedule
+    emit(mx::N2_LOAD, mx::N2_SLOT_LO); emit(mx::N2_MUL, mx::N2_SLOT_K1); emit(mx::N2_STORE, mx::N2_SLOT_TMP);
+    emit(mx::N2_LOAD, mx::N2_SLOT_HI); emit(mx::N2_MUL, mx::N2_SLOT_K2); emit(mx::N2_ADD, mx::N2_SLOT_TMP);
+    emit(mx::N2_STORE, mx::N2_SLOT_TABLE);
+  }
   if (ebits == 0) {
     emit(mx::N2_LOAD, mx::N2_SLOT_ONE);
   } else if (flags & MX_PLAN_FIXED_WINDOW) {
@@ -541,9 +571,6 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
       return (int)v;
     };
     auto slot_of = [&](int dg) { return dg ? mx::N2_SLOT_TABLE + dg - 1 : mx::N2_SLOT_ONE; };
-    emit(mx::N2_LOAD, mx::N2_SLOT_LO); emit(mx::N2_MUL, mx::N2_SLOT_K1); emit(mx::N2_STORE, mx::N2_SLOT_TMP);
-    emit(mx::N2_LOAD, mx::N2_SLOT_HI); emit(mx::N2_MUL, mx::N2_SLOT_K2); emit(mx::N2_ADD, mx::N2_SLOT_TMP);
-    emit(mx::N2_STORE, mx::N2_SLOT_TABLE);
     for (int t = 2; t < (1 << fw); ++t) { emit(mx::N2_MUL, mx::N2_SLOT_TABLE); emit(mx::N2_STORE, mx::N2_SLOT_TABLE + t - 1); }
     const int nwin = (ebits + fw - 1) / fw;
     emit(mx::N2_LOAD, slot_of(digit(nwin - 1)));
@@ -552,10 +579,6 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
   } else {
     w = sliding_window(ebits);
     std::vector<SlidingOp> ops = sliding_schedule(h_exp, exp_limbs, w);
-    // x = (x_lo, 0) * K1 + (x_hi, 0) * K2
-    emit(mx::N2_LOAD, mx::N2_SLOT_LO); emit(mx::N2_MUL, mx::N2_SLOT_K1); emit(mx::N2_STORE, mx::N2_SLOT_TMP);
-    emit(mx::N2_LOAD, mx::N2_SLOT_HI); emit(mx::N2_MUL, mx::N2_SLOT_K2); emit(mx::N2_ADD, mx::N2_SLOT_TMP);
-    emit(mx::N2_STORE, mx::N2_SLOT_TABLE);
     const int nodd = 1 << (w - 1);
     if (nodd > 1) {
       emit(mx::N2_SQR, 1); emit(mx::N2_STORE, mx::N2_SLOT_SQ); emit(mx::N2_LOAD, mx::N2_SLOT_TABLE);
@@ -590,39 +613,9 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
     MX_TRY(upload_words(dp + g * cb, rows[g].data(), rows[g].size(), s));
   }
   MX_TRY(upload_words(dp + N2_GEOS * cb, tape.data(), tape.size(), s));
-  // ---- the five-wavefront latency form (mx_bipair.hpp): constants for R' = 2^(W hL), the fold rows (computed on the
-  // device from N by the bipartite form's setup kernel) and the quotients of the folds, floor(2^(W (Pd + k)) / N)
-  Geometry gb;
-  if (bipair_geometry(bits, gb)) {
-    char* bp = dp + bipair_section_offset(limbs_n);
-    std::vector<u32> rows((size_t)n2_consts_words(limbs_n));
-    n2_constants(rows.data(), h_n, limbs_n, gb.W * gb.h_lo, k);
-    MX_TRY(upload_words(bp, rows.data(), rows.size(), s));
-    const int pd = gb.L * gb.nblk, pw = gb.L * gb.K;
-    std::vector<u32> quot((size_t)mx::BP_QROWS * pw, 0u);
-    for (int r = 0; r < mx::BP_QROWS; ++r) {
-      const int m = gb.W * (pd + r);                            // 2^m / N
-      const int la = m / 32 + 1;
-      std::vector<u32> num(la, 0u), q(la, 0u), rem(limbs_n, 0u);
-      num[m / 32] = 1u << (m % 32);
-      divmod_words(q.data(), rem.data(), num.data(), la, h_n, limbs_n);
-      for (int i = 0; i < pw; ++i) {                            // W-bit limb i of the quotient
-        const int bit = gb.W * i, w0 = bit >> 5, off = bit & 31;
-        u64 v = w0 < la ? q[w0] : 0u;
-        if (w0 + 1 < la) v |= (u64)q[w0 + 1] << 32;
-        quot[(size_t)r * pw + i] = (u32)(v >> off) & ((1u << gb.W) - 1u);
-      }
-      if (bit_length(q.data(), la) > gb.W * pw) return MX_ERR_SIZE;
-    }
-    char* qp = bp + n2_consts_bytes(limbs_n) + bipair_fold_bytes();
-    MX_TRY(upload_words(qp, quot.data(), quot.size(), s));
-    mx::BiSetupArgs sa;
-    sa.mods = (const u32*)bp;                                   // row 0 of the constants: N
-    sa.consts = (u32*)(bp + n2_consts_bytes(limbs_n));
-    sa.groups = 1; sa.limbs = limbs_n; sa.nblk = gb.nblk; sa.pd = pd; sa.h_lo = gb.h_lo;
-    MX_TRY(mxl::launch_bisetup(gb.K, sa, s));
-    geometries |= N2_GEO_BIPAIR;
-  }
+  int pivot = 0;
+  MX_TRY(prepare_bipair_section(h_n, limbs_n, bits, dp + bipair_section_offset(limbs_n), s, pivot));
+  if (pivot) geometries |= N2_GEO_BIPAIR | (pivot << N2_GEO_PIVOT_SHIFT);      // the plan carries the pivot its constants were built with
   plan->d_plan = d_plan;
   plan->plan_bytes = plan_bytes;
   plan->limbs_n = limbs_n;
@@ -649,39 +642,79 @@ extern "C" int64_t mx_powmod_nsquare_run_workspace_bytes(const mx_nsquare_plan* 
   return most < 0 ? MX_ERR_SIZE : most;
 }
 
+namespace {
+// The pivot of the five-wavefront form of a plan: the one prepare built the plan's constants with (bits 8-15 of
+// `geometries`), checked against the geometry — a multiple of L, L <= h_lo < Pd, E = 2^(W (Pd - h_lo)) a digit below N.
+// A plan of an older library has no pivot recorded: the knob's, as that library did (gb.h_lo on entry).
+int plan_pivot(const mx_nsquare_plan* plan, Geometry& gb) {
+  const int h = (plan->geometries >> N2_GEO_PIVOT_SHIFT) & 0xFF, pd = gb.L * gb.nblk;
+  if (h == 0) return MX_OK;
+  if (h % gb.L != 0 || h < gb.L || h >= pd || gb.W * (pd - h) >= plan->n_bits - 1) return MX_ERR_ARG;
+  gb.h_lo = h;
+  return MX_OK;
+}
+
+// What every launch of a run starts from: the whole tape on the constants of geometry gi, one plain segment.
+mx::PowmodN2Args n2_run_args(const mx_nsquare_plan* plan, const uint32_t* d_bases, uint32_t* d_out, int limbs2, int64_t batch,
+                             void* d_ws, const N2Launch& r) {
+  const int64_t cb = n2_consts_bytes(plan->limbs_n);
+  const char* dp = (const char*)plan->d_plan;
+  mx::PowmodN2Args a;
+  a.bases = d_bases; a.out = d_out;
+  a.consts = (const u32*)(dp + geo_index(r.ch.lpl) * cb);
+  a.tape = (const u32*)(dp + N2_GEOS * cb);
+  a.ntape = plan->ntape;
+  a.slots = (u32*)d_ws;
+  a.batch = batch; a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = r.p.geo.nblk; a.ksplit = plan->n_bits - 1;
+  a.friendly = r.friendly;
+  a.sched = nullptr; a.sched_groups = a.sched_segments = a.sched_n_sqr = 0;
+  a.first = a.last = 1; a.pos_begin = 0; a.pos_end = 0x7FFFFFFF;
+  return a;
+}
+// The last product and the epilogue as a segment of their own.  (The last product is the last word of the tape: the
+// segment is handed that word alone, at position 1 — walking the whole tape to it, a dependent scalar load per word, was
+// 100 of the five-wavefront launch's 136 us.)
+void last_word_segment(mx::PowmodN2Args& a) {
+  a.tape += a.ntape - 1; a.ntape = 1;
+  a.first = 0; a.last = 1; a.pos_begin = 1; a.pos_end = 0x7FFFFFFF;
+}
+}  // namespace
+
 extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_bases, uint32_t* d_out,
                                      int limbs2, int64_t batch, int limbs_per_lane, int wavefronts_per_group,
                                      int segments, void* d_ws, int64_t ws_bytes, void* stream) {
   if (!plan || !plan->d_plan || !d_bases || !d_out || !d_ws) return MX_ERR_ARG;
-  if (limbs2 <= 0 || batch <= 0 || plan->limbs_n <= 0 || plan->ntape <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
-  if (wavefronts_per_group < 0 || (wavefronts_per_group > 2 && wavefronts_per_group != 4)) return MX_ERR_ARG;
+  if (limbs2 <= 0 || plan->limbs_n <= 0 || plan->ntape <= 0) return MX_ERR_ARG;
   if (segments < 0 || segments > 64) return MX_ERR_ARG;
   const int bits = plan->n_bits;
   if (2 * bits - 1 > 32 * limbs2) return MX_ERR_ARG;          // rows too narrow for N^2
+  // this entry alone: MX_ERR_ARG where the shape queries say MX_ERR_SIZE
   if (wavefronts_per_group == 4 && limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) return MX_ERR_ARG;
-  N2Choice ch = n2_auto_shape(bits, batch, limbs_per_lane, wavefronts_per_group);
-  if (ch.wpg == 4 && wavefronts_per_group != 4 && !(plan->geometries & N2_GEO_BIPAIR)) ch.wpg = 2;      // a plan of an older layout
-  if (ch.wpg == 4) {
+  N2Launch r;
+  MX_TRY(resolve_n2(bits, batch, limbs_per_lane, wavefronts_per_group, plan->window, r));
+  if (r.ch.wpg == 4 && wavefronts_per_group != 4 && !(plan->geometries & N2_GEO_BIPAIR)) r.ch.wpg = 2;      // a plan of an older layout
+  const N2Choice& ch = r.ch;
+  const N2Shape& p = r.p;
+  const bool five = ch.wpg == 4;
+  if (!(plan->geometries & (five ? N2_GEO_BIPAIR : 1 << geo_index(ch.lpl)))) return MX_ERR_SIZE;
+  if (p.table_bytes + (ch.resident ? p.sched_bytes : 0) > ws_bytes) return MX_ERR_WORKSPACE;
+  if (2 * p.geo.K * p.geo.L + 8 < limbs2 + 2) return MX_ERR_ARG;   // row wider than the staging area
+  mx::PowmodN2Args a = n2_run_args(plan, d_bases, d_out, limbs2, batch, d_ws, r);
+  hipStream_t s = (hipStream_t)stream;
+  if (five) {
     // the five-wavefront latency form: its own kernel for everything in front of the last product, then the last product and
     // the epilogue as a last segment of the two-wavefront 3-limb kernel, whose slots it shares
-    Geometry gb;
-    if (!(plan->geometries & N2_GEO_BIPAIR) || !bipair_geometry(bits, gb)) return MX_ERR_SIZE;
-    N2Shape p;
-    if (!shape_n2(bits, plan->window, batch, LIMBS_PER_LANE_LAT, 2, p)) return MX_ERR_SIZE;
-    if (p.table_bytes > ws_bytes) return MX_ERR_WORKSPACE;
-    if (2 * p.geo.K * p.geo.L + 8 < limbs2 + 2) return MX_ERR_ARG;
+    Geometry gb = r.bi;
+    MX_TRY(plan_pivot(plan, gb));
     const int64_t cb = n2_consts_bytes(plan->limbs_n);
-    const char* dp = (const char*)plan->d_plan;
-    const char* bp = dp + bipair_section_offset(plan->limbs_n);
-    hipStream_t s = (hipStream_t)stream;
+    const char* bp = (const char*)plan->d_plan + bipair_section_offset(plan->limbs_n);
     const int pd = gb.L * gb.nblk;
     mx::PowmodBiPairArgs b;
     b.bases = d_bases;
     b.consts = (const u32*)bp;
     b.fold = (const u32*)(bp + cb);
     b.quot = (const u32*)(bp + cb + bipair_fold_bytes());
-    b.tape = (const u32*)(dp + N2_GEOS * cb);
+    b.tape = a.tape;
     b.slots = (u32*)d_ws;
     b.batch = batch; b.nlanes = p.nlanes;
     b.limbsn = plan->limbs_n; b.limbs2 = limbs2; b.ntape = plan->ntape;
@@ -692,36 +725,9 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
     b.e_pos = pd - gb.h_lo;
     MxKernelTimer timer(s);
     MX_TRY(mxb::launch_n2_bipair(gb.K, b, p.nblocks * mx::N2_SPLIT_PAIRS, s));
-    mx::PowmodN2Args a;
-    a.bases = d_bases; a.out = d_out;
-    a.consts = (const u32*)(dp + geo_index(LIMBS_PER_LANE_LAT) * cb);
-    a.tape = b.tape; a.ntape = plan->ntape; a.slots = (u32*)d_ws;
-    a.batch = batch; a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = p.geo.nblk; a.ksplit = bits - 1;
-    a.friendly = 1;
-    a.sched = nullptr; a.sched_groups = a.sched_segments = a.sched_n_sqr = 0;
-    // (the last product is the last word of the tape: the segment is handed that word alone, at position 1 — walking the
-    // whole tape to it, a dependent scalar load per word, was 100 of this launch's 136 us)
-    a.tape = b.tape + (plan->ntape - 1); a.ntape = 1;
-    a.first = 0; a.last = 1; a.pos_begin = 1; a.pos_end = 0x7FFFFFFF;
+    last_word_segment(a);
     return launch_n2(a, p, 2, s);
   }
-  N2Shape p;
-  if (!shape_n2(bits, plan->window, batch, ch.lpl, ch.wpg, p)) return MX_ERR_SIZE;
-  const int gi = geo_index(ch.lpl);
-  if (!(plan->geometries & (1 << gi))) return MX_ERR_SIZE;
-  if (p.table_bytes + (ch.resident ? p.sched_bytes : 0) > ws_bytes) return MX_ERR_WORKSPACE;
-  if (2 * p.geo.K * p.geo.L + 8 < limbs2 + 2) return MX_ERR_ARG;   // row wider than the staging area
-  const int64_t cb = n2_consts_bytes(plan->limbs_n);
-  const char* dp = (const char*)plan->d_plan;
-  mx::PowmodN2Args a;
-  a.bases = d_bases; a.out = d_out;
-  a.consts = (const u32*)(dp + gi * cb);
-  a.tape = (const u32*)(dp + N2_GEOS * cb);
-  a.ntape = plan->ntape;
-  a.slots = (u32*)d_ws;
-  a.batch = batch; a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = p.geo.nblk; a.ksplit = bits - 1;
-  a.friendly = n2_friendly_instance(p.geo, ch.wpg, bits);
-  hipStream_t s = (hipStream_t)stream;
   // segments: consecutive launches that each execute a stretch of the tape (mx_powmod_n2.hpp); positions
   // are counted in squarings, the accumulator travels through a scratch slot of the workspace
   int nseg = segments > 0 ? segments : n2_auto_segments(plan->n_sqr, p.nlanes / 64 * ch.wpg);
@@ -736,14 +742,12 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
     if (nseg < 1) nseg = 1;
     a.sched = (u32*)((char*)d_ws + p.table_bytes);
     a.sched_groups = (int)p.groups; a.sched_segments = nseg; a.sched_n_sqr = plan->n_sqr;
-    a.first = a.last = 1; a.pos_begin = 0; a.pos_end = 0x7FFFFFFF;
     MX_HIP(hipMemsetAsync(a.sched, 0, (size_t)(mx::N2_TS_HEADER + p.groups * (nseg - 1)) * 4, s));
     // no more workgroups than there are groups for their pairs
     int64_t wgs = (int64_t)ch.resident * device_cus();
     if (wgs > p.nblocks) wgs = p.nblocks;
     return launch_n2(a, p, ch.wpg, s, wgs);
   }
-  a.sched = nullptr; a.sched_groups = a.sched_segments = a.sched_n_sqr = 0;
   // The friendly-modulus instances of the one-wavefront wide kernel (mx_capi_n2w.hip: groups of 4 and 8 lanes) run the
   // tape up to, not including, its last product (N2_MULC, tape position n_sqr + 1); that product and the epilogue run as
   // one more segment on the plain instance (mx_powmod_n2.hpp).
@@ -757,9 +761,8 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
     MX_TRY(launch_n2(a, p, ch.wpg, s));
   }
   if (fr_tape) {
-    a.first = 0; a.last = 1; a.friendly = 0;
-    a.tape += plan->ntape - 1; a.ntape = 1;          // (the last word of the tape alone, as in the latency form above)
-    a.pos_begin = 1; a.pos_end = 0x7FFFFFFF;
+    a.friendly = 0;
+    last_word_segment(a);
     MX_TRY(launch_n2(a, p, ch.wpg, s));
   }
   return MX_OK;
@@ -794,8 +797,14 @@ extern "C" int mx_powmod_nsquare(const uint32_t* d_bases, uint32_t* d_out, const
 
 // ---- multi-exponentiation modulo N^2 (mx_multiexp_n2.hpp): homomorphic linear maps of ciphertexts -----------------
 namespace mxm { int launch_multiexp(int K, bool table, const mx::MultiexpN2Args& a, int64_t nblocks, hipStream_t s); }
+namespace mxmm { int launch_shared(int K, const mx::SharedN2Args& a, int64_t nblocks, hipStream_t s); }
 namespace {
 constexpr int MX_MULTIEXP_MAX_WINDOW = 8;
+// limits of the narrow-geometry entries
+constexpr int64_t MX_GRID_WAVEFRONTS = (int64_t)1 << 31;       // one grid holds fewer wavefronts than this; columns, rows and shared tables of a map: at most this many
+constexpr int64_t MX_MAX_ROWS = ((int64_t)1 << 31) - 1;        // row counts of the histogram and scan entries stay below (one more group: the one row)
+constexpr int64_t MX_MAX_POSITIONS = (int64_t)1 << 30;         // samples of a tile, positions of a convolution (they travel as int)
+constexpr int64_t MX_MAX_LOCAL_TABLES = (int64_t)1 << 36;      // tables of a convolution's own grids
 constexpr int MX_MULTIEXP_MODEL_MAX_WINDOW = 6;         // the cost model's range (the caller may ask for up to 8)
 // the narrow geometry of the pair kernel: groups of 1 .. 32 lanes
 bool multiexp_geometry(int n_bits, int limbs_per_lane, Geometry& g) {
@@ -868,6 +877,71 @@ void weight_fields(int terms, int weight_bits, int window, int& wwords, int& nwi
   wwords = (weight_bits + 31) / 32;
   nwin = terms > 0 ? (weight_bits + window - 1) / window : 0;
 }
+
+// a sizing query's answer (negative: its refusal) against what the caller brought
+inline int workspace_fits(int64_t need, int64_t have) {
+  if (need < 0) return (int)need;
+  return need > have ? MX_ERR_WORKSPACE : MX_OK;
+}
+
+// What the weighted maps (multiexp, matmul, conv) all refuse as arguments, after the counts of their own; then the
+// refusals of narrow_launch.
+int weighted_launch(const mx_nsquare_plan* plan, const void* d_out, const void* d_ws, int64_t n_rows, int limbs2,
+                    const int32_t* d_index, const uint32_t* d_weights, int terms, int weight_bits, int limbs_per_lane,
+                    int window, NarrowLaunch& o) {
+  if (!plan || !plan->d_plan || !d_out || !d_ws || plan->limbs_n <= 0) return MX_ERR_ARG;
+  if (n_rows <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
+  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  if (weight_bits > 2 * plan->n_bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  return narrow_launch(plan, limbs2, limbs_per_lane, o);
+}
+
+// Workspace of n_tables tables.  The table pass runs one group per table in one grid: at most 2^31 wavefronts — which
+// also keeps the byte count (below 2^37 tables of at most 2^19 bytes) inside 64 bits.
+int64_t tables_workspace_bytes(int n_bits, int64_t n_tables, int limbs_per_lane, int window) {
+  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
+  Geometry g;
+  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
+  const int gpw = 64 / g.K;
+  if ((n_tables + gpw - 1) / gpw >= MX_GRID_WAVEFRONTS) return MX_ERR_SIZE;
+  return mx_multiexp_nsquare_workspace_bytes(n_bits, n_tables, limbs_per_lane, window);
+}
+
+// rows x blocks_per_row workgroups in one grid
+inline bool rows_fit_grid(int64_t n_rows, int64_t blocks_per_row) { return n_rows <= MX_GRID_WAVEFRONTS / blocks_per_row - 1; }
+
+// The maps with weights shared among positions (matmul: the samples of a tile; conv: the positions of the output grids),
+// after the entry point's checks: the table pass over n_local + n_shared tables (d_inputs NULL: the tables already in the
+// workspace, built by an earlier call with the same inputs and window), then the shared-weight pass — output row r at
+// position p reads table column * stride + p (+ origin[p] where there are origins), out [p / image_positions][r][p % ..].
+int launch_shared_map(const NarrowLaunch& o, const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_local,
+                      int64_t n_shared, int limbs2, const int32_t* d_index, const uint32_t* d_weights, int terms,
+                      int weight_bits, const int64_t* d_origin, int64_t stride, int64_t positions, int64_t image_positions,
+                      uint32_t* d_out, int64_t n_rows, int window, void* d_ws, int64_t ws_bytes, hipStream_t s) {
+  const int64_t pos_blocks = o.blocks(positions);
+  if (!rows_fit_grid(n_rows, pos_blocks)) return MX_ERR_SIZE;                 // more wavefronts than one grid holds
+  MX_TRY(workspace_fits(tables_workspace_bytes(plan->n_bits, n_local + n_shared, LIMBS_PER_LANE, window), ws_bytes));
+  MxKernelTimer timer(s);
+  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_local + n_shared, limbs2, window, d_ws, s));
+  mx::SharedN2Args a{};
+  a.tables = (const u32*)d_ws;
+  a.consts = o.consts;
+  a.index = d_index;
+  a.weights = d_weights;
+  a.origin = (const mx::i64*)d_origin;
+  a.out = d_out;
+  a.n_local = n_local; a.n_shared = n_shared; a.rows = n_rows;
+  a.stride = (int)stride;
+  a.image_positions = (int)image_positions;      // (conv: divides n_positions <= 2^30)
+  a.positions = (int)positions; a.pos_blocks = (int)pos_blocks;
+  a.terms = terms;
+  a.window = window;
+  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
+  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
+  return mxmm::launch_shared(o.g.K, a, n_rows * pos_blocks, s);
+}
 }  // namespace
 
 extern "C" int mx_multiexp_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
@@ -904,18 +978,10 @@ extern "C" int mx_multiexp_nsquare_run(const mx_nsquare_plan* plan, const uint32
                                        const int32_t* d_index, const uint32_t* d_weights, int terms, int weight_bits,
                                        uint32_t* d_out, int64_t n_outputs, int limbs_per_lane, int window, void* d_ws,
                                        int64_t ws_bytes, void* stream) {
-  if (!plan || !plan->d_plan || !d_out || !d_ws || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_inputs <= 0 || n_outputs <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
-  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
-  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
-  const int bits = plan->n_bits;
-  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  if (n_inputs <= 0) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  const int64_t need = mx_multiexp_nsquare_workspace_bytes(bits, n_inputs, LIMBS_PER_LANE, window);
-  if (need < 0) return (int)need;
-  if (need > ws_bytes) return MX_ERR_WORKSPACE;
+  MX_TRY(weighted_launch(plan, d_out, d_ws, n_outputs, limbs2, d_index, d_weights, terms, weight_bits, limbs_per_lane, window, o));
+  MX_TRY(workspace_fits(mx_multiexp_nsquare_workspace_bytes(plan->n_bits, n_inputs, LIMBS_PER_LANE, window), ws_bytes));
   mx::MultiexpN2Args a{};
   a.tables = (u32*)d_ws;
   a.consts = o.consts;
@@ -1084,8 +1150,6 @@ extern "C" int mx_fixedbase_nsquare_run(const mx_nsquare_plan* plan, const void*
 }
 
 // ---- encrypted matrix products over a batch of ciphertext vectors (mx_matmul_n2.hpp) ---------------------------------
-namespace mxmm { int launch_shared(int K, const mx::SharedN2Args& a, int64_t nblocks, hipStream_t s); }
-
 extern "C" int mx_matmul_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
   return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
 }
@@ -1103,8 +1167,7 @@ extern "C" int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_row
   // counts beyond what one launch takes (mx_matmul_nsquare_run) are refused here too; this keeps every product below
   // inside 64 bits: 2^31 columns of at most 2^20 bytes, 2^31 rows of at most 2^30 samples, and terms * outputs is formed
   // only for fewer outputs than fill the device
-  const int64_t lim = (int64_t)1 << 31;
-  if (n_cols > lim || n_rows > lim || terms > lim) return MX_ERR_SIZE;
+  if (n_cols > MX_GRID_WAVEFRONTS || n_rows > MX_GRID_WAVEFRONTS || terms > MX_GRID_WAVEFRONTS) return MX_ERR_SIZE;
   *lanes = g.K;
   *limbs_per_lane_out = g.L;
   // the window of ONE sample's map (every sample pays for its own tables), limited so that one sample's tables fit
@@ -1116,7 +1179,7 @@ extern "C" int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_row
   const int64_t per_sample = n_cols * (entry_bytes << w);
   int64_t tile = per_sample > 0 ? table_budget_bytes / per_sample : batch;
   if (tile > batch) tile = batch;
-  if (tile > (int64_t)1 << 30) tile = (int64_t)1 << 30;
+  if (tile > MX_MAX_POSITIONS) tile = MX_MAX_POSITIONS;
   if (tile < 1) tile = 1;
   *tile_batch = tile;
   *chunk_terms = splitk_chunk(g, n_rows * tile, terms);      // on the outputs of one tile
@@ -1125,62 +1188,22 @@ extern "C" int mx_matmul_nsquare_shape(int n_bits, int64_t n_cols, int64_t n_row
 
 extern "C" int64_t mx_matmul_nsquare_workspace_bytes(int n_bits, int64_t n_cols, int64_t n_shared, int64_t tile_batch,
                                                      int limbs_per_lane, int window) {
-  if (n_cols < 0 || n_shared < 0 || tile_batch < 1 || tile_batch > ((int64_t)1 << 30) || n_cols > ((int64_t)1 << 31) ||
-      n_shared > ((int64_t)1 << 31)) return MX_ERR_ARG;
-  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
-  Geometry g;
-  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  // the table pass runs one group per table in one grid: at most 2^31 wavefronts — which also keeps the byte count
-  // (below 2^37 tables of at most 2^19 bytes) inside 64 bits
-  const int64_t n_tables = n_cols * tile_batch + n_shared;
-  const int gpw = 64 / g.K;
-  if ((n_tables + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
-  return mx_multiexp_nsquare_workspace_bytes(n_bits, n_tables, limbs_per_lane, window);
+  if (n_cols < 0 || n_shared < 0 || tile_batch < 1 || tile_batch > MX_MAX_POSITIONS || n_cols > MX_GRID_WAVEFRONTS ||
+      n_shared > MX_GRID_WAVEFRONTS) return MX_ERR_ARG;
+  return tables_workspace_bytes(n_bits, n_cols * tile_batch + n_shared, limbs_per_lane, window);
 }
 
 extern "C" int mx_matmul_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_cols, int64_t n_shared,
                                      int64_t tile_batch, int limbs2, const int32_t* d_index, const uint32_t* d_weights,
                                      int terms, int weight_bits, uint32_t* d_out, int64_t n_rows, int limbs_per_lane,
                                      int window, void* d_ws, int64_t ws_bytes, void* stream) {
-  if (!plan || !plan->d_plan || !d_out || !d_ws || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_cols < 0 || n_shared < 0 || n_cols > ((int64_t)1 << 31) || n_shared > ((int64_t)1 << 31)) return MX_ERR_ARG;
-  if (tile_batch < 1 || tile_batch > ((int64_t)1 << 30) || n_rows <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
-  if (n_cols * tile_batch + n_shared <= 0) return MX_ERR_ARG;
-  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
-  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
-  const int bits = plan->n_bits;
-  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  if (n_cols < 0 || n_shared < 0 || n_cols > MX_GRID_WAVEFRONTS || n_shared > MX_GRID_WAVEFRONTS) return MX_ERR_ARG;
+  if (tile_batch < 1 || tile_batch > MX_MAX_POSITIONS || n_cols * tile_batch + n_shared <= 0) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  const int64_t tile_blocks = o.blocks(tile_batch);
-  if (n_rows > ((int64_t)1 << 31) / tile_blocks - 1) return MX_ERR_SIZE;      // more wavefronts than one grid holds
-  const int64_t n_tables = n_cols * tile_batch + n_shared;
-  if (o.blocks(n_tables) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
-  const int64_t need = mx_matmul_nsquare_workspace_bytes(bits, n_cols, n_shared, tile_batch, LIMBS_PER_LANE, window);
-  if (need < 0) return (int)need;
-  if (need > ws_bytes) return MX_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  MxKernelTimer timer(s);
-  // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs, tile and window)
-  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_tables, limbs2, window, d_ws, s));
-  // the shared-weight pass with the samples of the tile as positions: table column * tile + sample, out [tile][rows]
-  mx::SharedN2Args a{};
-  a.tables = (const u32*)d_ws;
-  a.consts = o.consts;
-  a.index = d_index;
-  a.weights = d_weights;
-  a.origin = nullptr;
-  a.out = d_out;
-  a.n_local = n_cols * tile_batch; a.n_shared = n_shared; a.rows = n_rows;
-  a.stride = (int)tile_batch;
-  a.image_positions = 1;
-  a.positions = (int)tile_batch; a.pos_blocks = (int)tile_blocks;
-  a.terms = terms;
-  a.window = window;
-  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
-  return mxmm::launch_shared(o.g.K, a, n_rows * tile_blocks, s);
+  MX_TRY(weighted_launch(plan, d_out, d_ws, n_rows, limbs2, d_index, d_weights, terms, weight_bits, limbs_per_lane, window, o));
+  // the samples of the tile as positions: table column * tile + sample, out [tile][rows]
+  return launch_shared_map(o, plan, d_inputs, n_cols * tile_batch, n_shared, limbs2, d_index, d_weights, terms, weight_bits,
+                           nullptr, tile_batch, tile_batch, 1, d_out, n_rows, window, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- encrypted convolutions of ciphertext grids with a public kernel (mx_matmul_n2.hpp) ------------------------------
@@ -1190,16 +1213,9 @@ extern "C" int mx_conv_nsquare_instances(int* lanes, int* limbs_per_lane, int ma
 
 extern "C" int64_t mx_conv_nsquare_workspace_bytes(int n_bits, int64_t n_local, int64_t n_shared, int limbs_per_lane,
                                                    int window) {
-  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > ((int64_t)1 << 36) || n_shared > ((int64_t)1 << 31))
+  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > MX_MAX_LOCAL_TABLES || n_shared > MX_GRID_WAVEFRONTS)
     return MX_ERR_ARG;
-  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
-  Geometry g;
-  if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
-  // the table pass runs one group per table in one grid: at most 2^31 wavefronts — which also keeps the byte count
-  // (below 2^37 tables of at most 2^19 bytes) inside 64 bits
-  const int gpw = 64 / g.K;
-  if ((n_local + n_shared + gpw - 1) / gpw >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
-  return mx_multiexp_nsquare_workspace_bytes(n_bits, n_local + n_shared, limbs_per_lane, window);
+  return tables_workspace_bytes(n_bits, n_local + n_shared, limbs_per_lane, window);
 }
 
 extern "C" int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_local, int64_t n_shared,
@@ -1207,44 +1223,15 @@ extern "C" int mx_conv_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
                                    int weight_bits, const int64_t* d_origin, int64_t n_positions, int64_t image_positions,
                                    uint32_t* d_out, int64_t n_rows, int limbs_per_lane, int window, void* d_ws,
                                    int64_t ws_bytes, void* stream) {
-  if (!plan || !plan->d_plan || !d_out || !d_ws || !d_origin || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > ((int64_t)1 << 36) || n_shared > ((int64_t)1 << 31))
+  if (!d_origin) return MX_ERR_ARG;
+  if (n_local < 0 || n_shared < 0 || n_local + n_shared < 1 || n_local > MX_MAX_LOCAL_TABLES || n_shared > MX_GRID_WAVEFRONTS)
     return MX_ERR_ARG;
-  if (n_positions < 1 || n_positions > ((int64_t)1 << 30) || image_positions < 1 || n_positions % image_positions != 0) return MX_ERR_ARG;
-  if (n_rows <= 0 || limbs2 <= 0 || terms < 0 || weight_bits < 0) return MX_ERR_ARG;
-  if (terms > 0 && (!d_index || !d_weights)) return MX_ERR_ARG;
-  if (window < 1 || window > MX_MULTIEXP_MAX_WINDOW) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
-  const int bits = plan->n_bits;
-  if (weight_bits > 2 * bits + 64) return MX_ERR_ARG;                // the documented weight bound
+  if (n_positions < 1 || n_positions > MX_MAX_POSITIONS || image_positions < 1 || n_positions % image_positions != 0) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  const int64_t pos_blocks = o.blocks(n_positions);
-  if (n_rows > ((int64_t)1 << 31) / pos_blocks - 1) return MX_ERR_SIZE;       // more wavefronts than one grid holds
-  const int64_t need = mx_conv_nsquare_workspace_bytes(bits, n_local, n_shared, LIMBS_PER_LANE, window);
-  if (need < 0) return (int)need;
-  if (need > ws_bytes) return MX_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  MxKernelTimer timer(s);
-  // (d_inputs NULL: the tables already in the workspace, built by an earlier call with the same inputs and window)
-  if (d_inputs) MX_TRY(launch_table_pass(o, plan, d_inputs, n_local + n_shared, limbs2, window, d_ws, s));
-  // the shared-weight pass: the table of the tap at position 0 + the position's origin, out [image][rows][position]
-  mx::SharedN2Args a{};
-  a.tables = (const u32*)d_ws;
-  a.consts = o.consts;
-  a.index = d_index;
-  a.weights = d_weights;
-  a.origin = (const mx::i64*)d_origin;
-  a.out = d_out;
-  a.n_local = n_local; a.n_shared = n_shared; a.rows = n_rows;
-  a.stride = 1;
-  a.image_positions = (int)image_positions;      // divides n_positions <= 2^30
-  a.positions = (int)n_positions; a.pos_blocks = (int)pos_blocks;
-  a.terms = terms;
-  a.window = window;
-  weight_fields(terms, weight_bits, window, a.wwords, a.nwin);
-  a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
-  return mxmm::launch_shared(o.g.K, a, n_rows * pos_blocks, s);
+  MX_TRY(weighted_launch(plan, d_out, d_ws, n_rows, limbs2, d_index, d_weights, terms, weight_bits, limbs_per_lane, window, o));
+  // the table of the tap at position 0 + the position's origin, out [image][rows][position]
+  return launch_shared_map(o, plan, d_inputs, n_local, n_shared, limbs2, d_index, d_weights, terms, weight_bits, d_origin, 1,
+                           n_positions, image_positions, d_out, n_rows, window, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- encrypted histograms: sums of ciphertexts by a public bin index (mx_hist_n2.hpp) --------------------------------
@@ -1266,6 +1253,15 @@ int hist_chunk(const Geometry& g, int64_t n_segments, int64_t total_terms) {
   return (int)(chunk < 1 ? 1 : chunk);
 }
 int64_t hist_row_bytes(const Geometry& g) { return (int64_t)2 * g.K * g.L * 4; }
+// a row count of the histogram and scan entries: at least `least`, and room for one more group (the one row)
+inline bool row_count_ok(int64_t n, int64_t least) { return n >= least && n < MX_MAX_ROWS; }
+// What the histogram and scan launches all refuse after their own arguments: a limbs_per_lane other than the narrow one
+// (MX_ERR_ARG), the refusals of narrow_launch, and more groups than one grid holds wavefronts for (MX_ERR_SIZE).
+int rows_launch(const mx_nsquare_plan* plan, int limbs2, int limbs_per_lane, int64_t groups, NarrowLaunch& o) {
+  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
+  return o.blocks(groups) >= MX_GRID_WAVEFRONTS ? MX_ERR_SIZE : MX_OK;
+}
 }  // namespace
 
 extern "C" int mx_histogram_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
@@ -1289,7 +1285,7 @@ extern "C" int mx_histogram_nsquare_shape(int n_bits, int64_t n_samples, int64_t
 
 extern "C" int64_t mx_histogram_nsquare_workspace_bytes(int n_bits, int64_t n_rows, int limbs_per_lane) {
   Geometry g;
-  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) - 1) return MX_ERR_ARG;
+  if (!row_count_ok(n_rows, 0)) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   if (!multiexp_geometry(n_bits, limbs_per_lane, g)) return MX_ERR_SIZE;
   return align256((n_rows + 1) * hist_row_bytes(g));
@@ -1298,13 +1294,10 @@ extern "C" int64_t mx_histogram_nsquare_workspace_bytes(int n_bits, int64_t n_ro
 extern "C" int mx_histogram_nsquare_convert(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_samples, int limbs2,
                                             uint32_t* d_rows, int64_t rows_bytes, int limbs_per_lane, void* stream) {
   if (!plan || !plan->d_plan || !d_inputs || !d_rows || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_samples <= 0 || n_samples >= ((int64_t)1 << 31) - 1 || limbs2 <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  if (!row_count_ok(n_samples, 1) || limbs2 <= 0) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  const int64_t need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_samples, LIMBS_PER_LANE);
-  if (need < 0) return (int)need;
-  if (need > rows_bytes) return MX_ERR_WORKSPACE;
+  MX_TRY(rows_launch(plan, limbs2, limbs_per_lane, n_samples + 1, o));       // one more group: the one row
+  MX_TRY(workspace_fits(mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_samples, LIMBS_PER_LANE), rows_bytes));
   mx::HistN2Args a{};
   a.inputs = d_inputs;
   a.rows_out = d_rows;
@@ -1313,28 +1306,20 @@ extern "C" int mx_histogram_nsquare_convert(const mx_nsquare_plan* plan, const u
   a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk; a.ksplit = plan->n_bits - 1;
   hipStream_t s = (hipStream_t)stream;
   MxKernelTimer timer(s);
-  return mxh::launch_hist(o.g.K, true, a, o.blocks(n_samples + 1), s);       // one more group: the one row
+  return mxh::launch_hist(o.g.K, true, a, o.blocks(n_samples + 1), s);
 }
 
 extern "C" int mx_histogram_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, const int32_t* d_index,
                                         int64_t n_pieces, int chunk, uint32_t* d_out, int pair_form_out, int limbs2,
                                         int64_t out_bytes, int limbs_per_lane, void* stream) {
   if (!plan || !plan->d_plan || !d_rows || !d_index || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) - 1 || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
+  if (!row_count_ok(n_rows, 0) || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
   if (chunk < 1 || chunk > MX_HIST_MAX_CHUNK) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
   const int64_t groups = n_pieces + (pair_form_out ? 1 : 0);                  // one more group: the one row of the next level
-  if (o.blocks(groups) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;             // more wavefronts than one grid holds
-  int64_t need;
-  if (pair_form_out) {
-    need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_pieces, LIMBS_PER_LANE);
-    if (need < 0) return (int)need;
-  } else {
-    need = n_pieces * (int64_t)limbs2 * 4;
-  }
-  if (need > out_bytes) return MX_ERR_WORKSPACE;
+  MX_TRY(rows_launch(plan, limbs2, limbs_per_lane, groups, o));
+  MX_TRY(workspace_fits(pair_form_out ? mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_pieces, LIMBS_PER_LANE)
+                                      : n_pieces * (int64_t)limbs2 * 4, out_bytes));
   mx::HistN2Args a{};
   a.rows = d_rows;
   a.consts = o.consts;
@@ -1360,16 +1345,12 @@ extern "C" int mx_scan_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
                                    const int32_t* d_carry_index, int exclusive, uint32_t* d_out, int limbs2, int64_t out_bytes,
                                    int limbs_per_lane, void* stream) {
   if (!plan || !plan->d_plan || !d_rows || !d_index || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1 || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
-  if (d_carry_rows && (!d_carry_index || n_carry_rows < 0 || n_carry_rows >= ((int64_t)1 << 31) - 1)) return MX_ERR_ARG;
+  if (!row_count_ok(n_rows, 1) || n_pieces <= 0 || limbs2 <= 0) return MX_ERR_ARG;
+  if (d_carry_rows && (!d_carry_index || !row_count_ok(n_carry_rows, 0))) return MX_ERR_ARG;
   if (chunk < 1 || chunk > MX_HIST_MAX_CHUNK) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  if (o.blocks(n_pieces + 1) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;       // more wavefronts than one grid holds
-  const int64_t need = mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_rows, LIMBS_PER_LANE);
-  if (need < 0) return (int)need;
-  if (need > out_bytes) return MX_ERR_WORKSPACE;
+  MX_TRY(rows_launch(plan, limbs2, limbs_per_lane, n_pieces + 1, o));         // one more group: the one row of the output set
+  MX_TRY(workspace_fits(mx_histogram_nsquare_workspace_bytes(plan->n_bits, n_rows, LIMBS_PER_LANE), out_bytes));
   mx::ScanN2Args a{};
   a.rows = d_rows;
   a.carry_rows = d_carry_rows;
@@ -1382,18 +1363,16 @@ extern "C" int mx_scan_nsquare_run(const mx_nsquare_plan* plan, const uint32_t* 
   a.limbsn = plan->limbs_n; a.limbs2 = limbs2; a.nblk = o.g.nblk;
   hipStream_t s = (hipStream_t)stream;
   MxKernelTimer timer(s);
-  return mxh::launch_scan(o.g.K, false, a, o.blocks(n_pieces + 1), s);         // one more group: the one row of the output set
+  return mxh::launch_scan(o.g.K, false, a, o.blocks(n_pieces + 1), s);
 }
 
 extern "C" int mx_scan_nsquare_store(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, uint32_t* d_out,
                                      int limbs2, int64_t out_bytes, int limbs_per_lane, void* stream) {
   if (!plan || !plan->d_plan || !d_rows || !d_out || plan->limbs_n <= 0) return MX_ERR_ARG;
-  if (n_rows <= 0 || n_rows >= ((int64_t)1 << 31) - 1 || limbs2 <= 0) return MX_ERR_ARG;
-  if (limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE) return MX_ERR_ARG;
+  if (!row_count_ok(n_rows, 1) || limbs2 <= 0) return MX_ERR_ARG;
   NarrowLaunch o;
-  MX_TRY(narrow_launch(plan, limbs2, limbs_per_lane, o));
-  if (o.blocks(n_rows) >= ((int64_t)1 << 31)) return MX_ERR_SIZE;
-  if (n_rows * (int64_t)limbs2 * 4 > out_bytes) return MX_ERR_WORKSPACE;
+  MX_TRY(rows_launch(plan, limbs2, limbs_per_lane, n_rows, o));
+  MX_TRY(workspace_fits(n_rows * (int64_t)limbs2 * 4, out_bytes));
   mx::ScanN2Args a{};
   a.rows = d_rows;
   a.consts = o.consts;

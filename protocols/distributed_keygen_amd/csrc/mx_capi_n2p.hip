@@ -1,26 +1,14 @@
 // Instantiations of the packing kernel modulo N^2 (mx_pack_n2.hpp) for the narrow geometry, every group width of the
 // pair kernel (translation unit of its own, built in parallel with the others).
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_pack_n2.hpp"
 
 namespace mxp {
-template <int K>
-static int launch_k(const mx::PackN2Args& a, int64_t nblocks, hipStream_t s) {
-  const size_t lds = mx::pack_n2_lds_bytes<K, LIMBS_PER_LANE>();
-  hipLaunchKernelGGL((mx::pack_n2_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-
 int launch_pack(int K, const mx::PackN2Args& a, int64_t nblocks, hipStream_t s) {
-  switch (K) {
-    case 1: return launch_k<1>(a, nblocks, s);
-    case 2: return launch_k<2>(a, nblocks, s);
-    case 4: return launch_k<4>(a, nblocks, s);
-    case 8: return launch_k<8>(a, nblocks, s);
-    case 16: return launch_k<16>(a, nblocks, s);
-    case 32: return launch_k<32>(a, nblocks, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32>(K, [&](auto k) {
+    constexpr int KK = decltype(k)::value;
+    return mx_launch(mx::pack_n2_kernel<KK, LIMBS_PER_LANE, LIMB_BITS>, nblocks, 64, mx::pack_n2_lds_bytes<KK, LIMBS_PER_LANE>(), s, a);
+  });
 }
 }  // namespace mxp

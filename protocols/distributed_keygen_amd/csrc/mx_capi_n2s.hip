@@ -1,5 +1,6 @@
 // Two-wavefront instantiations of the N^2-modulus pair kernel (mx_powmod_n2_split.hpp) for 3 and 9 limbs per
 // lane (translation unit of its own, built in parallel with the others).
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_powmod_n2_split.hpp"
 
@@ -11,9 +12,7 @@ static int launch_form(const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s
     static bool allowed[MX_MAX_DEVICES] = {};
     MX_HIP(mx_allow_dynamic_lds(reinterpret_cast<const void*>(&mx::powmod_n2_split_kernel<K, L, LIMB_BITS, TS, FR>), (int)lds, allowed));
   }
-  hipLaunchKernelGGL((mx::powmod_n2_split_kernel<K, L, LIMB_BITS, TS, FR>), dim3((unsigned)nblocks), dim3(64 * 2 * mx::N2_SPLIT_PAIRS), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::powmod_n2_split_kernel<K, L, LIMB_BITS, TS, FR>, nblocks, 64 * 2 * mx::N2_SPLIT_PAIRS, lds, s, a);
 }
 // time-sliced instances exist for 9 limbs per lane and groups of at most 16 lanes (key_length up to 4096): a launch
 // of wider groups that outnumbers the resident wavefronts is better served by more limbs per lane
@@ -33,15 +32,7 @@ static int launch(bool ts, const mx::PowmodN2Args& a, int64_t nblocks, hipStream
 
 template <int L>
 static int launch_l(int K, bool ts, const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {
-  switch (K) {
-    case 1: return launch<1, L>(ts, a, nblocks, s);
-    case 2: return launch<2, L>(ts, a, nblocks, s);
-    case 4: return launch<4, L>(ts, a, nblocks, s);
-    case 8: return launch<8, L>(ts, a, nblocks, s);
-    case 16: return launch<16, L>(ts, a, nblocks, s);
-    case 32: return launch<32, L>(ts, a, nblocks, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32>(K, [&](auto k) { return launch<decltype(k)::value, L>(ts, a, nblocks, s); });
 }
 
 int launch_n2_split(int K, int L, bool ts, const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {

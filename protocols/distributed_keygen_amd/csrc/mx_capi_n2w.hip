@@ -1,34 +1,23 @@
 // Wide-geometry (L = 18) instantiations of the N^2-modulus pair kernel (third translation unit).
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_powmod_n2.hpp"
 
 namespace mxw {
 template <int K, bool FR>
 static int launch_form(const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {
-  size_t lds = mx::powmod_n2_lds_bytes<K, LIMBS_PER_LANE_WIDE>(FR);
-  hipLaunchKernelGGL((mx::powmod_n2_kernel<K, LIMBS_PER_LANE_WIDE, LIMB_BITS, FR>), dim3((unsigned)nblocks), dim3(64), lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::powmod_n2_kernel<K, LIMBS_PER_LANE_WIDE, LIMB_BITS, FR>, nblocks, 64, mx::powmod_n2_lds_bytes<K, LIMBS_PER_LANE_WIDE>(FR), s, a);
 }
 // friendly-modulus instances (mx_powmod_n2.hpp) for groups of 4 and 8 lanes — key_length 2048 and 4096, the launches
 // that fill the machine — where the host found LIMB_BITS + 6 bits of room in R (a.friendly)
-template <int K>
-static int launch(const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {
-  if constexpr (K == 4 || K == 8) {
-    if (a.friendly) return launch_form<K, true>(a, nblocks, s);
-  }
-  return launch_form<K, false>(a, nblocks, s);
-}
-
 int launch_n2_wide(int K, const mx::PowmodN2Args& a, int64_t nblocks, hipStream_t s) {
-  switch (K) {
-    case 1: return launch<1>(a, nblocks, s);
-    case 2: return launch<2>(a, nblocks, s);
-    case 4: return launch<4>(a, nblocks, s);
-    case 8: return launch<8>(a, nblocks, s);
-    case 16: return launch<16>(a, nblocks, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16>(K, [&](auto k) {
+    constexpr int KK = decltype(k)::value;
+    if constexpr (KK == 4 || KK == 8) {
+      if (a.friendly) return launch_form<KK, true>(a, nblocks, s);
+    }
+    return launch_form<KK, false>(a, nblocks, s);
+  });
 }
 }  // namespace mxw
 

@@ -1,6 +1,6 @@
 // mx_chacha20_rows: the device random-row generator (mx_chacha.hpp) behind the C ABI (translation unit of its own, built
 // in parallel with the others).
-#include "mx_host.hpp"
+#include "mx_launch.hpp"
 #include "mx_chacha.hpp"
 
 extern "C" int mx_chacha20_rows(const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, uint32_t* d_out,
@@ -21,7 +21,5 @@ extern "C" int mx_chacha20_rows(const uint32_t key[8], const uint32_t nonce[3], 
   a.row_words = row_words;
   a.bits = bits;
   const int64_t groups = (blocks + mx::CHACHA_THREADS - 1) / mx::CHACHA_THREADS;      // <= 2^24
-  hipLaunchKernelGGL(mx::chacha20_rows_kernel, dim3((unsigned)groups), dim3(mx::CHACHA_THREADS), 0, (hipStream_t)stream, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::chacha20_rows_kernel, groups, mx::CHACHA_THREADS, 0, (hipStream_t)stream, a);
 }

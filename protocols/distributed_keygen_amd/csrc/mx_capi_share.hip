@@ -1,5 +1,6 @@
 // mx_share_candidates / mx_shamir_share: additive shares of the prime candidates and their Shamir sharings
 // (mx_share.hpp) behind the C ABI (translation unit of its own, built in parallel with the others).
+#include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_share.hpp"
 
@@ -42,17 +43,6 @@ int64_t share_lds_bytes(int degree) {
   return (int64_t)(64 / K) * (M_t::LDS_WORDS + (int64_t)degree * M_t::S) * 4;
 }
 
-template <int K>
-int launch_share_k(const mx::ShareArgs& a, hipStream_t s) {
-  const int gpw = 64 / K;
-  const int64_t nblocks = (a.batch + gpw - 1) / gpw;
-  const int64_t lds = share_lds_bytes<K>(a.degree);
-  if (lds > 65536 || nblocks > 0x7FFFFFFF) return MX_ERR_SIZE;
-  hipLaunchKernelGGL((mx::shamir_share_kernel<K, LIMBS_PER_LANE, LIMB_BITS>), dim3((unsigned)nblocks), dim3(64), (size_t)lds, s, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
-}
-
 }  // namespace
 
 extern "C" int mx_share_candidates(const uint32_t* d_random, uint32_t* d_out, int64_t count, int prime_length, int first_party,
@@ -65,9 +55,7 @@ extern "C" int mx_share_candidates(const uint32_t* d_random, uint32_t* d_out, in
   a.in_words = (prime_length - 3 + 31) / 32; a.row_words = row_words; a.mod4 = first_party ? 3u : 0u;
   const int64_t nblocks = (count * row_words + mx::CANDIDATE_THREADS - 1) / mx::CANDIDATE_THREADS;
   if (nblocks > 0x7FFFFFFF) return MX_ERR_SIZE;
-  hipLaunchKernelGGL(mx::share_candidates_kernel, dim3((unsigned)nblocks), dim3(mx::CANDIDATE_THREADS), 0, (hipStream_t)stream, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(mx::share_candidates_kernel, nblocks, mx::CANDIDATE_THREADS, 0, (hipStream_t)stream, a);
 }
 
 extern "C" int64_t mx_share_workspace_bytes(int limbs, int n_points) {
@@ -108,14 +96,12 @@ extern "C" int mx_shamir_share(const uint32_t* d_secrets, const uint32_t* d_draw
   a.mod = w; a.rmodn = w + limbs; a.split = w + 2 * limbs; a.xr = w + 3 * limbs;
   a.batch = batch; a.limbs = limbs; a.nblk = geo.nblk; a.degree = degree; a.n_points = n_points;
   a.cw = (bits + 64 + 31) / 32; a.split_bit = bits - 1;
-  switch (geo.K) {
-    case 1: return launch_share_k<1>(a, s);
-    case 2: return launch_share_k<2>(a, s);
-    case 4: return launch_share_k<4>(a, s);
-    case 8: return launch_share_k<8>(a, s);
-    case 16: return launch_share_k<16>(a, s);
-    case 32: return launch_share_k<32>(a, s);
-    case 64: return launch_share_k<64>(a, s);
-  }
-  return MX_ERR_SIZE;
+  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(geo.K, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    const int gpw = 64 / K;
+    const int64_t nblocks = (a.batch + gpw - 1) / gpw;
+    const int64_t lds = share_lds_bytes<K>(a.degree);
+    if (lds > 65536 || nblocks > 0x7FFFFFFF) return MX_ERR_SIZE;
+    return mx_launch(mx::shamir_share_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, nblocks, 64, (size_t)lds, s, a);
+  });
 }

@@ -1,6 +1,6 @@
 // mx_slots_encode / mx_slots_decode: the slot codec (mx_slots.hpp) behind the C ABI (translation unit of its own, built in
 // parallel with the others).
-#include "mx_host.hpp"
+#include "mx_launch.hpp"
 #include "mx_slots.hpp"
 
 using namespace mxh;
@@ -46,9 +46,7 @@ template <typename Kernel>
 int slots_launch(Kernel kernel, const mx::SlotsArgs& a, void* stream) {
   const unsigned groups = (unsigned)((a.outputs + a.rows_per_group - 1) / a.rows_per_group);
   const size_t lds = (size_t)a.rows_per_group * a.lds_stride * 4;
-  hipLaunchKernelGGL(kernel, dim3(groups), dim3(mx::SLOTS_THREADS), lds, (hipStream_t)stream, a);
-  MX_HIP(hipGetLastError());
-  return MX_OK;
+  return mx_launch(kernel, groups, mx::SLOTS_THREADS, lds, (hipStream_t)stream, a);
 }
 
 }  // namespace

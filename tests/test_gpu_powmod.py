@@ -532,3 +532,31 @@ def test_four_wavefront_form_exists_only_where_its_kernel_does(eng):
         finally:
             eng.set_limbs_per_lane(0)
             eng.set_wavefronts_per_group(0)
+
+
+def test_four_wavefront_plan_runs_with_the_pivot_it_was_prepared_with(eng):
+    """The constants of the five-wavefront form (R' = 2^(W h_lo), fold and quotient rows) depend on the pivot h_lo, and the
+    engine caches plans by (n, exponent): mx_powmod_nsquare_prepare_ex records the pivot in bits 8-15 of
+    mx_nsquare_plan.geometries and mx_powmod_nsquare_run takes it from there.  A plan prepared under one setting of the
+    bi_pivot knob and run under another — both directions — is bit for bit CPython pow.  n_bits = 1027: the smallest modulus
+    class with the form (groups of 16 lanes, 39 positions; the library's pivot is 21)."""
+    n_bits = 1027
+    rng = random.Random(1027)
+    n = rng.getrandbits(n_bits) | (1 << (n_bits - 1)) | 1
+    n2 = n * n
+    bases = [0, n2 - 1, rng.randrange(n2)]
+    try:
+        eng.set_limbs_per_lane(3)
+        eng.set_wavefronts_per_group(4)
+        for first, second in ((30, 0), (0, 30)):
+            e = rng.getrandbits(64) | (1 << 63)
+            want = [pow(b, e, n2) for b in bases]
+            eng.debug_knob("bi_pivot", first)
+            assert eng.nsquare_launch_shape(n_bits, len(bases))[4] == 4
+            assert eng.powmod_nsquare_batch(bases, e, n) == want, (first, "prepared and run")      # the plan is cached under `first`
+            eng.debug_knob("bi_pivot", second)
+            assert eng.powmod_nsquare_batch(bases, e, n) == want, (first, second, "cached plan, other knob")
+    finally:
+        eng.debug_knob("bi_pivot", 0)
+        eng.set_limbs_per_lane(0)
+        eng.set_wavefronts_per_group(0)

@@ -34,7 +34,8 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     # mx_nsquare_launch_split, MX_KNOB_GENERIC_LATENCY / MX_KNOB_N2_SPLIT
     # 4.0: mx_set_limbs_per_lane removed (no process-wide launch-shape state), knobs atomic, mx_powmod_nsquare_prepare_ex
     # with MX_PLAN_FIXED_WINDOW; 4.3: wavefronts_per_group 4 (the five-wavefront latency form), MX_KNOB_N2_BIPAIR;
-    # 4.4: mx_nsquare_latency_form
+    # 4.4: mx_nsquare_latency_form; still 4.4: bits 8-15 of mx_nsquare_plan.geometries carry the pivot the plan's five-wavefront
+    # constants were built with (the struct's size and layout are unchanged; 0 there = a plan of an older library)
     assert lib.mx_version() == 404
     assert lib.mx_error_string(-3).decode().startswith("modulus")
 
