@@ -598,6 +598,45 @@ int mx_scan_nsquare_store(const mx_nsquare_plan* plan, const uint32_t* d_rows, i
  * max_entries written; returns their number. */
 int mx_scan_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
 
+/* ---- encrypted sparse matrix products: a public CSR matrix over ciphertexts (ABI 4.4, additions) -----------------
+ *   y_r = bias_r * prod_{t in row r} x_{col[t]} ^ |val[t]|  mod N^2        (a negative weight: the caller hands in the inverse)
+ * as a histogram over windowed digits (csrc/mx_spmm_n2.hpp).  With window w and weights below 2^weight_bits there are
+ * D = ceil(weight_bits / w) digit positions; every non-zero digit d of a term at position p is a weight-1 term of the
+ * segment r * D + p which names the table row of x^d.  The caller builds the index arrays; the library has the two
+ * kernels on either side of mx_histogram_nsquare_run:
+ *   tables: one group of lanes per input writes x^1 .. x^(2^w - 1) in pair form as rows of a histogram row set: entry
+ *           (input i, digit d) is row i * (2^w - 1) + d - 1, the one row follows the last entry, so the result is the
+ *           d_rows (n_rows = n_inputs * (2^w - 1)) of mx_histogram_nsquare_run.  rows_bytes at least what
+ *           mx_spmm_nsquare_workspace_bytes gives for (n_inputs, window).  With window 1 this is the conversion alone.
+ *   horner: d_rows is a row set of n_rows * positions rows (row r * positions + p the product of segment (r, p): the
+ *           output of a run with pair_form_out).  One group of lanes per output row: acc = S[r][positions - 1], then
+ *           for p = positions - 2 .. 0 `window` pair squarings and one pair product by S[r][p]; then one product by
+ *           d_bias_rows[r] — n_rows pair-form rows, e.g. mx_histogram_nsquare_convert of the residues 1 + b_r N — unless
+ *           it is null; n_rows canonical residues in [0, N^2) of limbs2 words (out_bytes at least n_rows * limbs2 * 4),
+ *           NOT fresh ciphertexts.  Trip counts depend on (positions, window) alone.
+ * The shape query needs no GPU: the geometry, the row size, the window and the positions for n_tables tables (the
+ * inputs plus the inverted columns), n_rows output rows and nnz stored terms of weights below 2^weight_bits.  The window
+ * minimises   n_tables (2^w - 2) + nnz ceil(weight_bits / w) + n_rows (ceil(weight_bits / w) - 1) (w + 1)   over
+ * w = 1 .. 6, ties to the smaller w; `window` 1 .. 8 overrides it.  *positions = max(1, ceil(weight_bits / window)).
+ * The chunk of the index arrays is mx_histogram_nsquare_shape's, for the digit terms and n_rows * positions segments.
+ * MX_ERR_ARG for a null pointer, a negative count, n_inputs / n_rows / positions < 1, weight_bits outside 0 .. 63,
+ * positions above 64, a window outside 1 .. 8 (0 .. 8 in the shape query), a row count of 2^31 - 1 or more, a
+ * limbs_per_lane other than 9 or 0, or rows too narrow for N^2; MX_ERR_SIZE outside the narrow geometry (groups of up
+ * to 32 lanes) or beyond one grid; MX_ERR_WORKSPACE for rows_bytes / out_bytes below the sizes above.  Everything is
+ * checked before anything is enqueued. */
+int mx_spmm_nsquare_shape(int n_bits, int64_t n_tables, int64_t n_rows, int64_t nnz, int weight_bits, int limbs_per_lane,
+                          int window, int* lanes, int* limbs_per_lane_out, int* window_out, int* positions,
+                          int64_t* row_bytes);
+int64_t mx_spmm_nsquare_workspace_bytes(int n_bits, int64_t n_inputs, int window, int limbs_per_lane);
+int mx_spmm_nsquare_tables(const mx_nsquare_plan* plan, const uint32_t* d_inputs, int64_t n_inputs, int limbs2, int window,
+                           uint32_t* d_rows, int64_t rows_bytes, int limbs_per_lane, void* stream);
+int mx_spmm_nsquare_horner(const mx_nsquare_plan* plan, const uint32_t* d_rows, int64_t n_rows, int positions, int window,
+                           const uint32_t* d_bias_rows, uint32_t* d_out, int limbs2, int64_t out_bytes, int limbs_per_lane,
+                           void* stream);
+/* The kernel instances mx_spmm_nsquare_tables / _horner can select: (lanes per element, limbs per lane) pairs, at most
+ * max_entries written; returns their number. */
+int mx_spmm_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries);
+
 /* ---- packing: many small plaintexts per ciphertext (ABI 4.4, additions) ------------------------------------------
  *   d_out[j] = prod_{i < slots} d_cts[j * slots + i] ^ (2^(slot_bits * i))  mod N^2,   j < ceil(count / slots)
  * which encrypts sum_i m_i 2^(slot_bits i) when every d_cts[r] encrypts m_r (g = N + 1): one threshold decryption of

@@ -116,6 +116,11 @@ SYMBOLS = {
     "mx_scan_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "mx_scan_nsquare_store": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "mx_scan_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_spmm_nsquare_shape": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, *[POINTER(c_int)] * 4, POINTER(c_int64)]),
+    "mx_spmm_nsquare_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int]),
+    "mx_spmm_nsquare_tables": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "mx_spmm_nsquare_horner": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "mx_spmm_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_pack_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mx_pack_nsquare_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
     "mx_slots_encode": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),

@@ -1264,6 +1264,18 @@ int rows_launch(const mx_nsquare_plan* plan, int limbs2, int limbs_per_lane, int
 }
 }  // namespace
 
+// rows_launch for the entry points that live in a translation unit of their own (mx_capi_n2sp.hip): the lanes and
+// blocks of the geometry, the plan's constant rows and the grid of `groups` groups.
+namespace mxh {
+int narrow_rows_launch(const mx_nsquare_plan* plan, int limbs2, int limbs_per_lane, int64_t groups, int* lanes, int* nblk,
+                       const uint32_t** consts, int64_t* nblocks) {
+  NarrowLaunch o;
+  MX_TRY(rows_launch(plan, limbs2, limbs_per_lane, groups, o));
+  *lanes = o.g.K; *nblk = o.g.nblk; *consts = o.consts; *nblocks = o.blocks(groups);
+  return MX_OK;
+}
+}  // namespace mxh
+
 extern "C" int mx_histogram_nsquare_instances(int* lanes, int* limbs_per_lane, int max_entries) {
   return mx_multiexp_nsquare_instances(lanes, limbs_per_lane, max_entries);      // the same narrow instances
 }

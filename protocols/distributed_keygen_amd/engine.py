@@ -1195,6 +1195,78 @@ class Engine:
         flat = self._download_ints(self._freshened(self._histogram_run_t(x_t, bins_t.to(self.device), n_bins, n), fixed_base))
         return [flat[f * n_bins : (f + 1) * n_bins] for f in range(feats)]
 
+    # ------------------------------------------------------------------ encrypted sparse matrix products (public CSR matrix)
+    def spmm_nsquare_shape(self, n: int, n_tables: int, n_rows: int, nnz: int, weight_bits: int,
+                           window: int = 0) -> Tuple[int, int, int]:
+        """(window, digit positions, row bytes per table entry) of mx_spmm_nsquare_shape: the library's window for
+        `n_tables` tables (the inputs plus the inverted columns), `n_rows` output rows and `nnz` stored terms of weights
+        below 2^weight_bits; ``window`` > 0 overrides it."""
+        k, l, w, positions, row_bytes = self._query("mx_spmm_nsquare_shape", int(n).bit_length(), int(n_tables), int(n_rows),
+                                                    int(nnz), int(weight_bits), 0, int(window),
+                                                    outs=_INTS[:4] + (_ctypes.c_int64,))
+        return w, positions, int(row_bytes)
+
+    def spmm_nsquare_t(self, cts_t, crow_t, col_t, val_t, n: int, bias: Optional[Sequence[int]] = None, window: int = 0,
+                       chunk: int = 0, table_budget_bytes: int = 0):
+        """y_r = (1 + (bias_r mod n) n) * prod_{t in [crow[r], crow[r+1])} cts[col[t]]^val[t]  mod n^2 on the device
+        (csrc/mx_spmm_n2.hpp): the product of a PUBLIC sparse matrix in CSR form with a vector of
+        ciphertexts, as a histogram over the windowed digits of the weights and Horner's rule over the digit positions.
+
+        ``cts_t``: ``[n_in, limbs2]`` rows of residues below n^2; ``crow_t`` ``[R + 1]``, ``col_t`` ``[nnz]`` and signed
+        ``val_t`` ``[nnz]`` (|val| <= 2^63 - 1): integer tensors on the device or the host (lists and numpy arrays are
+        taken too); ``bias``: one plaintext per row or None.  A negative weight uses the inverse of its input (one product
+        tree for all such columns; ValueError like ``pow`` if one has none — under positive weights only, a
+        non-invertible input is legal), duplicate (row, column) entries are terms of their own, a stored 0 is no term, an
+        empty row gives 1 or its bias factor.  Returns ``[R, limbs2]`` canonical residues on the current stream — not
+        fresh ciphertexts.  ``window`` in 1..8 overrides the library's window, ``chunk`` > 0 the terms per piece,
+        ``table_budget_bytes`` > 0 the bytes one stage of tables may take with its index arrays
+        (spmm_plan.TABLE_BUDGET_BYTES): for tests and probes.  ValueError, before any launch, for arrays of another
+        shape or dtype, a crow that does not run from 0 to nnz without decreasing, a column outside [0, n_in), a value
+        of -2^63, a bias of another length, or a modulus the pair kernel refuses.  The planning (digits, tables, sorting,
+        pieces, levels, stages) is spmm_plan.py."""
+        from . import spmm_plan as sp
+
+        n, window, chunk = int(n), int(window), int(chunk)
+        _check_modulus(n)
+        n_in, limbs2 = cts_t.shape
+        _check_rows_n2(n, limbs2)
+        if not 0 <= window <= sp.MAX_WINDOW:
+            raise ValueError(f"window must lie in [0, {sp.MAX_WINDOW}]")
+        if not 0 <= chunk <= sp.hp.MAX_CHUNK:
+            raise ValueError(f"chunk must lie in [0, {sp.hp.MAX_CHUNK}]")
+        crow_t, col_t, val_t = (t.to(self.device) for t in sp.as_matrix((crow_t, col_t, val_t), n_in))
+        sp.check_bias(bias, crow_t.numel() - 1)
+        sp.check_matrix(crow_t, col_t, val_t, n_in)
+        return self._spmm_run_t(cts_t, crow_t, col_t, val_t, n, bias, window, chunk, int(table_budget_bytes))
+
+    def _spmm_run_t(self, cts_t, crow_t, col_t, val_t, n: int, bias=None, window: int = 0, chunk: int = 0,
+                    table_budget_bytes: int = 0):
+        """spmm_nsquare_t for device index tensors that check_matrix has passed (on either side of the upload)."""
+        from . import spmm_plan as sp
+
+        with self.torch.cuda.device(self.device):
+            return sp.spmm(_SpmmBackend(self, n, cts_t.shape[1], n.bit_length()), cts_t.contiguous(), cts_t.shape[0], crow_t,
+                           col_t, val_t, bias, window, chunk, table_budget_bytes)
+
+    @_int_args
+    def ciphertext_spmm_batch(self, cts: Sequence[int], crow, col, val, n: int, bias: Optional[Sequence[int]] = None,
+                              fixed_base=None) -> List[int]:
+        """[(1 + (bias_r mod n) n) * prod(pow(cts[col[t]], val[t], n^2) for t in range(crow[r], crow[r+1])) mod n^2 for r]
+        — the product of the public sparse matrix (crow, col, val) in CSR form (lists, numpy arrays or torch tensors)
+        with the ciphertexts.  ``pow`` with a negative weight is the inverse; an empty row gives 1 or its bias factor."""
+        from . import spmm_plan as sp
+
+        n2, limbs2 = _nsquare(n)
+        vals = cts if isinstance(cts, (list, tuple)) else list(cts)
+        crow_t, col_t, val_t = sp.as_matrix((crow, col, val), len(vals))
+        sp.check_bias(bias, crow_t.numel() - 1)
+        sp.check_matrix(crow_t, col_t, val_t, len(vals))            # every refusal: before anything is uploaded
+        if crow_t.numel() == 1:
+            return []
+        x_t = self._upload_ints(vals, limbs2, n2) if vals else self._empty_rows(limbs2)
+        out_t = self._spmm_run_t(x_t, crow_t.to(self.device), col_t.to(self.device), val_t.to(self.device), n, bias)
+        return self._download_ints(self._freshened(out_t, fixed_base))
+
     # ------------------------------------------------------------------ encrypted prefix sums over series of ciphertexts
     def cumsum_nsquare_t(self, cts_t, lengths, n: int, exclusive: bool = False, reverse: bool = False, chunk: int = 0,
                          table_budget_bytes: int = 0):
@@ -2400,6 +2472,38 @@ class _HistogramBackend(_N2Backend):
         one = self.torch.zeros((count, self.limbs2), dtype=self.torch.int32, device=self.eng.device)
         one[:, 0] = 1
         return one
+
+
+class _SpmmBackend(_HistogramBackend):
+    """spmm_plan.spmm over device rows: the histogram's row sets, conversion and accumulate run, and the two entries of
+    csrc/mx_spmm_n2.hpp."""
+
+    def shape(self, n_tables, n_rows, nnz, weight_bits, window):
+        return self.eng.spmm_nsquare_shape(self.n, n_tables, n_rows, nnz, weight_bits, window)[:2]
+
+    def pool(self, cts_t, plus, minus):
+        parts = []
+        if plus.numel():
+            parts.append(cts_t.index_select(0, plus))
+        if minus.numel():
+            parts.append(self.eng.modinv_t(cts_t.index_select(0, minus), self.n * self.n))      # ValueError without an inverse
+        return parts[0] if len(parts) == 1 else self.torch.cat(parts, dim=0)
+
+    def tables(self, pool_t, lo, hi, window):
+        rows_t = self._row_set((hi - lo) * ((1 << window) - 1))
+        self.eng._call("mx_spmm_nsquare_tables", self.plan.desc, pool_t[lo:hi].data_ptr(), hi - lo, self.limbs2, window,
+                       rows_t.data_ptr(), rows_t.numel() * 4, 0, plans=(self.plan,))
+        return rows_t
+
+    def bias(self, values):
+        return self.bias_rows([int(b) % self.n for b in values])
+
+    def horner(self, rows_t, n_rows, positions, window, bias_rows_t):
+        out_t = self._empty(n_rows)
+        self.eng._call("mx_spmm_nsquare_horner", self.plan.desc, rows_t.data_ptr(), n_rows, positions, window,
+                       bias_rows_t.data_ptr() if bias_rows_t is not None else None, out_t.data_ptr(), self.limbs2,
+                       out_t.numel() * 4, 0, plans=(self.plan,))
+        return out_t
 
 
 class _ScanBackend(_HistogramBackend):

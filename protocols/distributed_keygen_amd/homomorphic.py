@@ -17,6 +17,9 @@ them to many ciphertexts at once:
   * ``histogram``: the product of the ciphertexts of every (feature, bin) for a PUBLIC bin index per feature and
     sample — the per-feature, per-bin sums of encrypted gradients that gradient-boosted trees are built on, grouped
     encrypted statistics by public categories.  Weight-1 products only: no ciphertext needs an inverse;
+  * ``sparse_matmul``: a public sparse matrix in CSR form (arrays the caller already holds, or a torch sparse tensor)
+    times a vector of ciphertexts — the gradient X^T Enc(d) over sparse features, neighbourhood sums over a public
+    adjacency matrix, weighted GROUP BY.  Planned with array operations, however many non-zeros there are;
   * ``cumsum``: the running totals along series of ciphertexts, c_0 c_1 ... c_j for every j — the left and right
     gradient sums of every split threshold straight from ``histogram`` output, cumulative distributions and running
     totals over an encrypted time series, summed-area rows.  One product per element and level, exclusive and
@@ -187,6 +190,24 @@ def histogram(cts: Sequence[Any], bins: Any, n_bins: int, n: Optional[int] = Non
     hp.check_bins(bins_t, count, n_bins, values=False)
     vals, n = _values(cts, n)
     return _engine(engine).ciphertext_histogram_batch(vals, bins_t, int(n_bins), n, **_fresh(randomizer, n, bins_t.shape[0] * int(n_bins)))
+
+
+def sparse_matmul(cts: Sequence[Any], matrix: Any, n: Optional[int] = None, bias: Optional[Sequence[int]] = None,
+                  engine: Any = None, randomizer: Any = None) -> List[int]:
+    """The encrypted A x + b for a PUBLIC sparse matrix A: [(1 + (b_r mod N) N) prod_t c_(col[t])^(val[t]) mod N^2 over
+    the stored terms t of row r, for every row r].  ``matrix`` is a ``(crow, col, val)`` triple in CSR form (nested lists,
+    numpy arrays or torch tensors; signed ``val`` with |val| <= 2^63 - 1) or a torch sparse CSR or COO tensor of an
+    integer dtype with ``len(cts)`` columns (converted by torch's own ``to_sparse_csr``).  A negative weight uses the
+    inverse of its ciphertext (ValueError, as ``neg``, if it has none), duplicate entries are terms of their own, a stored
+    0 contributes nothing, an empty row gives 1 or its bias factor.  ValueError for anything else, before anything is
+    launched; shape and dtype before a ciphertext is read (the values of the matrix are checked once, by the engine)."""
+    from . import spmm_plan as sp
+
+    crow, col, val = sp.as_matrix(matrix, len(cts))
+    rows = crow.numel() - 1
+    sp.check_bias(bias, rows)
+    vals, n = _values(cts, n)
+    return _engine(engine).ciphertext_spmm_batch(vals, crow, col, val, n, bias=bias, **_fresh(randomizer, n, rows))
 
 
 def cumsum(series: Sequence[Any], n: Optional[int] = None, exclusive: bool = False, reverse: bool = False, engine: Any = None,
