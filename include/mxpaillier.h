@@ -762,6 +762,40 @@ int mx_shamir_share(const uint32_t* d_secrets, const uint32_t* d_draws, const ui
                     uint32_t* d_out, const uint32_t* h_mod, int limbs, int64_t batch, void* d_workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* ---- jointly random generators of the biprimality test (ABI 4.4, additions) ----------------------------------------
+ * The generator step of a key-generation round (`__biprime_test_g_generation`, DK:1001-1054) for all survivors of the
+ * sieve at once: `groups` candidate moduli N_c, `group_size` generators each, row c * group_size + k belongs to
+ * generator k of candidate c (csrc/mx_generators.hpp; tools/generators_model.py is the model).  The moduli are DEVICE
+ * rows d_mods [groups][limbs] of at most mod_bits bits, as for mx_powmod_multi_dev (the survivors' moduli stay on the
+ * device from their reconstruction on); they must be odd and >= 3.  h_mods is an optional HOST copy of the same rows:
+ * when it is not NULL every row is checked (MX_ERR_MODULUS for an even row, a row below 3 or one wider than mod_bits);
+ * device rows alone cannot be checked — an even modulus then yields an unspecified residue for its group, never a hang.
+ *
+ * mx_generator_shares: d_out[r] = d_draws[r] mod N_c, canonical.  d_draws is [groups * group_size][cw] with
+ *   cw = ceil((mod_bits + 64) / 32): draws of mod_bits + 64 bits (what mx_chacha20_rows writes for bits = mod_bits + 64,
+ *   row_words = cw), so a share is uniform on [0, N_c) up to a bias below 2^-64; any row of cw words is reduced
+ *   correctly.  d_out is [groups * group_size][limbs].
+ * mx_generator_sum: d_out[r] = sum_j d_shares[j][r] mod N_c, canonical.  d_shares is [n_parties][groups * group_size]
+ *   [limbs]; ANY row of `limbs` words is accepted as a share (N_c itself, unreduced values, 2^(32 limbs) - 1).  d_out has
+ *   the layout mx_jacobi_dev and mx_powmod_multi_dev read.  The shares are added as unreduced columns and reduced once:
+ *   the sum of their parts below 2^(mod_bits - 1), plus a residue below 2 N_c, must stay below the Montgomery radix
+ *   R >= 2^(mod_bits + 4), i.e. (n_parties + 4) 2^(mod_bits - 1) <= 2^(mod_bits + 4), which holds up to 28 parties;
+ *   MX_GEN_MAX_PARTIES is the power of two inside that bound.
+ * Both: two launches on `stream` (the per-modulus constant R^2 mod N_c into the workspace, then the rows), no
+ * synchronisation; control flow and addresses depend on the sizes alone.  groups = 0 or group_size = 0 returns MX_OK
+ * without a launch.  MX_ERR_ARG for a null pointer (other than h_mods), limbs < 1, a negative count, mod_bits outside
+ * [2, 32 * limbs] or n_parties outside [1, MX_GEN_MAX_PARTIES]; MX_ERR_MODULUS as above; MX_ERR_SIZE for mod_bits beyond
+ * the engine's widest modulus, rows wider than the kernel stages (limbs far beyond mod_bits / 32) or more rows than a
+ * launch addresses; MX_ERR_WORKSPACE below mx_generator_workspace_bytes.  A refused call launches nothing. */
+#define MX_GEN_MAX_PARTIES 16
+int64_t mx_generator_workspace_bytes(int limbs, int64_t groups);
+int mx_generator_shares(const uint32_t* d_draws, uint32_t* d_out, const uint32_t* d_mods, const uint32_t* h_mods, int limbs,
+                        int mod_bits, int64_t groups, int64_t group_size, void* d_workspace, int64_t workspace_bytes,
+                        void* stream);
+int mx_generator_sum(const uint32_t* d_shares, int n_parties, uint32_t* d_out, const uint32_t* d_mods, const uint32_t* h_mods,
+                     int limbs, int mod_bits, int64_t groups, int64_t group_size, void* d_workspace, int64_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ class CombinePlan(ctypes.Structure):
 
 
 MX_PLAN_FIXED_WINDOW = 1      # include/mxpaillier.h
+MX_GEN_MAX_PARTIES = 16       # include/mxpaillier.h
 MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
 
 _P4 = [POINTER(c_int)] * 4
@@ -134,6 +135,9 @@ SYMBOLS = {
     "mx_share_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "mx_share_workspace_bytes": (c_int64, [c_int, c_int]),
     "mx_shamir_share": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "mx_generator_workspace_bytes": (c_int64, [c_int, c_int64]),
+    "mx_generator_shares": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "mx_generator_sum": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -7,6 +7,10 @@ Reference: src/tno/mpc/protocols/distributed_keygen/distributed_keygen.py (DK).
                                  p_i, q_i, correct_param)       DK:1056-1108 -> biprime_test_v_calculation[_batch]
     __biprime_test_with_v_i(batched_v_i, modulus, correct_param,
                             party_indices)                      DK:1110-1175 -> biprime_test_with_v_i[_batch]
+    __biprime_test_g_generation(correct_param, index,
+                                candidate_n_list, ...)          DK:1001-1054 -> biprime_test_g_shares_batch (the draws)
+                                                                               and biprime_test_g_sum_batch (the sums);
+                                                                               the exchange between them stays the caller's
 
 The reference wraps the v-values in ``Batched[AdditiveVariable]`` containers (utils.py:301-504);
 here they are the plain lists those containers carry, in the same order.  Argument meaning, result
@@ -112,6 +116,91 @@ def biprime_test_v_calculation(
     return biprime_test_v_calculation_batch([g_values], index, [modulus], [p_i], [q_i], correct_param_biprime, engine)[0]
 
 
+# ------------------------------------------------------------------ DK:1001-1054
+JACOBI_CORRECTION_FACTOR = 4          # DK:60: generators drawn per correctness round (about half have Jacobi symbol 1)
+
+
+def generator_draw_width(moduli: Sequence[int]) -> "tuple[int, int]":
+    """(bits, words) of a generator draw for these moduli: 64 bits more than the widest of them."""
+    bits = max(int(n).bit_length() for n in moduli) + 64
+    return bits, -(-bits // 32)
+
+
+def _check_generator_args(moduli: Sequence[int], group_size: int) -> None:
+    if int(group_size) < 1:
+        raise ValueError("group_size must be at least 1")
+    for n in moduli:
+        if n < 3 or n % 2 == 0:
+            raise ValueError("modulus must be odd and >= 3")
+
+
+def biprime_test_g_shares_batch(moduli: Sequence[int], group_size: int, rng: Any, engine: Any = None) -> List[List[int]]:
+    """This party's additive shares of the jointly random generators (DK:1030-1044), one list of `group_size` per
+    modulus: share k of modulus c is D[c * group_size + k] mod N_c, D the rows of ONE
+    ``rng.rows_t(engine, S * group_size, B + 64, cw)`` (generator_draw_width).  Uniform on [0, N_c) up to a bias below
+    2^-64, where the reference draws on [0, N_c] inclusive — only the sum modulo N_c is ever used, so parties on either
+    path interoperate.  An engine without ``generator_shares_batch`` draws the rows and the reduction is Python's."""
+    moduli = [int(n) for n in moduli]
+    _check_generator_args(moduli, group_size)
+    if rng is None:
+        raise ValueError("a DeviceRng is needed")
+    if not moduli:
+        return []
+    eng = _engine(engine)
+    if hasattr(eng, "generator_shares_batch"):
+        return eng.generator_shares_batch(moduli, group_size, rng)
+    bits, words = generator_draw_width(moduli)
+    draws = eng._download_ints(rng.rows_t(eng, len(moduli) * group_size, bits, words))
+    return [[draws[c * group_size + k] % n for k in range(group_size)] for c, n in enumerate(moduli)]
+
+
+def biprime_test_g_sum_batch(shares: Sequence[Sequence[Sequence[int]]], moduli: Sequence[int], group_size: int,
+                             engine: Any = None) -> List[List[int]]:
+    """The generators (DK:1051-1053): per modulus the sums of the parties' shares modulo it, as canonical residues —
+    `shares` holds one nested list per party.  Any integer is accepted as a share."""
+    moduli = [int(n) for n in moduli]
+    _check_generator_args(moduli, group_size)
+    if len(shares) == 0 or any(len(col) != len(moduli) or any(len(row) != group_size for row in col) for col in shares):
+        raise ValueError("every party needs group_size shares per modulus")
+    if not moduli:
+        return []
+    eng = _engine(engine)
+    if hasattr(eng, "generator_sum_batch"):
+        return eng.generator_sum_batch(list(shares), moduli, group_size)
+    return [[sum(int(col[c][k]) for col in shares) % n for k in range(group_size)] for c, n in enumerate(moduli)]
+
+
+class GeneratorRows:
+    """The generators of a round as ``BiprimeRound.sum_generators`` left them: device rows ``[S * group_size, limbs]`` (or,
+    for an engine without the device forms, nothing) and the group size.  Stands where the reference holds
+    ``list[list[int]]``: ``len()`` is the number of candidates, ``lists()`` downloads the nested ints on first use.
+    Two handles are equal when they were summed from equal share tables — what lets the rounds of parties that share
+    a process merge their v-calculations without comparing device memory."""
+
+    __slots__ = ("engine", "rows", "group_size", "count", "source", "_lists")
+
+    def __init__(self, engine: Any, rows: Any, group_size: int, count: int, source: Any = None, lists: Any = None) -> None:
+        self.engine, self.rows, self.group_size, self.count, self.source, self._lists = engine, rows, int(group_size), int(count), source, lists
+
+    def __len__(self) -> int:
+        return self.count
+
+    def lists(self) -> List[List[int]]:
+        if self._lists is None:
+            self._lists = self.engine._fetched_ints("generators", self.rows, groups=([self.group_size] * self.count, self.group_size))
+        return self._lists
+
+    def __eq__(self, other: Any) -> bool:
+        if not isinstance(other, GeneratorRows):
+            return NotImplemented
+        if self is other:
+            return True
+        return (self.group_size == other.group_size and self.count == other.count and self.source is not None
+                and other.source is not None and (self.source is other.source or self.source == other.source))
+
+    __hash__ = None  # type: ignore[assignment]
+
+
 # ------------------------------------------------------------------ DK:1110-1175
 def _party_column(v_by_party: Sequence[Dict[int, Sequence[int]]], party: int, nslots: int) -> List[int]:
     """All candidates' first `nslots` values of one party as one flat list, short lists padded with zeros (a missing
@@ -215,6 +304,7 @@ class BiprimeRound:
         self.moduli: List[int] = []           # their moduli, same order
         self._mods_rows: Any = None
         self._own: Any = None                 # (party index, v lists as returned, device handle)
+        self._gen: Any = None                 # (generator share lists as returned, their device rows, group size)
 
     def reconstruct_and_sieve(self, shares_by_party: Dict[int, Sequence[int]], prime: int, degree: int,
                               prime_list: Sequence[int], points: Any = None) -> Dict[int, int]:
@@ -226,7 +316,7 @@ class BiprimeRound:
         count = len(shares_by_party[pts[0]])
         if any(len(shares_by_party[i]) != count for i in pts):
             raise ValueError("every party needs one share per candidate")
-        self._mods_rows = self._own = None
+        self._mods_rows = self._own = self._gen = None
         if count == 0:
             self.has_divisor, self.survivors, self.moduli = [], [], []
             return {}
@@ -246,11 +336,49 @@ class BiprimeRound:
         """The result of `other`.reconstruct_and_sieve for a party that was handed the same share table: the survivors
         (and their moduli on the device, read-only) are shared, nothing is computed."""
         self.has_divisor, self.survivors, self.moduli = list(other.has_divisor), list(other.survivors), list(other.moduli)
-        self._mods_rows, self._own = other._mods_rows, None
+        self._mods_rows, self._own, self._gen = other._mods_rows, None, None
         return dict(zip(self.survivors, self.moduli))
 
     def shares_survivors_with(self, other: "BiprimeRound") -> bool:
         return self is other or (self._mods_rows is other._mods_rows and (self.moduli is other.moduli or self.moduli == other.moduli))
+
+    # ---- the generator step (DK:1001-1054), opt-in: patch.install(generator_rng=...) -----------------------------
+    def draw_generator_shares(self, rng: Any, group_size: int) -> List[List[int]]:
+        """This party's shares of the survivors' generators (biprime_test_g_shares_batch: one call on `rng`), as the
+        nested ints the exchange takes; the rows stay on the device for sum_generators."""
+        eng = self.engine
+        self._gen = None
+        fn = getattr(eng, "generator_shares_batch", None)
+        if not self.moduli or fn is None or not _accepts(fn, "keep_rows"):
+            return biprime_test_g_shares_batch(self.moduli, group_size, rng, eng)
+        _check_generator_args(self.moduli, group_size)
+        if rng is None:
+            raise ValueError("a DeviceRng is needed")
+        lists, rows = fn(self.moduli, group_size, rng, mods_rows=self._mods_rows, keep_rows=True)
+        self._gen = (lists, rows, int(group_size))
+        return lists
+
+    def sum_generators(self, shares_by_party: Dict[int, Sequence[Sequence[int]]], index: int) -> "GeneratorRows":
+        """The survivors' generators from every party's shares (``{party index: nested lists}``), summed on the device
+        and left there: a GeneratorRows for v_calculation.  This party's rows are taken from the device only if the
+        exchanged lists are the drawn ones (the rule `verdicts` applies to the v values)."""
+        eng, moduli = self.engine, self.moduli
+        order = sorted(shares_by_party)
+        if not order:
+            raise ValueError("no shares")
+        group_size = self._gen[2] if self._gen is not None else (len(shares_by_party[order[0]][0]) if moduli else 1)
+        source = (moduli, shares_by_party)
+        fn = getattr(eng, "generator_sum_batch", None)
+        if not moduli or fn is None or not _accepts(fn, "keep_rows"):
+            lists = biprime_test_g_sum_batch([shares_by_party[i] for i in order], moduli, group_size, eng)
+            return GeneratorRows(eng, None, group_size, len(moduli), source, lists)
+        columns: List[Any] = [shares_by_party[i] for i in order]
+        if self._gen is not None and self._gen[1] is not None and index in shares_by_party:
+            mine = shares_by_party[index]
+            if mine is self._gen[0] or (len(mine) == len(self._gen[0]) and all(a is b or list(a) == b for a, b in zip(mine, self._gen[0]))):
+                columns[order.index(index)] = self._gen[1]
+        rows = fn(columns, moduli, group_size, mods_rows=self._mods_rows, keep_rows=True)
+        return GeneratorRows(eng, rows, group_size, len(moduli), source)
 
     @staticmethod
     def v_calculation_merged(rounds: Sequence["BiprimeRound"], requests: Sequence[Any]) -> List[List[List[int]]]:
@@ -264,6 +392,9 @@ class BiprimeRound:
             return [[] for _ in rounds]
         if first._mods_rows is None or not hasattr(eng, "biprime_verdict_columns") or not _accepts(eng.biprime_v_batch, "mods_rows"):
             return [r.v_calculation(*q) for r, q in zip(rounds, requests)]
+        handle = g_values if isinstance(g_values, GeneratorRows) and g_values.rows is not None and _accepts(eng.biprime_v_batch, "g_rows") else None
+        if isinstance(g_values, GeneratorRows) and handle is None:
+            g_values = g_values.lists()
         s = len(moduli)
         exps: List[int] = []
         for (gv, index, p_shares, q_shares, kp) in requests:
@@ -271,8 +402,12 @@ class BiprimeRound:
                 raise ValueError("one g list, p share and q share per surviving candidate expected")
             exps.extend(biprime_exponent(index, n, p, q) for n, p, q in zip(moduli, p_shares, q_shares))
         parties = len(rounds)
-        lists, rows = eng.biprime_v_batch(list(g_values) * parties, exps, list(moduli) * parties, keep,
-                                          mods_rows=first._mods_rows.repeated(parties), keep_rows=True)
+        if handle is not None:      # the generators of requests[0], repeated on the device: nothing packed, nothing uploaded
+            lists, rows = eng.biprime_v_batch(None, exps, list(moduli) * parties, keep, mods_rows=first._mods_rows.repeated(parties),
+                                              keep_rows=True, g_rows=(handle.rows.repeat(parties, 1), handle.group_size))
+        else:
+            lists, rows = eng.biprime_v_batch(list(g_values) * parties, exps, list(moduli) * parties, keep,
+                                              mods_rows=first._mods_rows.repeated(parties), keep_rows=True)
         out = []
         for k, (rnd, q) in enumerate(zip(rounds, requests)):
             mine = lists[k * s : (k + 1) * s]
@@ -289,10 +424,20 @@ class BiprimeRound:
         if not moduli:
             return []
         eng = self.engine
+        handle = None
+        if isinstance(g_values, GeneratorRows):       # sum_generators' result: its rows go to the kernels as they are
+            if g_values.rows is not None and self._mods_rows is not None and _accepts(eng.biprime_v_batch, "g_rows"):
+                handle = g_values
+            else:
+                g_values = g_values.lists()
         if self._mods_rows is None or not hasattr(eng, "biprime_verdict_columns"):
             return biprime_test_v_calculation_batch(g_values, index, moduli, p_shares, q_shares, correct_param_biprime, eng)
         exps = [biprime_exponent(index, n, p, q) for n, p, q in zip(moduli, p_shares, q_shares)]
-        lists, rows = eng.biprime_v_batch(g_values, exps, moduli, correct_param_biprime, mods_rows=self._mods_rows, keep_rows=True)
+        if handle is not None:
+            lists, rows = eng.biprime_v_batch(None, exps, moduli, correct_param_biprime, mods_rows=self._mods_rows, keep_rows=True,
+                                              g_rows=(handle.rows, handle.group_size))
+        else:
+            lists, rows = eng.biprime_v_batch(g_values, exps, moduli, correct_param_biprime, mods_rows=self._mods_rows, keep_rows=True)
         self._own = (index, lists, rows)
         return lists
 

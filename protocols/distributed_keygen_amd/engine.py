@@ -1897,6 +1897,149 @@ class Engine:
         vals = self._download_ints(out_t.view(len(points) * batch, limbs))
         return {x: vals[j * batch : (j + 1) * batch] for j, x in enumerate(points)}
 
+    # ------------------------------------------------------------------ jointly random generators (DK:1001-1054)
+    def _generator_operands(self, mods, group_size: int, limbs: Optional[int] = None):
+        """(device moduli rows [S, limbs], host copy or None, max bits, limbs) of the generator entry points.  `mods`: a
+        sequence of ints (checked odd and >= 3, uploaded, and handed to the library a second time as the host rows it
+        checks) or a device (rows, bits) pair; `limbs` defaults to the rows of the widest modulus."""
+        if int(group_size) < 1:
+            raise ValueError("group_size must be at least 1")
+        if _is_device_pair(mods):
+            rows_t, bits = mods[0], int(mods[1])
+            if limbs is not None and rows_t.shape[1] != limbs:
+                raise ValueError("device moduli must have the row width of the operands")
+            if not rows_t.is_contiguous():
+                raise ValueError("contiguous rows expected")
+            if not 2 <= bits <= 32 * rows_t.shape[1]:
+                raise ValueError("modulus wider than the limb rows")
+            return rows_t, None, bits, rows_t.shape[1]
+        mods = [int(m) for m in mods]
+        for m in mods:
+            _check_modulus(m)
+        bits = _limbs.max_bits(mods)
+        limbs = _limbs.limbs_for_bits(bits) if limbs is None else int(limbs)
+        if bits > 32 * limbs:
+            raise ValueError("modulus wider than the limb rows")
+        h_mods = _limbs.pack(mods, limbs)
+        return self.to_device(h_mods), h_mods, bits, limbs
+
+    def generator_shares_t(self, mods, group_size: int, rng=None, draws_t=None, out_t=None):
+        """This party's additive shares of the jointly random generators of a round's biprimality tests
+        (`__biprime_test_g_generation`, DK:1030-1044), for S candidate moduli with `group_size` = G generators each:
+        ``out[c * G + k] = D[c * G + k] mod mods[c]`` as int32 rows ``[S * G, limbs]`` of canonical residues.
+
+        The draws D have B + 64 bits, B the bit length of the widest modulus: ``draws_t`` ``[S * G, cw]`` with
+        cw = ceil((B + 64) / 32), or ONE call ``rng.rows_t(self, S * G, B + 64, cw)`` whose row c * G + k is the draw of
+        generator k of candidate c.  A share is uniform on [0, N_c) up to a bias below 2^-64 (the convention of
+        shamir_share_t and encrypt_fresh_batch).  The reference draws ``randint(0, N_c)`` on [0, N_c] INCLUSIVE; only
+        the sum of the parties' shares modulo N_c is ever used, so parties on either path interoperate.
+
+        ``mods``: a sequence of ints or a device ``(rows, bits)`` pair.  ValueError — nothing launched, no call number
+        taken — for group_size < 1, an even modulus or one below 3, neither or both of `rng` and `draws_t`, or rows of
+        another shape."""
+        group_size = int(group_size)
+        mods_t, h_mods, bits, limbs = self._generator_operands(mods, group_size, None if out_t is None else out_t.shape[-1])
+        groups = mods_t.shape[0]
+        total = groups * group_size
+        cw = (bits + 64 + 31) // 32
+        if (rng is None) == (draws_t is None):
+            raise ValueError("exactly one of rng and draws_t expected")
+        if draws_t is not None and tuple(draws_t.shape) != (total, cw):
+            raise ValueError(f"draws_t must have the shape ({total}, {cw})")
+        if out_t is not None and tuple(out_t.shape) != (total, limbs):
+            raise ValueError(f"out_t must have the shape ({total}, {limbs})")
+        if any(x is not None and not x.is_contiguous() for x in (draws_t, out_t)):
+            raise ValueError("contiguous rows expected")
+        if out_t is None:
+            out_t = self._empty_rows(limbs, total)
+        if total:
+            if draws_t is None:
+                draws_t = rng.rows_t(self, total, bits + 64, cw)
+            self._call("mx_generator_shares", draws_t.data_ptr(), out_t.data_ptr(), mods_t.data_ptr(),
+                       h_mods.ctypes.data if h_mods is not None else None, limbs, bits, groups, group_size,
+                       workspace=("mx_generator_workspace_bytes", limbs, groups))
+        return out_t
+
+    def generator_sum_t(self, shares_t, mods, group_size: int, out_t=None):
+        """The generators themselves (DK:1051-1053, ``AdditiveVariable.reconstruct``): ``out[c * G + k] = sum_j
+        shares[j][c * G + k] mod mods[c]`` as canonical residues, ``[S * G, limbs]`` — the rows biprime_v_t reads.
+        ``shares_t``: ``[parties, S * G, limbs]``; any row is a valid share (N_c itself, unreduced values).  ValueError —
+        nothing launched — for group_size < 1, an even modulus, no party or more than MX_GEN_MAX_PARTIES, or rows of
+        another shape."""
+        group_size = int(group_size)
+        if shares_t.dim() != 3 or not shares_t.is_contiguous():
+            raise ValueError("shares_t must be contiguous rows [parties, S * G, limbs]")
+        parties, total, limbs = shares_t.shape
+        if not 1 <= parties <= _lib.MX_GEN_MAX_PARTIES:
+            raise ValueError(f"1 .. {_lib.MX_GEN_MAX_PARTIES} parties expected")
+        mods_t, h_mods, bits, _ = self._generator_operands(mods, group_size, limbs)
+        groups = mods_t.shape[0]
+        if total != groups * group_size:
+            raise ValueError("shares_t must hold groups * group_size rows per party")
+        if out_t is not None and (tuple(out_t.shape) != (total, limbs) or not out_t.is_contiguous()):
+            raise ValueError(f"out_t must be contiguous rows of the shape ({total}, {limbs})")
+        if out_t is None:
+            out_t = self._empty_rows(limbs, total)
+        if total:
+            self._call("mx_generator_sum", shares_t.data_ptr(), parties, out_t.data_ptr(), mods_t.data_ptr(),
+                       h_mods.ctypes.data if h_mods is not None else None, limbs, bits, groups, group_size,
+                       workspace=("mx_generator_workspace_bytes", limbs, groups))
+        return out_t
+
+    def generator_shares_batch(self, mods: Sequence[int], group_size: int, rng, mods_rows: Any = None, keep_rows: bool = False):
+        """generator_shares_t with the shares as Python ints, one list of `group_size` per modulus (what the reference
+        exchanges, DK:1046-1049).  ``mods_rows``: the handle of exactly these moduli on the device; with ``keep_rows``
+        the result is ``(lists, rows)`` where ``rows`` keeps the shares on the device for generator_sum_batch."""
+        mods = [int(m) for m in mods]
+        group_size = int(group_size)
+        if group_size < 1:
+            raise ValueError("group_size must be at least 1")
+        for m in mods:
+            _check_modulus(m)
+        if not mods:
+            return ([], None) if keep_rows else []
+        limbs = _limbs.limbs_for_bits(_limbs.max_bits(mods))
+        mods_op = mods_rows.operand(self, len(mods), limbs) if mods_rows is not None else mods
+        rows_t = self.generator_shares_t(mods_op, group_size, rng=rng)
+        lists = self._fetched_ints("generator_shares", rows_t, groups=([group_size] * len(mods), group_size))
+        return (lists, rows_t) if keep_rows else lists
+
+    def generator_sum_batch(self, shares: Sequence[Any], mods: Sequence[int], group_size: int, mods_rows: Any = None,
+                            keep_rows: bool = False):
+        """generator_sum_t over Python ints: ``shares`` holds one entry per party, each one list of `group_size` shares per
+        modulus — or the device rows generator_shares_batch kept for that party.  A negative share or one wider than
+        the rows is reduced with ``%`` on the host before packing, so the result is always the reference's
+        ``sum(shares) % N``.  Returns the generators nested per modulus, or with ``keep_rows`` the device rows alone
+        (``[S * G, limbs]``, what biprime_v_t reads: nothing is downloaded)."""
+        mods = [int(m) for m in mods]
+        group_size = int(group_size)
+        if group_size < 1:
+            raise ValueError("group_size must be at least 1")
+        if not 1 <= len(shares) <= _lib.MX_GEN_MAX_PARTIES:
+            raise ValueError(f"1 .. {_lib.MX_GEN_MAX_PARTIES} parties expected")
+        for m in mods:
+            _check_modulus(m)
+        if any(not _is_device_rows(col) and (len(col) != len(mods) or any(len(row) != group_size for row in col)) for col in shares):
+            raise ValueError("every party needs group_size shares per modulus")
+        if not mods:
+            return None if keep_rows else []
+        limbs = _limbs.limbs_for_bits(_limbs.max_bits(mods))
+        total = len(mods) * group_size
+        shares_t = self.torch.empty((len(shares), total, limbs), dtype=self.torch.int32, device=self.device)
+        for j, col in enumerate(shares):
+            if _is_device_rows(col):
+                if tuple(col.shape) != (total, limbs):
+                    raise ValueError("the kept share rows do not belong to these candidates")
+                shares_t[j].copy_(col)
+            else:                      # (a staging buffer per party: the copies are asynchronous)
+                shares_t[j].copy_(self._packed_rows(f"generator_shares_{j}", col, limbs, mods, nested=group_size), non_blocking=True)
+        mods_op = mods_rows.operand(self, len(mods), limbs) if mods_rows is not None else mods
+        g_t = self.generator_sum_t(shares_t, mods_op, group_size)
+        if keep_rows:
+            self.synchronize()         # the staging buffers are free again
+            return g_t
+        return self._fetched_ints("generators", g_t, groups=([group_size] * len(mods), group_size))
+
     @_int_args
     def shamir_reconstruct_sieve_batch(self, columns: Sequence[Sequence[int]], coeffs: Sequence[int], prime: int,
                                        primes: Sequence[int], keep_rows: bool = False):
@@ -2031,25 +2174,33 @@ class Engine:
     @_int_args
     def biprime_v_batch(
         self, g_values: Sequence[Sequence[int]], exps: Sequence[int], mods: Sequence[int], keep: int,
-        mods_rows: Any = None, keep_rows: bool = False,
+        mods_rows: Any = None, keep_rows: bool = False, g_rows: Any = None,
     ):
         """The whole v-calculation of DK:1084-1099 for many candidates on the device: Jacobi symbols of
         all generators, selection of the first `keep` with symbol 1, v = g^exp mod N for those.
         Returns per candidate the list of v values (shorter than `keep` if fewer symbols were 1).
         `mods_rows`: the handle ``shamir_reconstruct_sieve_batch(..., keep_rows=True)`` returned for exactly these
         moduli — they are then not packed and uploaded again.  With ``keep_rows`` the result is
-        ``(lists, rows)`` where ``rows`` keeps this party's v values on the device for ``biprime_verdict_columns``."""
+        ``(lists, rows)`` where ``rows`` keeps this party's v values on the device for ``biprime_verdict_columns``.
+        ``g_rows`` = (device rows ``[groups * group_size, limbs]`` of reduced generators, group_size), what
+        ``generator_sum_batch(..., keep_rows=True)`` returned for these moduli: `g_values` is then not read, and nothing
+        is packed or uploaded for the generators."""
         groups = len(mods)
         if groups == 0:
             return ([], None) if keep_rows else []
         for m in mods:          # the int moduli are passed either way: an even N reconstructed from malformed shares (the
             _check_modulus(m)   # sieve's list starts at 3) must raise here, not reach the Montgomery and Jacobi kernels
-        gsize = max(len(g) for g in g_values)
+        gsize = int(g_rows[1]) if g_rows is not None else max(len(g) for g in g_values)
         if gsize == 0 or keep == 0:
             return ([[] for _ in mods], None) if keep_rows else [[] for _ in mods]
         limbs = _limbs.limbs_for_bits(_limbs.max_bits(mods))
-        # one list per candidate straight into the staging buffer (short lists zero padded: symbol (0/N) = 0, never selected)
-        g_t = self._staged_rows("generators", g_values, limbs, mods, nested=gsize)
+        if g_rows is not None:
+            g_t = g_rows[0]
+            if tuple(g_t.shape) != (groups * gsize, limbs):
+                raise ValueError("the kept generator rows do not belong to these candidates")
+        else:
+            # one list per candidate straight into the staging buffer (short lists zero padded: symbol (0/N) = 0, never selected)
+            g_t = self._staged_rows("generators", g_values, limbs, mods, nested=gsize)
         mods_op = mods_rows.operand(self, groups, limbs) if mods_rows is not None else mods
         v_t, cnt_t = self.biprime_v_t(g_t, mods_op, exps, gsize, keep)
         counts = cnt_t.cpu().numpy()

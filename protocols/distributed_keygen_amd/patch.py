@@ -25,6 +25,20 @@ script uses at scripts/bench_batch_size.py:94-110):
       -> same variables, labels, exchange and sums, with the additive shares of the round's candidates and their three
          Shamir sharings drawn and computed on the device (shamir.generate_pq_batch) instead of one candidate at a time
 
+  DistributedPaillier.__biprime_test_g_generation        :1001-1054    (only with ``generator_rng=``)
+      -> same signature, labels, ``Batched(AdditiveVariable(label="biprime", modulus=N))`` containers, one
+         ``exchange_reconstruct`` under ``f"{msg_id}_g"`` and return type, with this party's shares drawn and reduced on
+         the device (biprime.BiprimeRound.draw_generator_shares) instead of ``batch_g_size`` calls of ``randint`` per
+         candidate, and the sums modulo N taken there too (sum_generators).  The patched ``compute_modulus`` passes its
+         round through, so the generators reach the v-calculation as device rows and are never built as Python ints;
+         the SHARES still cross the exchange as ints, as the reference requires.
+         The shares are a deterministic expansion of the generator's key (``device_rng``: read it before use) AND they
+         are published by the protocol: every party sends its shares to all others, so the keystream of that one call
+         is disclosed by design.  ChaCha20 keeps the other calls of the same key secret all the same — a generator
+         shared with ``share_rng=`` does not leak the prime candidates' shares through the published rows.  A share is
+         uniform on [0, N) up to a bias below 2^-64 where the reference draws on [0, N] inclusive; only the sum modulo
+         N is used, so patched and unpatched parties interoperate.
+
 so ``DistributedPaillier.from_security_parameter()``, ``.decrypt()`` and ``.decrypt_sequence()``
 work unmodified.  ``uninstall()`` restores the originals.  The control plane (pools, message ids,
 share containers) is the reference's and is not re-implemented here.
@@ -102,8 +116,13 @@ def _gpu_key(key: Any, engine: Any) -> GpuPaillierSharedKey:
 
 
 def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = True, leaf: bool = False,
-            linger: float = 0.0, hw_queues: Optional[int] = None, share_rng: Any = None) -> None:
-    """``share_rng``: a ``device_rng.DeviceRng``, off by default.  With one, ``_generate_pq`` draws this party's additive
+            linger: float = 0.0, hw_queues: Optional[int] = None, share_rng: Any = None, generator_rng: Any = None) -> None:
+    """``generator_rng``: a ``device_rng.DeviceRng``, off by default.  With one, ``__biprime_test_g_generation`` draws this
+    party's shares of the jointly random generators on the device (one call on the generator per round), and inside
+    ``compute_modulus`` the generators are summed there and handed to the v-calculation as device rows — see the module
+    docstring for what that means for the generator's key.  Without one the reference's own ``randint`` loop stays.
+
+    ``share_rng``: a ``device_rng.DeviceRng``, off by default.  With one, ``_generate_pq`` draws this party's additive
     shares of the prime candidates and the coefficients of their Shamir sharings on the device and computes all shares
     of a round in ten launches (shamir.py's module docstring: what is drawn, the bias below 2^-64 of a coefficient, and
     that everything is a deterministic expansion of the generator's key — read it and ``device_rng`` before use).
@@ -343,6 +362,24 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
 
     rounds_batcher = _round_coalescers[package] = RoundCoalescer(engine, linger=linger)
 
+    async def generator_step(correct_param_biprime, index, candidate_n_list, party_indices, pool, msg_id, this_round=None):
+        """DK:1028-1053 with the draws and the sums on the device; returns biprime.GeneratorRows.  `this_round`: the
+        round that holds exactly these moduli (on the device), or None for a call from outside compute_modulus."""
+        batch_g_size = correct_param_biprime * biprime.JACOBI_CORRECTION_FACTOR
+        candidate_n_list = [int(n) for n in candidate_n_list]
+        if this_round is None or this_round.moduli != candidate_n_list:
+            this_round = biprime.BiprimeRound(engine)
+            this_round.moduli, this_round.survivors = candidate_n_list, list(range(len(candidate_n_list)))
+        own = this_round.draw_generator_shares(generator_rng, batch_g_size)
+        large_batch_of_gs = []
+        for candidate_n, row in zip(candidate_n_list, own):
+            batched_g_sharing = Batched(AdditiveVariable(label="biprime", modulus=candidate_n), batch_size=batch_g_size)
+            batched_g_sharing.set_share(index, row)
+            large_batch_of_gs.append(batched_g_sharing)
+        await exchange_reconstruct(large_batch_of_gs, index, pool, party_indices, msg_id=f"{msg_id}_g")
+        by_party = {i: [[var.get_share(i) for var in b.variables] for b in large_batch_of_gs] for i in party_indices.values()}
+        return this_round.sum_generators(by_party, index)
+
     async def compute_modulus(
         cls: Any, shares, index, pool, prime_list, party_indices, prime_length, shamir_scheme_t,
         shamir_scheme_2t, correct_param_biprime, session_id, batch_size: int = 1,
@@ -381,10 +418,14 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
             sieved_out += len(has_divisor) - len(survivors)
             if not survivors:
                 continue
-            g_values = await getattr(cls, mangled + "biprime_test_g_generation")(
-                correct_param_biprime, index, [moduli[k] for k in survivors], party_indices, pool,
-                f"{sid}_biprime_test_g_{rounds}",
-            )
+            if generator_rng is not None:      # the generators stay on the device: a handle in place of the nested lists
+                g_values = await generator_step(correct_param_biprime, index, [moduli[k] for k in survivors], party_indices,
+                                                pool, f"{sid}_biprime_test_g_{rounds}", this_round=this_round)
+            else:
+                g_values = await getattr(cls, mangled + "biprime_test_g_generation")(
+                    correct_param_biprime, index, [moduli[k] for k in survivors], party_indices, pool,
+                    f"{sid}_biprime_test_g_{rounds}",
+                )
             # DK:1313-1329 as one launch
             v_lists = await rounds_batcher.v_calculation(
                 this_round, g_values, index, [p_add[k] for k in survivors], [q_add[k] for k in survivors], correct_param_biprime)
@@ -408,6 +449,15 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
                 biprime_rejected += 1
 
     setattr(DP, "compute_modulus", classmethod(compute_modulus))
+
+    # ------------------------------------------------------------------ __biprime_test_g_generation on the device (opt-in)
+    if generator_rng is not None:
+        async def biprime_test_g_generation(cls: Any, correct_param_biprime, index, candidate_n_list, party_indices, pool, msg_id):
+            handle = await generator_step(correct_param_biprime, index, candidate_n_list, party_indices, pool, msg_id)
+            return handle.lists()
+
+        _save(DP, mangled + "biprime_test_g_generation")
+        setattr(DP, mangled + "biprime_test_g_generation", classmethod(biprime_test_g_generation))
 
     # ------------------------------------------------------------------ _generate_pq, shared on the device (opt-in)
     if share_rng is None:
