@@ -19,7 +19,7 @@
 // About 3 divsteps per operand bit are needed (203 batches at 2053 bits); the batch count is bounded,
 // so no input can hang the GPU.  (The formulation follows the posdivsteps Jacobi routine of
 // libsecp256k1's modinv64 module, re-derived here for 30-step batches and 32-bit limbs; the Python
-// model it was validated with against sympy is in tests/test_host_logic.py.)
+// model it was validated with against sympy is in tests/jacobi_model.py.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -113,10 +113,14 @@ __global__ void __launch_bounds__(64) jacobi_kernel(JacobiArgs A) {
   int jac = 0;
   int eta = -1;
   int live = NCH;
-  // ~3.1 divsteps per bit of the modulus are needed (measured over operand sizes and shapes); there is no
-  // proven bound for the all-positive variant, so the batch loop stops at 4.5 per bit and whatever is
-  // not finished by then (nothing, on all inputs tried) is completed by jacobi_fallback_kernel
-  // (A.max_batches = (32 * limbs * 9 / 2) / 30 + 8, set by the launcher)
+  // ~3.1 divsteps per bit of the modulus are needed by random operands; there is no proven bound for the
+  // all-positive variant, so the batch loop stops at 4.5 per bit and whatever is not finished by then is
+  // completed by jacobi_fallback_kernel (A.max_batches = (32 * limbs * 9 / 2) / 30 + 8, set by the launcher).
+  // Random operands never get there; structured ones do: a numerator just below a modulus of the form
+  // 2^k - 3 or 2^k - 1 (n - 1, n - 4: the operands stay close to each other and lose a few bits per batch)
+  // needs 9 to 11 divsteps per bit — 304 batches at 1028 bits, 670 at 2053, 1429 at 4100 against bounds of
+  // 166, 320, 627 (tests/jacobi_model.py: worst_batches) — so for such operands the safety net is the
+  // path that computes the symbol.
   const int max_batches = A.max_batches;
   for (int batch = 0; batch < max_batches; ++batch) {
     if (!__any(!done)) break;
@@ -222,10 +226,11 @@ __global__ void __launch_bounds__(64) jacobi_kernel(JacobiArgs A) {
 }
 
 // Safety net of the divstep kernel: the plain binary algorithm, from the original operands, for the
-// symbols the divstep kernel marked JACOBI_UNFINISHED (none, on all inputs tried: there is no proven
-// step bound for the all-positive divsteps, so the bound of jacobi_kernel is backed by an algorithm
-// that has one).  Launched right after it with the same arguments; a wavefront without a marked
-// symbol returns at once.
+// symbols the divstep kernel marked JACOBI_UNFINISHED (none among random operands; numerators just
+// below a modulus 2^k - 3 or 2^k - 1 and their like, which need two to three times the batch bound:
+// see jacobi_kernel.  There is no proven step bound for the all-positive divsteps, so the bound of
+// jacobi_kernel is backed by an algorithm that has one).  Launched right after it with the same
+// arguments; a wavefront without a marked symbol returns at once.
 //     t <- 1;  while a != 0:
 //         strip the z trailing zero bits of a;  if z odd and n mod 8 in {3,5}: t <- -t
 //         if a < n: swap (a, n); if a = n = 3 (mod 4): t <- -t

@@ -13,6 +13,7 @@ import pytest
 
 from conftest import unhex
 from fake_engine import FakeEngine
+from jacobi_model import posdivsteps_jacobi_model as _posdivsteps_jacobi_model
 from oracle import oracle
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -460,51 +461,6 @@ def test_shamir_mirror_matches_reference_vectors(golden_reconstruct):
             shamir.reconstruct_batch(allp, prime, degree, eng, points=[99] + order)
     assert shamir.reconstruct_batch({1: [], 2: [], 3: []}, 101, 2, eng) == []
     assert shamir.lagrange_coefficients_at_zero([1, 2, 3], 101) == [3, 98, 1]
-
-
-def _posdivsteps_jacobi_model(x: int, n: int, steps: int = 30) -> int:
-    """Python model of csrc/mx_jacobi.hpp: batches of `steps` all-positive divsteps decided from the
-    low 64 bits, a 2x2 matrix per batch applied to the full operands, sign tracked on the low bits."""
-    m64 = (1 << 64) - 1
-    if n == 1:
-        return 1
-    if x == 0 or n % 2 == 0:
-        return 0
-    f, g, eta, jac = n, x, -1, 0
-    for _ in range((n.bit_length() + 31) // 32 * 32 * 4 // steps + 8):
-        u, v, q, r = 1, 0, 0, 1
-        fl, gl, i = f & m64, g & m64, steps
-        while True:
-            t = (gl | (m64 << i)) & m64
-            zeros = (t & -t).bit_length() - 1
-            gl >>= zeros
-            u <<= zeros
-            v <<= zeros
-            eta -= zeros
-            i -= zeros
-            jac ^= zeros & ((fl >> 1) ^ (fl >> 2)) & 1
-            if i == 0:
-                break
-            if eta < 0:
-                eta = -eta
-                fl, gl, u, q, v, r = gl, fl, q, u, r, v
-                jac ^= ((fl & gl) >> 1) & 1
-                mask = (m64 >> (64 - min(eta + 1, i))) & 63
-                w = (fl * gl * (fl * fl - 2)) & mask
-            else:
-                mask = (m64 >> (64 - min(eta + 1, i))) & 15
-                w = (-(fl + (((fl + 1) & 4) << 1)) * gl) & mask
-            gl = (gl + fl * w) & m64
-            q += u * w
-            r += v * w
-        assert max(u, v, q, r) <= 1 << steps
-        f, g = (u * f + v * g) >> steps, (q * f + r * g) >> steps
-        assert f <= n and g <= n
-        if f == 1:
-            return 1 - 2 * (jac & 1)
-        if f == g:
-            return 0
-    raise AssertionError("no convergence")
 
 
 def test_divstep_jacobi_model_matches_sympy():
