@@ -796,6 +796,44 @@ int mx_generator_sum(const uint32_t* d_shares, int n_parties, uint32_t* d_out, c
                      int limbs, int mod_bits, int64_t groups, int64_t group_size, void* d_workspace, int64_t workspace_bytes,
                      void* stream);
 
+/* ---- private-key (CRT) decryption (ABI 4.4, additions) ---------------------------------------------------------------
+ * For the holder of an ordinary Paillier private key, who knows the primes p and q of N (Paillier 1999, section 7; never
+ * the distributed key, whose primes nobody knows).  Per ciphertext c:
+ *     x_p = (c mod p^2)^(p-1) mod p^2     m_p = L_p(x_p) h_p mod p     L_p(x) = (x - 1) / p
+ *     x_q = (c mod q^2)^(q-1) mod q^2     m_q = L_q(x_q) h_q mod q
+ *     m   = m_p + p ((m_q - m_p) p^-1 mod q)
+ * The two modexps are mx_powmod_nsquare_run with plans for (n, exponent) = (p, p - 1) and (q, q - 1) — both moduli are
+ * squares; the entry points here are what stands around them (csrc/mx_crt.hpp; tools/crt_model.py is the model).
+ *
+ * mx_crt_prepare: h_p, h_q, h_hp, h_hq, h_pinv are HOST rows of `limbs` words — the primes, h_p = L_p((N+1)^(p-1) mod
+ *   p^2)^-1 mod p, h_q likewise, and p^-1 mod q (residues; the three are taken modulo their prime).  Only Montgomery
+ *   constants are derived from them: no inverse, no primality test.  limbs2 is the width of the ciphertext rows, at least
+ *   the words of N^2.  The plan block needs mx_crt_plan_bytes(limbs, limbs2) bytes.  limbs_half = the words of the larger
+ *   of p^2 and q^2 and limbs_n = the words of N are reported in the plan.
+ *     MX_ERR_ARG for a null pointer, limbs or limbs2 below 1, p == q, or rows too narrow for N^2; MX_ERR_MODULUS for an even
+ *     p or q or one below 3; MX_ERR_SIZE beyond the engine's widest modulus (or limbs2 far beyond the words of N^2);
+ *     MX_ERR_WORKSPACE for a plan block that is too small.  A refused call launches nothing.
+ * mx_crt_split_run: d_cts [batch][limbs2], ANY value below 2^(32 limbs2) -> d_out [2][batch][limbs_half]: c mod p^2,
+ *   then c mod q^2, canonical; each half is a contiguous block of rows that mx_powmod_nsquare_run takes as it is.
+ * mx_crt_recombine_run: d_xp, d_xq [batch][limbs_half], x_p below p^2 and x_q below q^2 (what the modexps leave) ->
+ *   d_out [batch][out_stride] and d_status [batch]: status bit 0 = x_p is not 1 modulo p, bit 1 = x_q is not 1 modulo q;
+ *   m = 0 where the status is not 0, else m canonical in [0, N).  out_stride >= limbs_n; as for mx_combine_run, a wider
+ *   row receives the status in word [limbs_n] and zeros behind it, and d_status may then be NULL.
+ * Both runs: one launch on `stream`, no workspace, no synchronisation; control flow and addresses depend on the sizes
+ * alone.  MX_ERR_ARG for a null pointer, batch < 1, out_stride below limbs_n or no place for the status; MX_ERR_SIZE for
+ * more rows than a launch addresses. */
+typedef struct mx_crt_plan {
+  const void* d_plan;
+  int64_t plan_bytes;
+  int32_t limbs, limbs2, limbs_half, limbs_n, p_bits, q_bits;
+} mx_crt_plan;
+int64_t mx_crt_plan_bytes(int limbs, int limbs2);
+int mx_crt_prepare(mx_crt_plan* plan, const uint32_t* h_p, const uint32_t* h_q, const uint32_t* h_hp, const uint32_t* h_hq,
+                   const uint32_t* h_pinv, int limbs, int limbs2, void* d_plan, int64_t plan_bytes, void* stream);
+int mx_crt_split_run(const mx_crt_plan* plan, const uint32_t* d_cts, uint32_t* d_out, int64_t batch, void* stream);
+int mx_crt_recombine_run(const mx_crt_plan* plan, const uint32_t* d_xp, const uint32_t* d_xq, uint32_t* d_out, int out_stride,
+                         uint8_t* d_status, int64_t batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

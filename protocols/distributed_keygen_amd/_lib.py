@@ -33,6 +33,15 @@ class CombinePlan(ctypes.Structure):
     ]
 
 
+class CrtPlan(ctypes.Structure):
+    """mx_crt_plan (include/mxpaillier.h)."""
+
+    _fields_ = [
+        ("d_plan", c_void_p), ("plan_bytes", c_int64), ("limbs", ctypes.c_int32), ("limbs2", ctypes.c_int32),
+        ("limbs_half", ctypes.c_int32), ("limbs_n", ctypes.c_int32), ("p_bits", ctypes.c_int32), ("q_bits", ctypes.c_int32),
+    ]
+
+
 MX_PLAN_FIXED_WINDOW = 1      # include/mxpaillier.h
 MX_GEN_MAX_PARTIES = 16       # include/mxpaillier.h
 MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
@@ -138,6 +147,10 @@ SYMBOLS = {
     "mx_generator_workspace_bytes": (c_int64, [c_int, c_int64]),
     "mx_generator_shares": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "mx_generator_sum": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "mx_crt_plan_bytes": (c_int64, [c_int, c_int]),
+    "mx_crt_prepare": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_crt_split_run": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_int64, c_void_p]),
+    "mx_crt_recombine_run": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
 }
 
 
