@@ -834,6 +834,46 @@ int mx_crt_split_run(const mx_crt_plan* plan, const uint32_t* d_cts, uint32_t* d
 int mx_crt_recombine_run(const mx_crt_plan* plan, const uint32_t* d_xp, const uint32_t* d_xq, uint32_t* d_out, int out_stride,
                          uint8_t* d_status, int64_t batch, void* stream);
 
+/* Private-key (CRT) Paillier ENCRYPTION: the noise r^N mod N^2 from half-size modexps, for the party that knows p and q.
+ * Modulo p^2, x -> x^p depends on x mod p only, multiplicatively, so
+ *     rho_p = r^N mod p^2 = ((r mod p)^(q mod (p-1)) mod p)^p mod p^2,     rho_q likewise,
+ * and for randomness of the key holder's own, rho_p = (D mod p^2)^p, rho_q = (D mod q^2)^q of one draw D is a uniform N-th
+ * residue.  The modexps are mx_powmod_shared_lpl modulo p and q and mx_powmod_nsquare_run with plans for (n, exponent) =
+ * (p, p) and (q, q); the entry points here are what stands around them (csrc/mx_crt_enc.hpp; tools/crt_model.py:
+ * CrtEncPlan is the model).  mx_crt_split_run reduces a draw or a ciphertext modulo the squares.
+ *
+ * mx_crt_enc_prepare: h_p, h_q are HOST rows of `limbs` words, h_p2inv = (p^2)^-1 mod q^2 one of 2 * limbs words.  Only
+ *   Montgomery constants are derived from them.  limbs_r is the width of the randomness rows of mx_crt_prime_split_run
+ *   (any width from 1).  The plan block needs mx_crt_enc_plan_bytes(limbs, limbs_r) bytes.  limbs_half, limbs_n and
+ *   limbs2 = the words of N^2 are reported in the plan.
+ *     MX_ERR_ARG for a null pointer, limbs or limbs_r below 1 or p == q; MX_ERR_MODULUS for an even p or q or one below 3;
+ *     MX_ERR_SIZE beyond the engine's widest modulus (or limbs_r beyond what a lane group stages); MX_ERR_WORKSPACE for a
+ *     plan block that is too small.  A refused call launches nothing.
+ * mx_crt_prime_split_run: d_rows [batch][limbs_r], ANY value below 2^(32 limbs_r) -> d_out [2][batch][limbs_half]: r mod p,
+ *   then r mod q, canonical, zero above the prime's words — rows that mx_powmod_shared_lpl takes as they are and whose
+ *   results mx_powmod_nsquare_run takes as they are.
+ * mx_crt_lift_run: d_rho_p, d_rho_q [batch][limbs_half], below p^2 and q^2 -> d_out [batch][out_stride], canonical in
+ *   [0, N^2):  c = v rho with rho = CRT(rho_p, rho_q) and v = 1 + m N for d_messages [batch][message_stride] (m below N,
+ *   message_stride >= limbs_n), v = the ciphertext whose halves d_halves [2][batch][limbs_half] holds (what
+ *   mx_crt_split_run gives), or v = 1 when both are NULL.  d_status [batch]: bit 0 = rho_p is 0, bit 1 = rho_q is 0 (p or q
+ *   divides the randomness); the row is zero then.  out_stride >= limbs2; as for mx_crt_recombine_run a wider row receives
+ *   the status in word [limbs2] and zeros behind it, and d_status may then be NULL.
+ * Both runs: one launch on `stream`, no workspace, no synchronisation; control flow and addresses depend on the sizes
+ * and the mode alone.  MX_ERR_ARG for a null pointer, batch < 1, both d_messages and d_halves, message rows narrower than
+ * N, out_stride below limbs2 or no place for the status; MX_ERR_SIZE for more rows than a launch addresses. */
+typedef struct mx_crt_enc_plan {
+  const void* d_plan;
+  int64_t plan_bytes;
+  int32_t limbs, limbs_r, limbs2, limbs_half, limbs_n, p_bits, q_bits;
+} mx_crt_enc_plan;
+int64_t mx_crt_enc_plan_bytes(int limbs, int limbs_r);
+int mx_crt_enc_prepare(mx_crt_enc_plan* plan, const uint32_t* h_p, const uint32_t* h_q, const uint32_t* h_p2inv, int limbs,
+                       int limbs_r, void* d_plan, int64_t plan_bytes, void* stream);
+int mx_crt_prime_split_run(const mx_crt_enc_plan* plan, const uint32_t* d_rows, uint32_t* d_out, int64_t batch, void* stream);
+int mx_crt_lift_run(const mx_crt_enc_plan* plan, const uint32_t* d_rho_p, const uint32_t* d_rho_q, const uint32_t* d_messages,
+                    int message_stride, const uint32_t* d_halves, uint32_t* d_out, int out_stride, uint8_t* d_status,
+                    int64_t batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

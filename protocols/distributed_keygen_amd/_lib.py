@@ -42,6 +42,16 @@ class CrtPlan(ctypes.Structure):
     ]
 
 
+class CrtEncPlan(ctypes.Structure):
+    """mx_crt_enc_plan (include/mxpaillier.h)."""
+
+    _fields_ = [
+        ("d_plan", c_void_p), ("plan_bytes", c_int64), ("limbs", ctypes.c_int32), ("limbs_r", ctypes.c_int32),
+        ("limbs2", ctypes.c_int32), ("limbs_half", ctypes.c_int32), ("limbs_n", ctypes.c_int32), ("p_bits", ctypes.c_int32),
+        ("q_bits", ctypes.c_int32),
+    ]
+
+
 MX_PLAN_FIXED_WINDOW = 1      # include/mxpaillier.h
 MX_GEN_MAX_PARTIES = 16       # include/mxpaillier.h
 MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
@@ -151,6 +161,10 @@ SYMBOLS = {
     "mx_crt_prepare": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_crt_split_run": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_int64, c_void_p]),
     "mx_crt_recombine_run": (c_int, [POINTER(CrtPlan), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_crt_enc_plan_bytes": (c_int64, [c_int, c_int]),
+    "mx_crt_enc_prepare": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_crt_prime_split_run": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_int64, c_void_p]),
+    "mx_crt_lift_run": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -4,6 +4,7 @@
 #include "mx_launch.hpp"
 #include "mx_upload.hpp"
 #include "mx_crt.hpp"
+#include "mx_crt_host.hpp"
 
 namespace {
 
@@ -25,21 +26,6 @@ int crt_shape(int p_bits, int q_bits, int limbs2, int limbs_half, CrtShape& sh) 
   if (limbs2 > 2 * sh.split.K * sh.split.L + 6 || limbs_half > 2 * sh.recombine.K * sh.recombine.L + 6) return MX_ERR_SIZE;
   return MX_OK;
 }
-
-bool same_words(const u32* a, const u32* b, int limbs) {
-  for (int i = 0; i < limbs; ++i) if (a[i] != b[i]) return false;
-  return true;
-}
-
-// v 2^m mod r for any v of `limbs` words, as a row of rw words at dst (r has at most rw words)
-void scaled_residue(u32* dst, const u32* v, const u32* r, int limbs, int m) {
-  std::vector<u32> q(limbs), t(limbs + 1, 0u);
-  divmod_words(q.data(), t.data(), v, limbs, r, limbs);
-  shl_mod(t, r, limbs, m);
-  std::memcpy(dst, t.data(), (size_t)limbs * 4);
-}
-
-int64_t crt_blocks(int64_t batch, int K) { return (batch + 64 / K - 1) / (64 / K); }
 
 }  // namespace
 

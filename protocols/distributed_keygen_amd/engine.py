@@ -161,6 +161,7 @@ class Engine:
         self._n2_plans: "OrderedDict[Tuple[int, int, bool], _Plan]" = OrderedDict()
         self._combine_plans: "OrderedDict[Tuple[int, int, int], _Plan]" = OrderedDict()
         self._crt_plans: "OrderedDict[Tuple[int, int, int], _Plan]" = OrderedDict()
+        self._crt_enc_plans: "OrderedDict[Tuple[int, int, int], _Plan]" = OrderedDict()
         self._fixed_base_tables: "OrderedDict[Tuple[int, int, int, int], FixedBaseTable]" = OrderedDict()
         self._side_streams: List[Any] = []     # chunked int-level batches (_pipelined): streams verified concurrent
         self._side_streams_capped = False      # the process has fewer concurrent queues than chunks were wanted
@@ -169,7 +170,7 @@ class Engine:
         self._priority_aux = False             # small kernels on a high-priority companion stream (set_priority_aux)
         self._aux: Dict[int, Any] = {}         # stream -> its companion
         self._split_streams: Dict[int, Any] = {}   # stream -> the companion that runs the second part of a split launch
-        self._crt_streams: Dict[int, Any] = {}     # stream -> the companion that runs the modexp modulo q^2 of a private decryption
+        self._crt_streams: Dict[int, Any] = {}     # stream -> the companion that runs the chain modulo q^2 of a private decryption or encryption
         self._cu_streams: Dict[int, List[Any]] = {}    # cu_slice_streams: n -> its streams
         self._side_stream_pool: List[Any] = []     # every chunk stream ever created (_chunk_streams probes them again)
         self._capped_calls = 0                     # requests since _side_streams_capped was set (RECHECK_CAPPED_EVERY)
@@ -2363,6 +2364,26 @@ class Engine:
                                            stride, status_t.data_ptr() if status_t is not None else None, batch, plans=(plan,)))
         return out_t if packed else (out_t, status_t)
 
+    def _crt_pair(self, run_p, run_q, side_by_side: bool):
+        """(run_p(), run_q()) — the chains modulo p^2 and q^2 of a private-key operation: one after the other on the
+        caller's stream, or run_q on the caller's companion stream (one per stream, kept) beside run_p, joined again
+        before this returns.  Plans are prepared by the caller, on its stream, before the fan-out."""
+        if not side_by_side:
+            return run_p(), run_q()
+        torch = self.torch
+        cur = torch.cuda.current_stream(self.device)
+        side = self._crt_streams.get(int(cur.cuda_stream))
+        if side is None:
+            with torch.cuda.device(self.device):
+                side = self._crt_streams[int(cur.cuda_stream)] = torch.cuda.Stream(device=self.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            xq_t = run_q()
+        xp_t = run_p()
+        cur.wait_stream(side)
+        xq_t.record_stream(cur)                    # allocated on the companion, read by the caller's stream from here on
+        return xp_t, xq_t
+
     @_int_args
     def private_decrypt_t(self, cts_t, p: int, q: int, packed: bool = False, side_by_side: bool = True):
         """Decryption with the primes of N: cts_t int32 [batch, limbs2] -> (plaintext rows, status) as crt_recombine_t
@@ -2375,24 +2396,10 @@ class Engine:
         half_t = self.crt_split_t(cts_t, p, q)
         if batch == 0:
             return self.crt_recombine_t(half_t[0], half_t[1], p, q, packed=packed, limbs2=limbs2)
-        if not side_by_side:
-            xp_t = self.powmod_nsquare_t(half_t[0], p, p - 1)
-            xq_t = self.powmod_nsquare_t(half_t[1], q, q - 1)
-        else:
-            torch = self.torch
-            self.nsquare_plan(p, p - 1)            # both prepared on the caller's stream, before the fan-out
-            self.nsquare_plan(q, q - 1)
-            cur = torch.cuda.current_stream(self.device)
-            side = self._crt_streams.get(int(cur.cuda_stream))
-            if side is None:
-                with torch.cuda.device(self.device):
-                    side = self._crt_streams[int(cur.cuda_stream)] = torch.cuda.Stream(device=self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                xq_t = self.powmod_nsquare_t(half_t[1], q, q - 1)
-            xp_t = self.powmod_nsquare_t(half_t[0], p, p - 1)
-            cur.wait_stream(side)
-            xq_t.record_stream(cur)                # allocated on the companion, read by the caller's stream from here on
+        self.nsquare_plan(p, p - 1)                # both prepared on the caller's stream, before the fan-out
+        self.nsquare_plan(q, q - 1)
+        xp_t, xq_t = self._crt_pair(lambda: self.powmod_nsquare_t(half_t[0], p, p - 1),
+                                    lambda: self.powmod_nsquare_t(half_t[1], q, q - 1), side_by_side)
         return self.crt_recombine_t(xp_t, xq_t, p, q, packed=packed, limbs2=limbs2)
 
     @_int_args
@@ -2406,6 +2413,211 @@ class Engine:
         rows_t, status_t = self.private_decrypt_t(self._staged_rows("in", cts, limbs2, n2), p, q)
         status = status_t.cpu().numpy()
         return self._fetched_ints("messages", rows_t), [not bool(s) for s in status]
+
+    # ------------------------------------------------------------------ private-key (CRT) encryption
+    @_int_args
+    def crt_enc_plan(self, p: int, q: int, limbs_r: int = 0) -> _Plan:
+        """The plan of the encryption with the primes p, q of N (mx_crt_enc_prepare), cached next to crt_plan: Montgomery
+        constants of p and q for randomness rows of `limbs_r` words (0 = the words of N) and of p^2 and q^2 for the lift.
+        (p^2)^-1 mod q^2 is computed here, on the host; ValueError for a pair that is no key (private_key.crt_constants)."""
+        from .private_key import crt_constants
+
+        limbs_r = int(limbs_r) or _limbs.limbs_for(p * q)
+        key = (p, q, limbs_r)
+        plan = self._cached(self._crt_enc_plans, key)
+        if plan is not None:
+            return plan
+        crt_constants(p, q)
+        if limbs_r < 1:
+            raise ValueError("randomness rows need a word")
+        limbs = _limbs.limbs_for(max(p, q))
+        rows = [_limbs.pack_one(p, limbs), _limbs.pack_one(q, limbs), _limbs.pack_one(pow(p * p, -1, q * q), 2 * limbs)]
+        desc = _lib.CrtEncPlan()
+        nbytes = _lib.check(self.lib.mx_crt_enc_plan_bytes(limbs, limbs_r), "mx_crt_enc_plan_bytes")
+        return self._prepare(self._crt_enc_plans, key, nbytes, "mx_crt_enc_prepare",
+                             (desc, *(r.ctypes.data for r in rows), limbs, limbs_r), lambda *made: _Plan(desc, *made))
+
+    @_int_args
+    def crt_prime_split_t(self, rows_t, p: int, q: int):
+        """rows_t int32 [batch, limbs_r] (any value of that width) -> int32 [2, batch, limbs_half]: the rows modulo p, then
+        modulo q, zero above the prime; ``out[0]`` and ``out[1]`` are the contiguous operands of
+        ``powmod_shared_t(.., p, q mod (p-1))`` and ``(.., q, p mod (q-1))``, whose results ``powmod_nsquare_t(.., p, p)``
+        and ``(.., q, q)`` take as they are."""
+        batch, limbs_r = rows_t.shape
+        plan = self.crt_enc_plan(p, q, limbs_r)
+        out_t = self.torch.empty((2, batch, plan.desc.limbs_half), dtype=self.torch.int32, device=self.device)
+        if batch:
+            rows_t = rows_t.contiguous()
+            self._small(lambda: self._call("mx_crt_prime_split_run", plan.desc, rows_t.data_ptr(), out_t.data_ptr(), batch, plans=(plan,)))
+        return out_t
+
+    @_int_args
+    def crt_lift_t(self, rho_p_t, rho_q_t, p: int, q: int, messages_t=None, halves_t=None, packed: bool = False):
+        """The noise halves rho_p_t, rho_q_t int32 [batch, limbs_half] (below p^2 and q^2) -> (rows int32 [batch,
+        limbs(N^2)], status uint8 [batch]) of c = v rho mod N^2, canonical, with rho = CRT(rho_p, rho_q) and
+        v = 1 + m N for ``messages_t`` [batch, >= limbs(N)] (m below N), v = the ciphertexts whose halves ``halves_t``
+        [2, batch, limbs_half] holds (crt_split_t), or v = 1 for neither.  Status bit 0 = rho_p is 0, bit 1 = rho_q is 0
+        — p or q divides the randomness — and the row is zero then.  With ``packed=True`` ONE tensor [batch,
+        limbs(N^2) + 1] whose last word is the status."""
+        plan = self.crt_enc_plan(p, q)
+        batch, half = rho_p_t.shape
+        if half != plan.desc.limbs_half or tuple(rho_q_t.shape) != (batch, half):
+            raise ValueError("noise rows of the wrong shape")
+        if messages_t is not None and halves_t is not None:
+            raise ValueError("a message or a ciphertext, not both")
+        if messages_t is not None and (messages_t.dim() != 2 or messages_t.shape[0] != batch or messages_t.shape[1] < plan.desc.limbs_n):
+            raise ValueError("one message row per noise row expected, no narrower than N")
+        if halves_t is not None and tuple(halves_t.shape) != (2, batch, half):
+            raise ValueError("ciphertext halves of the wrong shape")
+        limbs2 = plan.desc.limbs2
+        stride = limbs2 + 1 if packed else limbs2
+        out_t = self.torch.empty((batch, stride), dtype=self.torch.int32, device=self.device)
+        status_t = None if packed else self.torch.empty(batch, dtype=self.torch.uint8, device=self.device)
+        if batch:
+            rho_p_t, rho_q_t = rho_p_t.contiguous(), rho_q_t.contiguous()
+            m_t = None if messages_t is None else messages_t.contiguous()
+            h_t = None if halves_t is None else halves_t.contiguous()
+            self._small(lambda: self._call(
+                "mx_crt_lift_run", plan.desc, rho_p_t.data_ptr(), rho_q_t.data_ptr(), m_t.data_ptr() if m_t is not None else None,
+                m_t.shape[1] if m_t is not None else 0, h_t.data_ptr() if h_t is not None else None, out_t.data_ptr(), stride,
+                status_t.data_ptr() if status_t is not None else None, batch, plans=(plan,)))
+        return out_t if packed else (out_t, status_t)
+
+    def _powmod_prime_t(self, rows_t, prime: int, exp: int):
+        """rows^exp mod `prime` for a SECRET exponent (q mod (p-1) or p mod (q-1): whoever learns one factors N).
+        ``powmod_shared_t`` follows a sliding-window schedule built on the host from the exponent's bits — the number and
+        order of squarings and multiplications is a function of the exponent, in the class of the pair kernel's default
+        tape.  With set_fixed_window(True) the launch goes through ``powmod_multi_t`` with one group instead: the generic
+        kernel's fixed-window ladder, one multiplication behind every `window` squarings whatever the digit, so that the
+        sequence of operations depends on the exponent's bit length only (the table row a window reads is still chosen
+        by its digit).  Same results bit for bit."""
+        if self._fixed_window:
+            return self.powmod_multi_t(rows_t, [prime], [exp], rows_t.shape[0])
+        return self.powmod_shared_t(rows_t, prime, exp)
+
+    def _private_noise_halves(self, count: int, p: int, q: int, randomness_t, rng, draws_t, side_by_side: bool):
+        """(rho_p rows, rho_q rows, the randomness rows they came from) for `count` ciphertexts: from the caller's r
+        (``randomness_t``: prime split, a modexp modulo each prime, one modulo each square with the prime as exponent) or
+        from fresh draws D of bits(N) + 64 bits (``rng``, or ``draws_t`` given: crt_split_t and the second modexp only)."""
+        if (randomness_t is not None) + (rng is not None) + (draws_t is not None) != 1:
+            raise ValueError("exactly one of randomness_t, rng and draws_t expected")
+        self.nsquare_plan(p, p)                    # both prepared on the caller's stream, before the fan-out
+        self.nsquare_plan(q, q)
+        if randomness_t is not None:
+            if randomness_t.dim() != 2 or randomness_t.shape[0] != count:
+                raise ValueError("one randomness row per ciphertext expected")
+            kept_t = randomness_t
+            mod_t = self.crt_prime_split_t(randomness_t, p, q)
+            e_p, e_q = q % (p - 1), p % (q - 1)
+            run_p = lambda: self.powmod_nsquare_t(self._powmod_prime_t(mod_t[0], p, e_p), p, p)
+            run_q = lambda: self.powmod_nsquare_t(self._powmod_prime_t(mod_t[1], q, e_q), q, q)
+        else:
+            if draws_t is None:
+                n = p * q
+                bits = n.bit_length() + 64
+                draws_t = self.random_rows_t(rng, count, bits, max(_limbs.limbs_for(n * n), (bits + 31) // 32))
+            elif draws_t.dim() != 2 or draws_t.shape[0] != count:
+                raise ValueError("one draw per ciphertext expected")
+            kept_t = draws_t
+            mod_t = self.crt_split_t(draws_t, p, q)
+            run_p = lambda: self.powmod_nsquare_t(mod_t[0], p, p)
+            run_q = lambda: self.powmod_nsquare_t(mod_t[1], q, q)
+        if count == 0:
+            return mod_t[0], mod_t[1], kept_t
+        rho_p_t, rho_q_t = self._crt_pair(run_p, run_q, side_by_side)
+        return rho_p_t, rho_q_t, kept_t
+
+    @_int_args
+    def private_noise_t(self, count: int, p: int, q: int, randomness_t=None, rng=None, draws_t=None, side_by_side: bool = True,
+                        packed: bool = False):
+        """`count` rows of noise rho = r^N mod N^2 under the key with the primes p, q, and their status, as crt_lift_t
+        returns them — for callers who keep a pool and multiply it in later (mulmod_t).  The randomness as in
+        private_encrypt_t."""
+        rho_p_t, rho_q_t, _ = self._private_noise_halves(count, p, q, randomness_t, rng, draws_t, side_by_side)
+        return self.crt_lift_t(rho_p_t, rho_q_t, p, q, packed=packed)
+
+    @_int_args
+    def private_encrypt_t(self, messages_t, p: int, q: int, randomness_t=None, rng=None, draws_t=None, side_by_side: bool = True,
+                          packed: bool = False, return_randomness: bool = False):
+        """Paillier encryption by the holder of the primes of N: messages_t int32 [batch, >= limbs(N)] (m below N) ->
+        (ciphertext rows [batch, limbs(N^2)], status) as crt_lift_t returns them, c = (1 + m N) r^N mod N^2.  Exactly one
+        source of randomness:
+
+        ``randomness_t`` [batch, any width]: the caller's r (only r mod N matters).  r^N modulo p^2 is
+            ((r mod p)^(q mod (p-1)) mod p)^p — crt_prime_split_t, ``powmod_shared_t(.., p, q mod (p-1))`` (with
+            set_fixed_window: ``powmod_multi_t`` with one group, _powmod_prime_t) and ``powmod_nsquare_t(.., p, p)`` — and
+            likewise modulo q^2: bit for bit the ciphertext of ``encrypt_batch``.
+        ``rng`` (device_rng.DeviceRng): one draw D of bits(N) + 64 bits per ciphertext; rho_p = (D mod p^2)^p and
+            rho_q = (D mod q^2)^q are a uniform N-th residue (up to 2^-64) — the reference's distribution — at the cost
+            of the second modexp alone.
+        ``draws_t`` [batch, >= limbs(N^2)]: the draws D given, for reproducible runs.
+
+        A row whose randomness shares a factor with N has a non-zero status and is zero.  `side_by_side`: the chain
+        modulo q^2 on the companion stream of private_decrypt_t beside the one modulo p^2; False keeps everything on the
+        caller's stream — 1.9 x slower for a lone ciphertext, and the faster call at ONE measured point: the caller's r at
+        key_length 4096 and 10 000 rows (67.6 against 85.6 ms).  Both modes beat ``encrypt_batch``'s route at every
+        measured point (1.3-2.4 x with the caller's r, 1.9-3.9 x fresh).  ``return_randomness``: a third result, the rows of r or D.  The modexps use this engine's plan
+        cache and launch shapes.  All four exponents — p, q, q mod (p-1), p mod (q-1) — are secrets: by default every
+        modexp follows a sliding-window schedule that is a function of its exponent's bits; set_fixed_window(True)
+        reaches all four (the pair kernel's fixed-window tape and the generic kernel's fixed-window ladder), after which
+        the sequence of operations depends on the exponents' bit lengths only, the table rows read still on their
+        digits."""
+        batch = messages_t.shape[0]
+        rho_p_t, rho_q_t, kept_t = self._private_noise_halves(batch, p, q, randomness_t, rng, draws_t, side_by_side)
+        out = self.crt_lift_t(rho_p_t, rho_q_t, p, q, messages_t=messages_t, packed=packed)
+        if not return_randomness:
+            return out
+        return (out, kept_t) if packed else (*out, kept_t)
+
+    @_int_args
+    def private_randomize_t(self, cts_t, p: int, q: int, randomness_t=None, rng=None, draws_t=None, side_by_side: bool = True,
+                            packed: bool = False, return_randomness: bool = False):
+        """Re-randomisation c r^N mod N^2 by the holder of the primes: cts_t int32 [batch, >= limbs(N^2)] (any value of
+        that width) -> (rows, status); the ciphertext enters through its halves (crt_split_t), everything else as
+        private_encrypt_t."""
+        batch = cts_t.shape[0]
+        halves_t = self.crt_split_t(cts_t, p, q)
+        rho_p_t, rho_q_t, kept_t = self._private_noise_halves(batch, p, q, randomness_t, rng, draws_t, side_by_side)
+        out = self.crt_lift_t(rho_p_t, rho_q_t, p, q, halves_t=halves_t, packed=packed)
+        if not return_randomness:
+            return out
+        return (out, kept_t) if packed else (*out, kept_t)
+
+    def _private_batch(self, run_t, rows_t, count: int, p: int, q: int, randomness, rng, return_randomness: bool):
+        if (randomness is None) == (rng is None):
+            raise ValueError("exactly one of randomness and rng expected")
+        if randomness is not None and len(randomness) != count:
+            raise ValueError("one randomness per value expected")
+        if count == 0:
+            return ([], [], []) if return_randomness else ([], [])
+        n = p * q
+        r_t = None if randomness is None else self._staged_rows("randomness", randomness, _limbs.limbs_for(n), n)
+        out_t, status_t, kept_t = run_t(rows_t(), p, q, randomness_t=r_t, rng=rng, return_randomness=True)
+        status = status_t.cpu().numpy()
+        out = self._fetched_ints("out", out_t), [not bool(s) for s in status]
+        if not return_randomness:
+            return out
+        return (*out, list(randomness) if randomness is not None else self._download_ints(kept_t))
+
+    @_int_args
+    def private_encrypt_batch(self, messages: Sequence[int], p: int, q: int, randomness: Optional[Sequence[int]] = None, rng=None,
+                              return_randomness: bool = False):
+        """(ciphertexts, ok) of the `messages` (ints, taken modulo N: negative ones are their residues) under the key with
+        the primes p, q — private_encrypt_t with page-locked staging both ways.  Exactly one of ``randomness`` (one r per
+        message, taken modulo N) and ``rng``; ok[e] is False, and the ciphertext 0, where the randomness shares a factor
+        with N.  ``return_randomness``: a third result, the r given or the draws D of the fresh mode."""
+        n = p * q
+        return self._private_batch(self.private_encrypt_t, lambda: self._staged_rows("in", messages, _limbs.limbs_for(n), n),
+                                   len(messages), p, q, randomness, rng, return_randomness)
+
+    @_int_args
+    def private_randomize_batch(self, ciphertexts: Sequence[int], p: int, q: int, randomness: Optional[Sequence[int]] = None,
+                                rng=None, return_randomness: bool = False):
+        """(c r^N mod N^2 for every ciphertext, ok) — private_randomize_t at the int level; ciphertexts are taken modulo
+        N^2, everything else as private_encrypt_batch."""
+        n2, limbs2 = _nsquare(p * q)
+        return self._private_batch(self.private_randomize_t, lambda: self._staged_rows("in", ciphertexts, limbs2, n2),
+                                   len(ciphertexts), p, q, randomness, rng, return_randomness)
 
     # ------------------------------------------------------------------ biprimality verdict
     def biprime_verdict_t(self, v_t, mods, pass_t=None):

@@ -28,6 +28,24 @@ longer prime — so a q^2 that is wider than p^2 can never exceed "the R of p^2"
                  d = m_q + 2 q - a              in (0, 4 q)
                  t = mont(d, p^-1 R1 mod q)     = (m_q - m_p) p^-1, < 2 q, made canonical
              m = m_p + p t: a plain product and an add, canonical in [0, N) because m_p < p and t <= q - 1.
+
+Private-key ENCRYPTION (csrc/mx_crt_enc.hpp).  Z*_{p^2} = C_{p-1} x C_p and x -> x^p mod p^2 depends on
+x mod p only, multiplicatively, so the reference's randomiser r^N mod N^2 is, modulo p^2,
+        rho_p = ((r mod p)^(q mod (p-1)) mod p)^p mod p^2,   rho_q likewise
+— one modexp modulo p and one modulo p^2 with the exponent p — and a key holder's own randomness needs the second only:
+rho_p = (D mod p^2)^p.  Around these modexps stand (CrtEncPlan):
+
+  prime split  the split above with the primes in place of their squares and the radix of ITS launch: Rp = 2^rp with
+             rp >= max(bits(p), bits(q), 16 limbs_r) + 4 for randomness rows of limbs_r words (any value of that width).
+  lift       R = 2^r2 with r2 >= 2 max(bits(p), bits(q)) + 4, lane groups that hold a half.  Per prime square P, with the
+             factor v in front of the noise (a message row m < N, a ciphertext half v < P, or nothing):
+                 a = mont(m, N R^2 mod P) + (R mod P)   = (1 + m N) R,  < 3 P < R      (m < N <= R / 16)
+                 a = mont(v, R^2 mod P)                 = v R,          < 2 P
+                 c_P = mont(a, rho_P)                   = v rho_P,      < 2 P          (rho_P < P; a < R)
+             c_p is made canonical (a summand of the result), c_q stays lazy.  Garner modulo Q = q^2 as above:
+                 a' = mont(c_p, R mod Q), < 2 Q;   d = c_q + 2 Q - a' in (0, 4 Q);   t = mont(d, (p^2)^-1 R mod Q), canonical
+             c = c_p + p^2 t by a plain product, canonical in [0, N^2).  status bit 0: rho_p = 0, bit 1: rho_q = 0 — p or q
+             divides the randomness — and the row is zero then.
 """
 
 from __future__ import annotations
@@ -163,6 +181,188 @@ class CrtPlan:
         return self.recombine(pow(cp, self.p - 1, self.p * self.p), pow(cq, self.q - 1, self.q * self.q))
 
 
+class CrtEncPlan:
+    """What mx_crt_enc_prepare derives from (p, q) and the width of the randomness rows: the constants of the prime split
+    and of the lift (module docstring), and the two exponents of the modexps modulo the primes."""
+
+    def __init__(self, p: int, q: int, limbs_r: int = 0) -> None:
+        if p % 2 == 0 or q % 2 == 0 or p < 3 or q < 3 or p == q:
+            raise ValueError("two different odd primes are needed")
+        self.p, self.q, self.n = p, q, p * q
+        self.n2 = self.n * self.n
+        self.limbs_n, self.limbs2 = limbs_for(self.n), limbs_for(self.n2)
+        self.limbs_r = limbs_r or self.limbs_n
+        self.limbs_half = max(limbs_for(p * p), limbs_for(q * q))
+        prime_bits = max(p.bit_length(), q.bit_length())
+        self.e_p, self.e_q = q % (p - 1), p % (q - 1)
+        assert self.e_p > 0 and self.e_q > 0            # p - 1 is even and q an odd prime: p - 1 never divides q
+        # prime split
+        self.split_bit = 16 * self.limbs_r
+        self.ks, nblk_s = geometry(max(prime_bits, self.split_bit))
+        self.rp = W * L * nblk_s
+        assert self.limbs_r <= 2 * self.ks * L + 6 and limbs_for(max(p, q)) <= 2 * self.ks * L + 6
+        self.split_rows = [(r, pow(2, self.split_bit + self.rp, r), pow(2, 2 * self.rp, r)) for r in (p, q)]
+        # lift
+        self.kl, self.nblk = geometry(2 * prime_bits)
+        self.r2 = W * L * self.nblk
+        assert self.nblk <= self.kl and max(self.limbs_half, self.limbs_n) <= 2 * self.kl * L + 6
+        big_r = 1 << self.r2
+        self.lift_rows = [(sq, self.n * big_r * big_r % sq, big_r % sq, big_r * big_r % sq) for sq in (p * p, q * q)]
+        self.p2inv_r = pow(p * p, -1, q * q) * big_r % (q * q)
+
+    # ---- crt_split_kernel over the primes
+    def prime_split(self, row: int) -> Tuple[int, int]:
+        assert 0 <= row < 1 << (32 * self.limbs_r)
+        rp_val = 1 << self.rp
+        lo, hi = row & ((1 << self.split_bit) - 1), row >> self.split_bit
+        assert lo < rp_val >> 4 and hi < rp_val >> 4
+        out = []
+        for r, k_cut, k_r2 in self.split_rows:
+            assert rp_val >= 16 * r and k_cut < r and k_r2 < r
+            h, _ = mont(hi, k_cut, r, self.rp)
+            assert h < 2 * r
+            t = lo + h
+            assert t < rp_val
+            u, _ = mont(t, k_r2, r, self.rp)
+            assert u < 2 * r
+            v, _ = mont(u, 1, r, self.rp)
+            assert v <= r
+            out.append(v - r if v >= r else v)
+        return out[0], out[1]
+
+    # ---- crt_lift_kernel
+    def _times_noise(self, half: int, rho: int, m, v) -> int:
+        """v rho modulo the square `half` holds, lazy (< 2 P): v = 1 + m N for a message row, the half v, or 1."""
+        sq, k_nr2, k_r, k_r2 = self.lift_rows[half]
+        big_r = 1 << self.r2
+        assert big_r >= 16 * sq and 0 <= rho < sq
+        if m is not None:
+            assert 0 <= m < self.n and self.n <= big_r >> 4
+            a, _ = mont(m, k_nr2, sq, self.r2)
+            assert a < 2 * sq
+            a += k_r
+            assert a < 3 * sq < big_r
+        elif v is not None:
+            assert 0 <= v < sq
+            a, _ = mont(v, k_r2, sq, self.r2)
+            assert a < 2 * sq
+        else:
+            return rho
+        c, _ = mont(a, rho, sq, self.r2)
+        assert c < 2 * sq
+        return c
+
+    def lift(self, rho_p: int, rho_q: int, m=None, halves=None) -> Tuple[int, int]:
+        """(c, status) for the noise (rho_p, rho_q) and at most one of a message m < N and a pair of ciphertext halves."""
+        assert m is None or halves is None
+        p2, q2 = self.p * self.p, self.q * self.q
+        status = (1 if rho_p == 0 else 0) | (2 if rho_q == 0 else 0)
+        cp = self._times_noise(0, rho_p, m, None if halves is None else halves[0])
+        cq = self._times_noise(1, rho_q, m, None if halves is None else halves[1])
+        cp = cp - p2 if cp >= p2 else cp                     # canonical: a summand of the result
+        big_r = 1 << self.r2
+        assert cp < p2 <= big_r >> 4 and cq < 2 * q2
+        a, _ = mont(cp, self.lift_rows[1][2], q2, self.r2)
+        assert a < 2 * q2 and (a - cp) % q2 == 0
+        d = cq + 2 * q2 - a
+        assert 0 < d < 4 * q2 < big_r
+        t, _ = mont(d, self.p2inv_r, q2, self.r2)
+        assert t < 2 * q2
+        t = t - q2 if t >= q2 else t
+        c = cp + p2 * t
+        assert 0 <= c < self.n2 and c.bit_length() <= W * L * (self.nblk + self.kl)
+        return (0, status) if status else (c, 0)
+
+    # ---- the routes
+    def noise_of_r(self, r: int) -> Tuple[int, int]:
+        """(rho_p, rho_q) of the caller's r: the prime split, a modexp modulo each prime, one modulo each square."""
+        p, q = self.p, self.q
+        rp, rq = self.prime_split(r)
+        return pow(pow(rp, self.e_p, p), p, p * p), pow(pow(rq, self.e_q, q), q, q * q)
+
+    def noise_of_draw(self, draw: int) -> Tuple[int, int]:
+        """(rho_p, rho_q) of a fresh draw D: (D mod p^2)^p and (D mod q^2)^q."""
+        p, q = self.p, self.q
+        return pow(draw % (p * p), p, p * p), pow(draw % (q * q), q, q * q)
+
+    def encrypt(self, m: int, r: int) -> Tuple[int, int]:
+        return self.lift(*self.noise_of_r(r), m=m % self.n)
+
+
+def formula_lift(p: int, q: int, rho_p: int, rho_q: int, m=None, halves=None) -> Tuple[int, int]:
+    """The lift on Python ints with `%`: (c, status)."""
+    n, p2, q2 = p * q, p * p, q * q
+    status = (1 if rho_p == 0 else 0) | (2 if rho_q == 0 else 0)
+    if status:
+        return 0, status
+    vp, vq = (1, 1) if m is None and halves is None else ((1 + m * n) % p2, (1 + m * n) % q2) if halves is None else halves
+    cp, cq = vp * rho_p % p2, vq * rho_q % q2
+    return cp + p2 * ((cq - cp) * pow(p2, -1, q2) % q2), 0
+
+
+def edge_randomness(p: int, q: int, limbs_r: int, rng: random.Random) -> List[int]:
+    n = p * q
+    top = 1 << (32 * limbs_r)
+    return [v % top for v in (0, 1, p, q, n - 1, n, top - 1, 7 * p, 5 * q, rng.getrandbits(32 * limbs_r), rng.randrange(1, n))]
+
+
+def enc_check(p: int, q: int, seed: int = 5, extra_words: int = 0) -> int:
+    """The encryption model against `%`, `pow` and the formulas for one key; returns the number of values checked."""
+    rng = random.Random(seed)
+    n, p2, q2 = p * q, p * p, q * q
+    n2 = n * n
+    plan = CrtEncPlan(p, q, limbs_for(n) + extra_words)
+    count = 0
+    for r in edge_randomness(p, q, plan.limbs_r, rng):
+        assert plan.prime_split(r) == (r % p, r % q)
+        count += 1
+    # r^N through the two short chains, bit for bit
+    r0 = rng.randrange(2, n)
+    for r in (1, 2, n - 1, r0, r0 + 3 * n):
+        if r >= 1 << (32 * plan.limbs_r):
+            continue
+        rho = plan.noise_of_r(r)
+        assert plan.lift(*rho) == (pow(r, n, n2), 0)
+        for m in (0, 1, n - 1, rng.randrange(n)):
+            assert plan.encrypt(m, r) == ((1 + m * n) * pow(r, n, n2) % n2, 0)
+        count += 1
+    # the lift on directed noise, all three modes
+    small, big = (p2, q2) if p2 < q2 else (q2, p2)
+    noise = [(1, 1), (p2 - 1, q2 - 1), (rng.randrange(1, p2), rng.randrange(1, q2)), (p2 - 1, 1), (1, q2 - 1),
+             (p2 - 1 if p2 > q2 else rng.randrange(1, p2), 1),      # rho_p above q^2 in the swapped order
+             (small - 1, 1), (p2 - 2, 2)]                           # rho_q below c_p mod q^2: the negative difference
+    for rho_p, rho_q in noise:
+        for m in (None, 0, 1, n - 1, rng.randrange(n)):
+            assert plan.lift(rho_p, rho_q, m=m) == formula_lift(p, q, rho_p, rho_q, m=m)
+        c = rng.randrange(n2)
+        halves = (c % p2, c % q2)
+        want = c * formula_lift(p, q, rho_p, rho_q)[0] % n2
+        assert plan.lift(rho_p, rho_q, halves=halves) == (want, 0) == formula_lift(p, q, rho_p, rho_q, halves=halves)
+        count += 1
+    for rho_p, rho_q, st in ((0, 1, 1), (1, 0, 2), (0, 0, 3), (0, q2 - 1, 1)):
+        for m in (None, 5):
+            assert plan.lift(rho_p, rho_q, m=m) == (0, st)
+        count += 1
+    for r, st in ((0, 3), (7 * p, 1), (5 * q, 2)):
+        assert plan.encrypt(3, r) == (0, st)
+        count += 1
+    # fresh draws: a uniform N-th residue — its lambda-th power is 1, the ciphertext decrypts, and r comes back
+    lam = (p - 1) * (q - 1)
+    for _ in range(3):
+        draw = rng.getrandbits(n.bit_length() + 64)
+        rho, st = plan.lift(*plan.noise_of_draw(draw))
+        if st:
+            continue
+        assert pow(rho, lam, n2) == 1
+        m = rng.randrange(n)
+        c, _ = plan.lift(*plan.noise_of_draw(draw), m=m)
+        assert c == (1 + m * n) * rho % n2 and lambda_decrypt(c, p, q) == m
+        r = pow(rho, pow(n, -1, lam), n)
+        assert pow(r, n, n2) == rho
+        count += 1
+    return count
+
+
 def formula_decrypt(c: int, p: int, q: int) -> Tuple[int, int]:
     """The formulas of the docstring on Python ints with `%`: (m, status)."""
     n = p * q
@@ -253,4 +453,5 @@ if __name__ == "__main__":
     for pb, qb in ((64, 67), (67, 64), (66, 66), (30, 101), (101, 30), (512, 515), (515, 512), (1025, 1026), (700, 261), (5, 9)):
         p_, q_ = key_of_bits(pb, qb)
         print(f"primes of {pb} and {qb} bits: {check(p_, q_)} values agree (rows as wide as N^2), "
-              f"{check(p_, q_, extra_words=3)} with rows 3 words wider")
+              f"{check(p_, q_, extra_words=3)} with rows 3 words wider; encryption {enc_check(p_, q_)} and "
+              f"{enc_check(p_, q_, extra_words=3)}")
