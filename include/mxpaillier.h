@@ -874,6 +874,34 @@ int mx_crt_lift_run(const mx_crt_enc_plan* plan, const uint32_t* d_rho_p, const 
                     int message_stride, const uint32_t* d_halves, uint32_t* d_out, int out_stride, uint8_t* d_status,
                     int64_t batch, void* stream);
 
+/* ---- the strong-pseudoprime (Miller-Rabin) test over a batch of candidates (ABI 4.4, additions) ----------------------
+ * For the party that makes or vets an ordinary private key: `groups` odd candidates n_c >= 3 as DEVICE rows d_cands
+ * [groups][limbs] of at most mod_bits bits, of any mix of lengths; n_c - 1 = 2^s d with d odd (csrc/mx_mr.hpp;
+ * tools/mr_model.py is the model).  h_cands is an optional HOST copy of the same rows, checked as for mx_generator_shares
+ * (MX_ERR_MODULUS for an even row, a row below 3 or one wider than mod_bits); unchecked device rows that are even yield an
+ * unspecified verdict, never a hang or an access outside the rows.
+ *
+ * mx_mr_split: d_d [groups][limbs] = d, d_s [groups] = s (1 <= s < mod_bits).
+ * mx_mr_tail:  the witness loop of `group_size` rounds per candidate.  d_x0 [groups * group_size][limbs] holds
+ *   b^d mod n_c, canonical — what mx_powmod_multi_dev leaves for the bases d_bases (same shape, canonical residues), the
+ *   moduli d_cands and the exponents d_d — and d_s the s of mx_mr_split.  d_pass[c * group_size + k] = 1 iff the round
+ *   passes: b == 0 (a vacuous round), x0 == 1, x0 == n_c - 1, or x0^(2^i) == n_c - 1 for an i in [1, s).  The loop of a
+ *   wavefront is as long as the largest s among its rows.
+ * mx_mr_base2: d_pass[c] = the verdict of the round to the base 2, from the candidate alone: one squaring and one
+ *   selected doubling per bit of mod_bits, no table; the sequence of operations depends on mod_bits and, for the
+ *   comparisons of the last steps, on the largest s of a wavefront.
+ * All three: one launch on `stream`, no workspace, no synchronisation; addresses depend on the sizes alone.  groups = 0 or
+ * group_size = 0 returns MX_OK without a launch.  MX_ERR_ARG for a null pointer (other than h_cands), limbs < 1, a negative
+ * count or mod_bits outside [2, 32 * limbs]; MX_ERR_MODULUS as above; MX_ERR_SIZE for mod_bits beyond the engine's widest
+ * modulus, rows wider than the kernel stages (limbs far beyond mod_bits / 32) or more rows than a launch addresses.  A
+ * refused call launches nothing. */
+int mx_mr_split(const uint32_t* d_cands, const uint32_t* h_cands, uint32_t* d_d, int32_t* d_s, int limbs, int mod_bits,
+                int64_t groups, void* stream);
+int mx_mr_tail(const uint32_t* d_x0, const uint32_t* d_bases, const int32_t* d_s, uint8_t* d_pass, const uint32_t* d_cands,
+               const uint32_t* h_cands, int limbs, int mod_bits, int64_t groups, int64_t group_size, void* stream);
+int mx_mr_base2(const uint32_t* d_cands, const uint32_t* h_cands, uint8_t* d_pass, int limbs, int mod_bits, int64_t groups,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,9 @@ SYMBOLS = {
     "mx_crt_enc_prepare": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_crt_prime_split_run": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_int64, c_void_p]),
     "mx_crt_lift_run": (c_int, [POINTER(CrtEncPlan), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_mr_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "mx_mr_tail": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p]),
+    "mx_mr_base2": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
 }
 
 

@@ -2236,6 +2236,148 @@ class Engine:
         out = self.sieve_t(self.to_device(_limbs.pack(candidates, limbs)), primes)
         return [bool(x) for x in out.cpu().numpy()]
 
+    # ------------------------------------------------------------------ Miller-Rabin and the prime search (primes.py)
+    def _mr_candidates(self, cands_t, bits: Optional[int] = None, above: int = 3, checked: bool = False) -> Tuple[int, int, int]:
+        """(rows, limbs, bits) of candidate rows for the strong-pseudoprime kernels.  ValueError — before anything of this
+        library is launched — for rows of another shape, `bits` outside [2, 32 * limbs], an even candidate or one below
+        `above` (a small host constant); device rows are read for that with two reductions unless the caller made the
+        rows itself (`checked`)."""
+        torch = self.torch
+        if not _is_device_rows(cands_t) or cands_t.dim() != 2 or cands_t.dtype != torch.int32 or not cands_t.is_contiguous():
+            raise ValueError("candidates must be contiguous int32 device rows [S, limbs]")
+        rows, limbs = cands_t.shape
+        if limbs < 1:
+            raise ValueError("candidates must have at least one word")
+        bits = 32 * limbs if bits is None else int(bits)
+        if not 2 <= bits <= 32 * limbs:
+            raise ValueError("bits must lie in [2, 32 * limbs]")
+        if rows and not checked:
+            low = cands_t[:, 0]
+            small = (low >= 0) & (low < above)
+            if limbs > 1:
+                small &= ~(cands_t[:, 1:] != 0).any(dim=1)
+            word, rest = bits >> 5, bits & 31
+            wide = torch.zeros_like(small)
+            if rest:                                     # the bits of the top word above `bits`, then the words above it
+                wide |= ((cands_t[:, word].to(torch.int64) & 0xFFFFFFFF) >> rest) != 0
+                word += 1
+            if word < limbs:
+                wide |= (cands_t[:, word:] != 0).any(dim=1)
+            if bool(((low & 1) == 0).any()) or bool(small.any()) or bool(wide.any()):
+                raise ValueError(f"candidates must be odd, at least {above} and of at most `bits` bits")
+        return rows, limbs, bits
+
+    def mr_split_t(self, cands_t, bits: Optional[int] = None, _checked: bool = False):
+        """n - 1 = 2^s d, d odd, for S odd candidates n >= 3 as int32 rows ``[S, limbs]`` (of any mix of bit lengths):
+        ``(d_t [S, limbs], s_t int32 [S])`` (mx_mr_split, csrc/mx_mr.hpp).  ValueError — nothing launched — for an even
+        candidate, one below 3 or rows of another shape."""
+        rows, limbs, bits = self._mr_candidates(cands_t, bits, checked=_checked)
+        d_t = self._empty_rows(limbs, rows)
+        s_t = self.torch.empty(rows, dtype=self.torch.int32, device=self.device)
+        if rows:
+            self._call("mx_mr_split", cands_t.data_ptr(), None, d_t.data_ptr(), s_t.data_ptr(), limbs, bits, rows)
+        return d_t, s_t
+
+    def miller_rabin_t(self, cands_t, bases_t, group_size: int, out_t=None, bits: Optional[int] = None, _checked: bool = False):
+        """The strong-pseudoprime test of S candidates to `group_size` = G bases each: uint8 ``[S * G]``, 1 where the
+        round of candidate c to the base ``bases_t[c * G + k]`` passes.  ``bases_t``: canonical residues ``[S * G,
+        limbs]``, for example ``generator_shares_t((cands_t, bits), G, rng)``; a base that is 0 modulo its candidate
+        tests nothing and passes, 1 and n - 1 pass by themselves.  Three launches: mr_split_t, the generic modexp
+        b^d mod n with one modulus and one exponent per group (powmod_multi_t), and the witness loop (mx_mr_tail).
+        ``bits``: the bit length of the widest candidate, 32 * limbs when not given.  ValueError — nothing launched —
+        for an even candidate, one below 3, group_size < 1 or rows of another shape."""
+        group_size = int(group_size)
+        if group_size < 1:
+            raise ValueError("group_size must be at least 1")
+        rows, limbs, bits = self._mr_candidates(cands_t, bits, checked=_checked)
+        total = rows * group_size
+        if not _is_device_rows(bases_t) or tuple(bases_t.shape) != (total, limbs) or not bases_t.is_contiguous():
+            raise ValueError(f"bases_t must be contiguous rows of the shape ({total}, {limbs})")
+        if out_t is not None and (tuple(out_t.shape) != (total,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
+            raise ValueError(f"out_t must be contiguous uint8 of the shape ({total},)")
+        if out_t is None:
+            out_t = self.torch.empty(total, dtype=self.torch.uint8, device=self.device)
+        if total:
+            d_t, s_t = self.mr_split_t(cands_t, bits, _checked=True)
+            x0_t = self.powmod_multi_t(bases_t, (cands_t, bits), (d_t, bits), group_size)
+            self._call("mx_mr_tail", x0_t.data_ptr(), bases_t.data_ptr(), s_t.data_ptr(), out_t.data_ptr(), cands_t.data_ptr(),
+                       None, limbs, bits, rows, group_size)
+        return out_t
+
+    def miller_rabin_base2_t(self, cands_t, bits: Optional[int] = None, out_t=None, _checked: bool = False):
+        """The strong-pseudoprime test to the base 2 from the candidates alone: uint8 ``[S]`` (mx_mr_base2: one launch,
+        one squaring and one selected doubling per bit of `bits`, no table — primes.py has the side-channel note).
+        ``bits``: the bit length of the widest candidate, 32 * limbs when not given.  ValueError — nothing launched —
+        for an even candidate, one below 3 or rows of another shape."""
+        rows, limbs, bits = self._mr_candidates(cands_t, bits, checked=_checked)
+        if out_t is not None and (tuple(out_t.shape) != (rows,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
+            raise ValueError(f"out_t must be contiguous uint8 of the shape ({rows},)")
+        if out_t is None:
+            out_t = self.torch.empty(rows, dtype=self.torch.uint8, device=self.device)
+        if rows:
+            self._call("mx_mr_base2", cands_t.data_ptr(), None, out_t.data_ptr(), limbs, bits, rows)
+        return out_t
+
+    def probable_prime_t(self, cands_t, bits: int, rounds: int, rng, _checked: bool = False):
+        """uint8 ``[S]``: 1 where the odd candidate (above primes.SIEVE_BOUND, at most `bits` bits) is a probable prime.
+        Three stages, each on the rows the one before left, compacted by indexing in between: the sieve by the odd
+        primes below primes.SIEVE_BOUND (it flags such a prime itself as well — ``primes.is_probable_prime_batch``
+        decides small values on the host), the base 2 (miller_rabin_base2_t), and `rounds` rounds to random bases drawn
+        by `rng` (ONE ``generator_shares_t`` draw of survivors * rounds rows, none when nothing is left), ANDed per
+        candidate.  A prime always passes; a composite passes with probability at most 4^-rounds.  ValueError —
+        nothing launched — for rounds < 1, an even or too small candidate or rows of another shape."""
+        from . import primes as _primes
+
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        rows, limbs, bits = self._mr_candidates(cands_t, bits, above=_primes.SIEVE_BOUND, checked=_checked)
+        torch = self.torch
+        out_t = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        if not rows:
+            return out_t
+        left = torch.nonzero(self.sieve_t(cands_t, _primes.sieve_primes()) == 0).flatten()
+        if left.numel():
+            left = left[self.miller_rabin_base2_t(cands_t[left].contiguous(), bits, _checked=True) != 0]
+        if left.numel():
+            kept_t = cands_t[left].contiguous()
+            bases_t = self.generator_shares_t((kept_t, bits), rounds, rng=rng)
+            passed = self.miller_rabin_t(kept_t, bases_t, rounds, bits=bits, _checked=True)
+            out_t[left] = passed.view(-1, rounds).min(dim=1).values
+        return out_t
+
+    def prime_search_t(self, count: int, bits: int, rng, rounds: int = 64, batch: Optional[int] = None):
+        """`count` random probable primes of exactly `bits` bits as rows ``[count, limbs]``: draw `batch` rows of `bits`
+        bits from `rng`, set the two top bits and bit 0 (the product of two such primes has exactly 2 * bits bits), run
+        probable_prime_t, keep the primes in draw order, and draw again while there are fewer than `count`.
+
+        The default `batch` (primes.default_batch): primes have a share of at least 2 / (bits ln 2) among such odd
+        numbers, so a batch holds about batch * 2 / (bits ln 2) of them, Poisson distributed; the default is the
+        smallest multiple of 64 for which a batch falls short of `count` with probability at most 2 %.  ValueError —
+        nothing launched — for count < 0, bits < 16 or rounds < 1."""
+        from . import primes as _primes
+
+        count, bits, rounds = int(count), int(bits), int(rounds)
+        if count < 0 or bits < 16 or rounds < 1:
+            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
+        limbs = _limbs.limbs_for_bits(bits)
+        if count == 0:
+            return self._empty_rows(limbs)
+        batch = _primes.default_batch(count, bits) if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be at least 1")
+        torch = self.torch
+        found: List[Any] = []
+        have = 0
+        while have < count:
+            rows_t = rng.rows_t(self, batch, bits)
+            for b in (bits - 1, bits - 2, 0):
+                rows_t[:, b >> 5] |= (1 << (b & 31)) - ((1 << 32) if (b & 31) == 31 else 0)      # the bit as an int32
+            verdict = self.probable_prime_t(rows_t, bits, rounds, rng, _checked=True)
+            found.append(rows_t[verdict != 0])
+            have += int(found[-1].shape[0])
+        return torch.cat(found)[:count].contiguous()
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):

@@ -1,0 +1,148 @@
+"""Probable primes on the GPU: a batched Miller-Rabin test and the search for random primes around it — what makes or
+vets the primes of an ordinary private key (``private_key.PaillierPrivateKey.generate`` / ``check_primes``).
+
+The test of a batch runs in three stages, each on what the one before left (``Engine.probable_prime_t``): trial division
+by the odd primes below ``SIEVE_BOUND`` (``Engine.sieve_t``), the strong-pseudoprime test to the base 2
+(``Engine.miller_rabin_base2_t``), and ``rounds`` rounds to random bases (``Engine.miller_rabin_t``: the generic modexp
+b^d mod n, then the witness loop).  A composite passes a round to a random base with probability at most 1/4, so
+``rounds = 64`` bounds the error for ANY input — a number chosen by somebody else to fool the test included — by 4^-64,
+without leaning on the average-case tables that hold only for random candidates.  The random rounds run only on the few
+candidates that survive the base 2, so the bound is cheap; a caller who tests candidates it drew itself at random may
+lower ``rounds`` (for random 1024-bit candidates a handful of rounds already gives 2^-80, Damgard-Landrock-Pomerance
+1993).
+
+Side channels.  The base-2 stage (csrc/mx_mr.hpp: mr_base2_kernel) works from the candidate alone, without a window table
+or a tape: one squaring and one selected doubling per bit, a sequence of operations that depends on the bit length of
+the widest candidate of the launch only (the comparisons at its end run for as many steps as the largest number of
+trailing zero bits of n - 1 in a wavefront).  A candidate that becomes p or q leaks neither through a schedule nor
+through table addresses there.  The random-base rounds go through ``Engine.powmod_multi_t``, the generic kernel's
+fixed-window ladder: its sequence of operations depends on the bit lengths only, the table rows it reads are chosen by the
+digits of d = (n - 1) / 2^s — the class private_key.py documents for the key's own modexps.  The sieve and the
+compaction between the stages show which candidates were dropped where; those are not the key.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Any, List, Optional, Sequence
+
+SIEVE_BOUND = 1 << 14          # the sieve divides by the 1899 odd primes below it; about 12 % of odd candidates survive
+
+_ODD_PRIMES: List[int] = []
+
+
+def sieve_primes() -> List[int]:
+    """The odd primes below SIEVE_BOUND."""
+    if not _ODD_PRIMES:
+        flags = bytearray([1]) * SIEVE_BOUND
+        for i in range(3, math.isqrt(SIEVE_BOUND) + 1, 2):
+            if flags[i]:
+                flags[i * i :: 2 * i] = bytearray(len(range(i * i, SIEVE_BOUND, 2 * i)))
+        _ODD_PRIMES.extend(i for i in range(3, SIEVE_BOUND, 2) if flags[i])
+    return _ODD_PRIMES
+
+
+def prime_density(bits: int) -> float:
+    """A lower bound of the share of primes among the odd numbers of `bits` bits: 2 / (bits ln 2)."""
+    return 2.0 / (bits * math.log(2.0))
+
+
+def poisson_shortfall(count: int, mean: float) -> float:
+    """P[X < count] for X Poisson with the given mean."""
+    term = total = math.exp(-mean)
+    for k in range(1, count):
+        term *= mean / k
+        total += term
+    return total if count > 0 else 0.0
+
+
+SHORTFALL = 0.02
+
+
+def default_batch(count: int, bits: int) -> int:
+    """The rows ``Engine.prime_search_t`` draws per batch when the caller names none: the smallest multiple of 64 whose
+    expected number of primes, batch * 2 / (bits ln 2), leaves a Poisson probability of at most 2 % that the batch
+    holds fewer than `count` — one batch is nearly always enough, and a second one is drawn when it is not."""
+    count, bits = int(count), int(bits)
+    if count < 1 or bits < 2:
+        raise ValueError("count >= 1 and bits >= 2 expected")
+    mean = float(count)
+    while poisson_shortfall(count, mean) > SHORTFALL:      # grows by at most a few standard deviations
+        mean += max(1.0, 0.25 * math.sqrt(mean))
+    return 64 * math.ceil(mean / prime_density(bits) / 64)
+
+
+def _trial_division(n: int) -> bool:
+    """Exact for 2 <= n < SIEVE_BOUND^2."""
+    if n % 2 == 0:
+        return n == 2
+    for p in sieve_primes():
+        if p * p > n:
+            break
+        if n % p == 0:
+            return False
+    return True
+
+
+def _engine(engine: Any) -> Any:
+    if engine is not None:
+        return engine
+    from .engine import default_engine
+
+    return default_engine()
+
+
+def _rng(rng: Any) -> Any:
+    if rng is not None:
+        return rng
+    from .device_rng import DeviceRng
+
+    return DeviceRng()
+
+
+def is_probable_prime_batch(values: Sequence[int], rounds: int = 64, rng: Any = None, engine: Any = None) -> List[bool]:
+    """[is n a (probable) prime for n in values] as one GPU batch.  Negative numbers, 0, 1 and even numbers are decided on
+    the host, and so is everything below SIEVE_BOUND^2, by exact trial division (the device sieve flags a small prime
+    itself as divisible); the rest goes through ``Engine.probable_prime_t``: wrong with probability at most 4^-rounds
+    for a composite, never for a prime.  ``rng``: a ``device_rng.DeviceRng`` for the random bases (default: a fresh
+    one)."""
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    vals = [int(v) for v in values]
+    out = [False] * len(vals)
+    device: List[int] = []
+    for i, n in enumerate(vals):
+        if n < 2 or (n % 2 == 0 and n != 2):
+            continue
+        if n < SIEVE_BOUND * SIEVE_BOUND:
+            out[i] = _trial_division(n)
+        else:
+            device.append(i)
+    if device:
+        from . import limbs
+
+        eng = _engine(engine)
+        cands = [vals[i] for i in device]
+        bits = limbs.max_bits(cands)
+        rows_t = eng.to_device(limbs.pack(cands, limbs.limbs_for_bits(bits)))
+        verdict = eng.probable_prime_t(rows_t, bits, rounds, _rng(rng))
+        verdict = verdict.cpu().numpy() if hasattr(verdict, "cpu") else verdict
+        for i, ok in zip(device, verdict):
+            out[i] = bool(ok)
+    return out
+
+
+def random_primes(count: int, bits: int, rng: Any = None, rounds: int = 64, engine: Any = None, batch: Optional[int] = None) -> List[int]:
+    """`count` random probable primes of exactly `bits` bits with the two top bits set (the product of two of them has
+    exactly 2 * bits bits), drawn and tested on the device: ``Engine.prime_search_t`` fetched as ints.  ``rng``: a
+    ``device_rng.DeviceRng`` (default: a fresh one, keyed from the operating system)."""
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must not be negative")
+    if count == 0:
+        return []
+    from . import limbs
+
+    eng = _engine(engine)
+    return limbs.unpack(eng.to_host(eng.prime_search_t(count, int(bits), _rng(rng), rounds=rounds, batch=batch)))

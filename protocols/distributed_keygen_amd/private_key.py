@@ -17,7 +17,9 @@ The status.  A row's status is non-zero when c^(p-1) is not 1 modulo p (bit 0) o
 prime p that happens exactly when p divides c: the status detects ciphertexts that share a factor with N (0, multiples of
 p or q) and nothing else.  Every c coprime to N is a valid ciphertext of SOME plaintext, so a corrupted or foreign
 ciphertext decrypts, without a status, to a wrong plaintext — as it does in every Paillier implementation.  With a
-composite "prime" the status fires for most ciphertexts; primality itself is never tested here.
+composite "prime" the status fires for most ciphertexts.  Neither decryption nor the constructor tests primality:
+``PaillierPrivateKey.check_primes`` does (a batched Miller-Rabin test on the device, primes.py), and
+``PaillierPrivateKey.generate`` makes a key from primes found by it.
 
 Side channels.  The exponents p - 1 and q - 1 are the secret.  By default the modexps follow a sliding-window tape
 that is a function of the exponent's bits, and the table row a window reads is chosen by its digits: timing and table
@@ -97,9 +99,10 @@ _NOT_VALID = ("Not a valid ciphertext under this key: c^(p-1) is not 1 modulo p 
 class PaillierPrivateKey:
     """The private key (p, q) of the public key N = p q with generator N + 1, decrypting and encrypting batches on the GPU.
 
-    Primality is the caller's business: the constructor refuses an even "prime", p == q and gcd(pq, (p-1)(q-1)) != 1,
-    and tests nothing else — two odd composites that pass these checks give a key that decrypts wrongly.  ``engine`` is
-    injected so that the host logic is testable without a GPU; the default is the process-wide HIP engine."""
+    The constructor refuses an even "prime", p == q and gcd(pq, (p-1)(q-1)) != 1, and tests nothing else — two odd
+    composites that pass these checks give a key that decrypts wrongly.  ``check_primes()`` vets a key received from
+    elsewhere; ``generate`` / ``generate_batch`` make keys from primes searched on the device.  ``engine`` is injected
+    so that the host logic is testable without a GPU; the default is the process-wide HIP engine."""
 
     def __init__(self, p: int, q: int, engine: Any = None) -> None:
         p, q = int(p), int(q)
@@ -109,6 +112,48 @@ class PaillierPrivateKey:
         self.n_square = self.n * self.n
         self._engine = engine
         self._own_rng: Any = None                 # the device generator of fresh encryptions, made on first use
+
+    # ------------------------------------------------------------------ key generation and vetting (primes.py)
+    @classmethod
+    def generate(cls, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None) -> "PaillierPrivateKey":
+        """A fresh key whose N has exactly `key_length` bits: two distinct random probable primes of key_length / 2 bits
+        each, found on the device (``primes.random_primes``: `rounds` Miller-Rabin rounds to random bases behind a sieve
+        and the base 2).  ``rng``: a ``device_rng.DeviceRng`` (default: a fresh one, keyed from the operating
+        system).  ValueError for an odd key_length or one below 64."""
+        return cls.generate_batch(1, key_length, rng=rng, rounds=rounds, engine=engine)[0]
+
+    @classmethod
+    def generate_batch(cls, count: int, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None) -> List["PaillierPrivateKey"]:
+        """`count` fresh keys — one per client or per session — from ONE search for 2 * count primes: key i takes primes
+        2 i and 2 i + 1 of the search's draw order.  A prime that came up twice (probability about 2^-(key_length / 2))
+        is searched again.  Everything else as ``generate``."""
+        count, key_length = int(count), int(key_length)
+        if count < 0:
+            raise ValueError("count must not be negative")
+        if key_length < 64 or key_length % 2:
+            raise ValueError("key_length must be even and at least 64")
+        if int(rounds) < 1:
+            raise ValueError("rounds must be at least 1")
+        if count == 0:
+            return []
+        from . import primes
+        from .device_rng import DeviceRng
+
+        rng = DeviceRng() if rng is None else rng
+        found: List[int] = []
+        while len(found) < 2 * count:
+            for prime in primes.random_primes(2 * count - len(found), key_length // 2, rng=rng, rounds=rounds, engine=engine):
+                if prime not in found:
+                    found.append(prime)
+        return [cls(found[2 * i], found[2 * i + 1], engine=engine) for i in range(count)]
+
+    def check_primes(self, rounds: int = 64, rng: Any = None, engine: Any = None) -> bool:
+        """True iff p and q both pass ``primes.is_probable_prime_batch`` with `rounds` random bases: wrong for a key with
+        a composite "prime" with probability at most 4^-rounds, whoever chose it.  What to run on a key received from
+        elsewhere before trusting its decryptions."""
+        from . import primes
+
+        return all(primes.is_probable_prime_batch([self.p, self.q], rounds=rounds, rng=rng, engine=self._eng(engine)))
 
     def _eng(self, engine: Any = None) -> Any:
         if engine is not None:
