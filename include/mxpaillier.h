@@ -902,6 +902,25 @@ int mx_mr_tail(const uint32_t* d_x0, const uint32_t* d_bases, const int32_t* d_s
 int mx_mr_base2(const uint32_t* d_cands, const uint32_t* h_cands, uint8_t* d_pass, int limbs, int mod_bits, int64_t groups,
                 void* stream);
 
+/* ---- the safe-prime search: p = 2h + 1 with h and p prime (ABI 4.4, additions) ---------------------------------------
+ * For the party that makes or vets a key of two safe primes (csrc/mx_safe.hpp; tools/mr_model.py is the model).
+ *
+ * mx_safe_sieve: the joint sieve of h and 2h + 1 over `batch` DEVICE rows d_halves [batch][limbs] of h:  d_out[e] = 1 iff
+ *   some h_primes[k] = l has h ≡ 0 (l divides h) or h ≡ (l - 1) / 2 (l divides 2h + 1) modulo l.  The geometry, the tables
+ *   and the workspace are those of mx_sieve (mx_safe_sieve_workspace_bytes = mx_sieve_workspace_bytes); limbs, table rows
+ *   and multiply-adds are read and issued once for the two conditions.  Primes must be odd, >= 3 and < 2^31; limbs <= 1024.
+ *   Two launches (the tables, the sieve) behind the upload of the list, no synchronisation.
+ * mx_safe_double: d_out = 2 d_in + 1 over `rows` DEVICE rows [rows][limbs] (d_out must not be d_in); one launch.  A row
+ *   whose top bit (bit 32 * limbs - 1) is set does not fit and comes out truncated: the caller refuses it beforehand.
+ * A count of 0 returns MX_OK without a launch.  MX_ERR_ARG for a null pointer, limbs < 1, n_primes < 1, a negative count,
+ * a listed prime that is even, below 3 or >= 2^31, or d_out == d_in; MX_ERR_SIZE for limbs > 1024 (the sieve) or more rows
+ * than a launch addresses; MX_ERR_WORKSPACE for a workspace below mx_safe_sieve_workspace_bytes.  A refused call launches
+ * nothing. */
+int64_t mx_safe_sieve_workspace_bytes(int limbs, int n_primes);
+int mx_safe_sieve(const uint32_t* d_halves, uint8_t* d_out, const uint32_t* h_primes, int n_primes, int limbs,
+                  int64_t batch, void* d_workspace, int64_t workspace_bytes, void* stream);
+int mx_safe_double(const uint32_t* d_in, uint32_t* d_out, int limbs, int64_t rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,9 @@ SYMBOLS = {
     "mx_mr_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "mx_mr_tail": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p]),
     "mx_mr_base2": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "mx_safe_sieve_workspace_bytes": (c_int64, [c_int, c_int]),
+    "mx_safe_sieve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "mx_safe_double": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
 }
 
 

@@ -13,46 +13,9 @@
 // One wavefront handles SIEVE_C candidates: lanes run over primes (coalesced table reads), the
 // candidates' limbs are staged transposed in LDS so that one ds_read_b128 feeds four MACs.
 #pragma once
-#include "mx_lanes.hpp"
+#include "mx_sieve_setup.hpp"
 
 namespace mx {
-
-constexpr int SIEVE_C = 8;   // candidates per wavefront
-
-struct SieveArgs {
-  const u32* cands;    // [batch][limbs] device
-  unsigned char* out;  // [batch] device
-  const u32* primes;   // [np] device
-  u32* pw;             // [limbs][np_pad] device: 2^(32 j) mod prime_k
-  u64* inv;            // [np_pad] device: prime^-1 mod 2^64
-  u64* lim;            // [np_pad] device: floor((2^64-1)/prime)
-  long long batch;
-  int limbs;
-  int np;
-  int np_pad;          // multiple of 64
-  int chunk;           // limbs between two folds of the 64-bit columns (>= limbs: never)
-};
-
-// one thread per prime: powers of 2^32, inverse and limit
-__global__ void sieve_setup_kernel(SieveArgs A) {
-  int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= A.np_pad) return;
-  if (k >= A.np) {   // padding lanes (masked out in the main kernel)
-    for (int j = 0; j < A.limbs; ++j) A.pw[(long long)j * A.np_pad + k] = 0;
-    A.inv[k] = 1; A.lim[k] = 0;
-    return;
-  }
-  u64 l = A.primes[k];
-  u64 r = 1 % l;
-  for (int j = 0; j < A.limbs; ++j) {
-    A.pw[(long long)j * A.np_pad + k] = (u32)r;
-    r = (r << 32) % l;
-  }
-  u64 x = l;                       // Newton inverse mod 2^64 (l odd): 3 -> 6 -> ... -> 96 bits
-  for (int i = 0; i < 5; ++i) x *= 2 - l * x;
-  A.inv[k] = x;
-  A.lim[k] = ~0ull / l;
-}
 
 __global__ void __launch_bounds__(64) sieve_kernel(SieveArgs A) {
   extern __shared__ u32 smem[];   // [limbs][SIEVE_C]

@@ -2378,6 +2378,131 @@ class Engine:
             have += int(found[-1].shape[0])
         return torch.cat(found)[:count].contiguous()
 
+    # ------------------------------------------------------------------ safe primes p = 2h + 1 (primes.py)
+    def _half_rows(self, halves_t) -> Tuple[int, int]:
+        if not _is_device_rows(halves_t) or halves_t.dim() != 2 or halves_t.dtype != self.torch.int32 or not halves_t.is_contiguous():
+            raise ValueError("halves must be contiguous int32 device rows [S, limbs]")
+        rows, limbs = halves_t.shape
+        if limbs < 1:
+            raise ValueError("halves must have at least one word")
+        return rows, limbs
+
+    def safe_sieve_t(self, halves_t, primes: Sequence[int], out_t=None):
+        """The joint sieve of h and 2h + 1 over rows of h: uint8 ``[S]``, 1 iff some listed prime l has h = 0 (l divides
+        h) or h = (l - 1) / 2 (l divides 2h + 1) modulo l — ``sieve_t(h) | sieve_t(2h + 1)`` from one pass over limbs and
+        tables (mx_safe_sieve, csrc/mx_safe.hpp).  ValueError — nothing launched — for an empty list, a listed prime
+        that is even, below 3 or not below 2^31, or rows of another shape."""
+        rows, limbs = self._half_rows(halves_t)
+        primes = [int(p) for p in primes]
+        if not primes or any(p < 3 or p % 2 == 0 or p >= 1 << 31 for p in primes):
+            raise ValueError("a list of odd primes in [3, 2^31) expected")
+        if out_t is not None and (tuple(out_t.shape) != (rows,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
+            raise ValueError(f"out_t must be contiguous uint8 of the shape ({rows},)")
+        if out_t is None:
+            out_t = self.torch.empty(rows, dtype=self.torch.uint8, device=self.device)
+        if rows:
+            h_primes = np.ascontiguousarray(np.asarray(primes, dtype=np.uint32))
+            self._call("mx_safe_sieve", halves_t.data_ptr(), out_t.data_ptr(), h_primes.ctypes.data, len(h_primes), limbs, rows,
+                       workspace=("mx_safe_sieve_workspace_bytes", limbs, len(h_primes)))
+        return out_t
+
+    def safe_double_t(self, halves_t, _checked: bool = False):
+        """2h + 1 for rows of h, as rows of the same width (mx_safe_double: one launch).  ValueError — nothing launched —
+        when a row has its top bit (bit 32 * limbs - 1) set, so that 2h + 1 would not fit the width, or for rows of
+        another shape."""
+        rows, limbs = self._half_rows(halves_t)
+        if rows and not _checked and bool((halves_t[:, limbs - 1] < 0).any()):      # the top bit is the int32's sign
+            raise ValueError("2h + 1 does not fit the rows' width")
+        out_t = self._empty_rows(limbs, rows)
+        if rows:
+            self._call("mx_safe_double", halves_t.data_ptr(), out_t.data_ptr(), limbs, rows)
+        return out_t
+
+    def safe_prime_t(self, halves_t, bits: int, rounds: int, rng, _checked: bool = False, _stages: Optional[List[Any]] = None):
+        """uint8 ``[S]``: 1 where p = 2h + 1 is a safe prime — h and p both prime — for rows of odd h above
+        primes.SIEVE_BOUND of at most `bits` - 1 bits; `bits` is the width of p.  Four stages, each on the rows the one
+        before left, compacted by indexing in between: the joint sieve by the odd primes below primes.SIEVE_BOUND
+        (safe_sieve_t), the base 2 on h (miller_rabin_base2_t, bits - 1), safe_double_t and the base 2 on p (bits), and
+        `rounds` rounds to random bases on h (ONE ``generator_shares_t`` draw of survivors * rounds rows, none when
+        nothing is left), ANDed per candidate.
+
+        The random rounds run on h only.  With h an odd prime, p = 2h + 1, 3 not dividing p (the sieve saw to it) and
+        2^(p-1) = 1 mod p, Pocklington's theorem makes p prime: the proven factor F = h of p - 1 exceeds sqrt(p) and
+        gcd(2^((p-1)/h) - 1, p) = gcd(3, p) = 1.  The round to the base 2 on p, with s = 1 and d = h, is that test
+        (2^h = 1 or -1 implies 2^(p-1) = 1).  So a safe prime always passes, and any other input — one chosen to fool
+        the test included — passes with probability at most 4^-rounds: a composite h survives the rounds with at most
+        that probability, and a prime h makes the verdict on p exact.  `_stages`, a list, receives the indices each
+        stage left.  ValueError — nothing launched — for rounds < 1, `bits` outside [3, 32 * limbs], an even or too
+        small h, one of more than bits - 1 bits, or rows of another shape."""
+        from . import primes as _primes
+
+        rounds, bits = int(rounds), int(bits)
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        rows, limbs = self._half_rows(halves_t)
+        if not 3 <= bits <= 32 * limbs:
+            raise ValueError("bits must lie in [3, 32 * limbs]")
+        self._mr_candidates(halves_t, bits - 1, above=_primes.SIEVE_BOUND, checked=_checked)
+        torch = self.torch
+        out_t = torch.zeros(rows, dtype=torch.uint8, device=self.device)
+        left = torch.arange(0, device=self.device)
+        if rows:
+            left = torch.nonzero(self.safe_sieve_t(halves_t, _primes.sieve_primes()) == 0).flatten()
+        stages = [left]
+        if left.numel():
+            left = left[self.miller_rabin_base2_t(halves_t[left].contiguous(), bits - 1, _checked=True) != 0]
+        stages.append(left)
+        if left.numel():
+            full_t = self.safe_double_t(halves_t[left].contiguous(), _checked=True)
+            left = left[self.miller_rabin_base2_t(full_t, bits, _checked=True) != 0]
+        stages.append(left)
+        if left.numel():
+            kept_t = halves_t[left].contiguous()
+            bases_t = self.generator_shares_t((kept_t, bits - 1), rounds, rng=rng)
+            passed = self.miller_rabin_t(kept_t, bases_t, rounds, bits=bits - 1, _checked=True)
+            out_t[left] = passed.view(-1, rounds).min(dim=1).values
+            left = left[out_t[left] != 0]
+        stages.append(left)
+        if _stages is not None:
+            _stages.extend(stages)
+        return out_t
+
+    def safe_prime_search_t(self, count: int, bits: int, rng, rounds: int = 64, batch: Optional[int] = None):
+        """`count` random safe primes p = 2h + 1 of exactly `bits` bits as rows ``[count, limbs]``, in draw order: draw
+        `batch` rows h of bits - 1 bits from `rng`, set bits bits - 2, bits - 3 and 0 (p then has exactly `bits` bits
+        with its two top bits set — the product of two such primes has exactly 2 * bits bits — and p = 3 mod 4), run
+        safe_prime_t, keep 2h + 1 of what passes, and draw again while there are fewer than `count`.
+
+        Safe primes are rare (primes.safe_prime_density: one odd h in about 190 000 at 1024 bits), so the default
+        `batch` (primes.default_safe_batch) is NOT sized to hold `count` of them: it is the Poisson batch of
+        primes.default_batch's rule from the safe-prime density, capped at primes.SAFE_BATCH_BYTES of rows per draw,
+        and the search loops over batches until one completes `count`.  ValueError — nothing launched — for count < 0,
+        bits < 16 or rounds < 1."""
+        from . import primes as _primes
+
+        count, bits, rounds = int(count), int(bits), int(rounds)
+        if count < 0 or bits < 16 or rounds < 1:
+            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
+        limbs = _limbs.limbs_for_bits(bits)
+        if count == 0:
+            return self._empty_rows(limbs)
+        batch = _primes.default_safe_batch(count, bits) if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be at least 1")
+        torch = self.torch
+        found: List[Any] = []
+        have = 0
+        while have < count:
+            halves_t = rng.rows_t(self, batch, bits - 1, limbs)
+            for b in (bits - 2, bits - 3, 0):
+                halves_t[:, b >> 5] |= (1 << (b & 31)) - ((1 << 32) if (b & 31) == 31 else 0)      # the bit as an int32
+            verdict = self.safe_prime_t(halves_t, bits, rounds, rng, _checked=True)
+            kept_t = halves_t[verdict != 0].contiguous()
+            if kept_t.shape[0]:
+                found.append(self.safe_double_t(kept_t, _checked=True))
+                have += int(kept_t.shape[0])
+        return torch.cat(found)[:count].contiguous()
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):

@@ -115,15 +115,20 @@ class PaillierPrivateKey:
 
     # ------------------------------------------------------------------ key generation and vetting (primes.py)
     @classmethod
-    def generate(cls, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None) -> "PaillierPrivateKey":
+    def generate(cls, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None, safe: bool = False) -> "PaillierPrivateKey":
         """A fresh key whose N has exactly `key_length` bits: two distinct random probable primes of key_length / 2 bits
         each, found on the device (``primes.random_primes``: `rounds` Miller-Rabin rounds to random bases behind a sieve
         and the base 2).  ``rng``: a ``device_rng.DeviceRng`` (default: a fresh one, keyed from the operating
-        system).  ValueError for an odd key_length or one below 64."""
-        return cls.generate_batch(1, key_length, rng=rng, rounds=rounds, engine=engine)[0]
+        system).  ``safe=True``: both primes are safe primes, p = 2 p' + 1 with p' prime (``primes.random_safe_primes``)
+        — what threshold Paillier with a dealer and the auxiliary moduli of range proofs ask for; such primes are rare
+        (one candidate in about 190 000 at key_length 2048), so the search takes correspondingly longer.  For two
+        distinct safe primes of equal length gcd(N, phi(N)) = 1 holds by itself.  ValueError for an odd key_length or
+        one below 64."""
+        return cls.generate_batch(1, key_length, rng=rng, rounds=rounds, engine=engine, safe=safe)[0]
 
     @classmethod
-    def generate_batch(cls, count: int, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None) -> List["PaillierPrivateKey"]:
+    def generate_batch(cls, count: int, key_length: int, rng: Any = None, rounds: int = 64, engine: Any = None,
+                       safe: bool = False) -> List["PaillierPrivateKey"]:
         """`count` fresh keys — one per client or per session — from ONE search for 2 * count primes: key i takes primes
         2 i and 2 i + 1 of the search's draw order.  A prime that came up twice (probability about 2^-(key_length / 2))
         is searched again.  Everything else as ``generate``."""
@@ -140,19 +145,23 @@ class PaillierPrivateKey:
         from .device_rng import DeviceRng
 
         rng = DeviceRng() if rng is None else rng
+        search = primes.random_safe_primes if safe else primes.random_primes
         found: List[int] = []
         while len(found) < 2 * count:
-            for prime in primes.random_primes(2 * count - len(found), key_length // 2, rng=rng, rounds=rounds, engine=engine):
+            for prime in search(2 * count - len(found), key_length // 2, rng=rng, rounds=rounds, engine=engine):
                 if prime not in found:
                     found.append(prime)
         return [cls(found[2 * i], found[2 * i + 1], engine=engine) for i in range(count)]
 
-    def check_primes(self, rounds: int = 64, rng: Any = None, engine: Any = None) -> bool:
+    def check_primes(self, rounds: int = 64, rng: Any = None, engine: Any = None, safe: bool = False) -> bool:
         """True iff p and q both pass ``primes.is_probable_prime_batch`` with `rounds` random bases: wrong for a key with
         a composite "prime" with probability at most 4^-rounds, whoever chose it.  What to run on a key received from
-        elsewhere before trusting its decryptions."""
+        elsewhere before trusting its decryptions.  ``safe=True``: true iff p and q are both SAFE primes
+        (``primes.is_safe_prime_batch``, the same error bound)."""
         from . import primes
 
+        if safe:
+            return all(primes.is_safe_prime_batch([self.p, self.q], rounds=rounds, rng=rng, engine=self._eng(engine)))
         return all(primes.is_probable_prime_batch([self.p, self.q], rounds=rounds, rng=rng, engine=self._eng(engine)))
 
     def _eng(self, engine: Any = None) -> Any:
