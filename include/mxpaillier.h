@@ -921,6 +921,35 @@ int mx_safe_sieve(const uint32_t* d_halves, uint8_t* d_out, const uint32_t* h_pr
                   int64_t batch, void* d_workspace, int64_t workspace_bytes, void* stream);
 int mx_safe_double(const uint32_t* d_in, uint32_t* d_out, int limbs, int64_t rows, void* stream);
 
+/* ---- decryption proofs of a dealt threshold key: challenge and response (ABI 4.4, additions) -------------------------
+ * The two steps of a proof of equal discrete logarithms that no other entry point covers (csrc/mx_sha256.hpp,
+ * csrc/mx_proof.hpp; tools/proof_model.py is the model; protocols/distributed_keygen_amd/threshold.py composes them with
+ * the modexps, the multi-exponentiation and the fixed-base tables above).
+ *
+ * mx_sha256_rows:  d_out[r] = SHA-256(prefix | BE(rows_0[r]) | .. | BE(rows_{n_sets-1}[r])),  r < count  (FIPS 180-4).
+ *   prefix: 32 HOST bytes that travel by value in the kernel-argument block (they may be freed or overwritten on return).
+ *   d_rows: a HOST array of n_sets DEVICE pointers, set s being [count][limbs[s]] little-endian words; limbs: a HOST array.
+ *   BE(row) is the row as a big-endian integer of 4 * limbs[s] bytes (its words in reverse order: they are the hash's
+ *   big-endian message words, no byte is swapped), so the message has 32 + 4 * sum limbs bytes.  n_sets = 0 hashes the
+ *   prefix alone, count times.  d_out is [count][8] little-endian words whose integer is the digest read as a big-endian
+ *   integer (word 7 holds the digest's first four bytes).  One launch on `stream`, no workspace, no synchronisation.
+ * mx_dleq_response:  d_z[r] = d_rho[r] + d_e[r] * x  over the integers,  r < count.
+ *   d_rho [count][wz], d_e [count][ew], d_x ONE row [wx] (the secret exponent, resident on the device), d_z [count][wz]
+ *   (it may be d_rho), d_status [count]: 1 iff the sum does not fit wz words (d_z[r] then holds its low wz words), else 0.
+ *   Plain multiply-adds with carries, one row per lane; control flow and addresses depend on (count, wz, ew, wx) only.
+ *   One launch on `stream`, no workspace, no synchronisation.
+ * A count of 0 returns MX_OK without a launch.  MX_ERR_ARG for a null pointer (d_rows and limbs may be NULL when n_sets is
+ * 0), n_sets outside [0, MX_SHA256_MAX_SETS], a width below 1 or a negative count; MX_ERR_SIZE for a message of more than
+ * MX_SHA256_MAX_WORDS words, a width above MX_DLEQ_MAX_WORDS or more rows than a launch addresses.  A refused call
+ * launches nothing. */
+#define MX_SHA256_MAX_SETS 8
+#define MX_SHA256_MAX_WORDS (1 << 24)
+#define MX_DLEQ_MAX_WORDS (1 << 20)
+int mx_sha256_rows(const uint8_t prefix[32], const uint32_t* const* d_rows, const int* limbs, int n_sets, int64_t count,
+                   uint32_t* d_out, void* stream);
+int mx_dleq_response(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z, uint8_t* d_status,
+                     int wz, int ew, int wx, int64_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

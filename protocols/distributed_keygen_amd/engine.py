@@ -2503,6 +2503,236 @@ class Engine:
                 have += int(kept_t.shape[0])
         return torch.cat(found)[:count].contiguous()
 
+    # ------------------------------------------------------------------ decryption proofs of a dealt threshold key (threshold.py)
+    def _word_rows(self, rows_t, what: str, width: Optional[int] = None) -> Tuple[int, int]:
+        if not _is_device_rows(rows_t) or rows_t.dim() != 2 or rows_t.dtype != self.torch.int32 or not rows_t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous int32 device rows [count, words]")
+        if rows_t.device != self.device:
+            raise ValueError(f"{what} live on {rows_t.device}, the operation runs on {self.device}")
+        rows, words = rows_t.shape
+        if words < 1 or (width is not None and words != width):
+            raise ValueError(f"{what} must have {'at least one word' if width is None else f'{width} words'}")
+        return rows, words
+
+    def sha256_rows_t(self, prefix: bytes, row_sets: Sequence[Any], count: Optional[int] = None):
+        """digest[r] = SHA-256(prefix | BE(rows_0[r]) | .. | BE(rows_{k-1}[r])) on the device (mx_sha256_rows,
+        csrc/mx_sha256.hpp): ``prefix`` 32 bytes, ``row_sets`` up to eight int32 device tensors ``[count, limbs_s]`` of
+        any widths, BE(row) the row as a big-endian integer of 4 * limbs_s bytes.  Returns ``[count, 8]`` int32 rows
+        whose integer is ``int.from_bytes(digest, "big")``.  ``count`` is needed only when there is no set (the prefix
+        alone, hashed `count` times).  ValueError — nothing launched — for anything else."""
+        prefix = bytes(prefix)
+        if len(prefix) != 32:
+            raise ValueError("the prefix must have 32 bytes")
+        sets = list(row_sets)
+        if len(sets) > _lib.MX_SHA256_MAX_SETS:
+            raise ValueError(f"at most {_lib.MX_SHA256_MAX_SETS} row sets")
+        shapes = [self._word_rows(t, "hashed rows") for t in sets]
+        if not sets and count is None:
+            raise ValueError("count expected when there is no row set")
+        rows = int(count) if count is not None else shapes[0][0]
+        if rows < 0 or any(s[0] != rows for s in shapes):
+            raise ValueError("every row set must have the same number of rows")
+        out_t = self.torch.empty((rows, 8), dtype=self.torch.int32, device=self.device)
+        if rows:
+            ptrs = (_ctypes.c_void_p * max(1, len(sets)))(*[t.data_ptr() for t in sets])
+            widths = (_ctypes.c_int * max(1, len(sets)))(*[s[1] for s in shapes])
+            self._call("mx_sha256_rows", prefix, ptrs, widths, len(sets), rows, out_t.data_ptr())
+        return out_t
+
+    def dleq_response_t(self, rho_t, e_t, x_t, out_t=None):
+        """(z, status): z[r] = rho[r] + e[r] * x over the integers on the device (mx_dleq_response, csrc/mx_proof.hpp).
+        ``rho_t`` ``[count, wz]``, ``e_t`` ``[count, ew]``, ``x_t`` ONE row ``[wx]`` or ``[1, wx]`` — the secret exponent,
+        which stays on the device —, z ``[count, wz]`` (``out_t``; it may be ``rho_t``), status uint8 ``[count]``: 1 where
+        the sum does not fit wz words (z then holds its low words).  The caller sizes wz so that it never happens and
+        reads the status when it cannot be sure."""
+        count, wz = self._word_rows(rho_t, "rho rows")
+        _, ew = self._word_rows(e_t, "challenge rows")
+        if e_t.shape[0] != count:
+            raise ValueError("one challenge row per rho row expected")
+        if not _is_device_rows(x_t) or x_t.dim() not in (1, 2) or (x_t.dim() == 2 and x_t.shape[0] != 1):
+            raise ValueError("ONE exponent row on the device expected")
+        _, wx = self._word_rows(x_t.view(1, -1), "the exponent row")
+        if out_t is None:
+            out_t = self.torch.empty_like(rho_t)
+        elif self._word_rows(out_t, "z rows", wz)[0] != count:
+            raise ValueError("one z row per rho row expected")
+        status_t = self.torch.empty(count, dtype=self.torch.uint8, device=self.device)
+        if count:
+            self._call("mx_dleq_response", rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(),
+                       wz, ew, wx, count)
+        return out_t, status_t
+
+    @_int_args
+    def multiexp_nsquare_rows_t(self, inputs_t, index_t, weights_t, terms: int, weight_bits: int, n: int, window: int = 0,
+                                _checked: bool = False):
+        """out[r] = prod_{t < terms} inputs[index[r][t]] ^ w[r][t] mod n^2 with the index and the weights ALREADY ON THE
+        DEVICE: ``index_t`` int32 ``[rows, terms]`` in [0, n_inputs), ``weights_t`` int32 ``[rows, terms * ww]`` (or any
+        contiguous view of it, such as ``[rows, terms, ww]``) of non-negative weights of ww = ceil(weight_bits / 32)
+        little-endian words, weight_bits <= 2 bits(n) + 64.  One launch of mx_multiexp_nsquare_run behind its table
+        pass: no plan, no sign split, no split-K — the thin entry for weights that are secret or were made on the device
+        (``multiexp_nsquare_t`` plans public ones).  Canonical residues ``[rows, limbs2]``."""
+        _check_modulus(n)
+        n_inputs, limbs2 = self._word_rows(inputs_t, "inputs")
+        _check_rows_n2(n, limbs2)
+        nb = n.bit_length()
+        if terms < 1 or weight_bits < 1 or weight_bits > 2 * nb + 64:
+            raise ValueError(f"terms >= 1 and weight_bits in 1 .. 2 bits(n) + 64 = {2 * nb + 64} expected")
+        if not 0 <= window <= 8:
+            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
+        rows, _ = self._word_rows(index_t, "the index", terms)
+        ww = (weight_bits + 31) // 32
+        if (not _is_device_rows(weights_t) or weights_t.dtype != self.torch.int32 or not weights_t.is_contiguous()
+                or weights_t.device != self.device or weights_t.dim() < 2 or weights_t.shape[0] != rows or weights_t.numel() != rows * terms * ww):
+            raise ValueError(f"contiguous int32 device weights of {terms} x {ww} words per row expected")
+        if n_inputs < 1:
+            raise ValueError("at least one input expected")
+        out_t = self._empty_rows(limbs2, rows)
+        if rows == 0:
+            return out_t
+        if not _checked and bool(((index_t < 0) | (index_t >= n_inputs)).any()):
+            raise ValueError("index out of range")
+        if window == 0:
+            window = self.multiexp_nsquare_shape(n, n_inputs, rows, terms, weight_bits)[0]
+        plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
+        self._call("mx_multiexp_nsquare_run", plan.desc, inputs_t.data_ptr(), n_inputs, limbs2, index_t.data_ptr(), weights_t.data_ptr(),
+                   terms, weight_bits, out_t.data_ptr(), rows, 0, window,
+                   workspace=("mx_multiexp_nsquare_workspace_bytes", nb, n_inputs, 0, window), plans=(plan,))
+        return out_t
+
+    def _rows_below(self, rows_t, bound: int):
+        """bool ``[count]``: the row, as a little-endian integer, is below `bound`."""
+        torch = self.torch
+        count, words = rows_t.shape
+        if bound >> (32 * words):
+            return torch.ones(count, dtype=torch.bool, device=self.device)
+        vals = rows_t.to(torch.int64) & 0xFFFFFFFF
+        lim = (self.to_device(_limbs.pack_one(bound, words).reshape(1, words)).to(torch.int64) & 0xFFFFFFFF)
+        pos = torch.arange(1, words + 1, device=self.device, dtype=torch.int64)
+        top = ((vals != lim) * pos).max(dim=1).values                  # 1 + the highest word that differs, 0 = equal
+        return (top > 0) & torch.gather(vals < lim, 1, (top - 1).clamp(min=0).view(-1, 1)).view(-1)
+
+    def _dleq_bases_t(self, cts_t, n: int, pieces: int, kw: int):
+        """[chat^(2^(32 kw j)) for j < pieces], chat = c^4: squarings on the pair kernel, each from the one before."""
+        out = [self.powmod_nsquare_t(cts_t, n, 4)]
+        for _ in range(pieces - 1):
+            out.append(self.powmod_nsquare_t(out[-1], n, 1 << (32 * kw)))
+        return out
+
+    def _dleq_powers_t(self, bases, exps_t, n: int, kw: int):
+        """prod_j bases[j][r] ^ (piece j of exps[r]): chat^(exps[r]) in ONE multi-exponentiation launch whose weight block
+        is the exponent rows themselves, read as [count][pieces][kw]."""
+        torch = self.torch
+        pieces, count = len(bases), exps_t.shape[0]
+        index_t = (torch.arange(count, device=self.device, dtype=torch.int32).view(-1, 1)
+                   + count * torch.arange(pieces, device=self.device, dtype=torch.int32).view(1, -1)).contiguous()
+        return self.multiexp_nsquare_rows_t(torch.cat(bases), index_t, exps_t, pieces, 32 * kw, n, _checked=True)
+
+    def _dleq_fixed_t(self, v_bases: Sequence[int], exps_t, n: int, kw: int):
+        """prod_j v_bases[j] ^ (piece j of exps[r]) through the fixed-base tables of the bases v^(2^(32 kw j))."""
+        out_t = None
+        for j, base in enumerate(v_bases):
+            table = self.fixed_base_table(n, base, 32 * kw)
+            piece_t = exps_t[:, j * kw : (j + 1) * kw].contiguous()
+            out_t = self.fixed_base_power_t(table, piece_t) if out_t is None else self.fixed_base_randomize_t(table, piece_t, out_t)
+        return out_t
+
+    def _dleq_challenge_t(self, ctx: bytes, chat_t, ci2_t, a_t, b_t):
+        """The 128-bit challenge rows: the first 16 bytes of the digest are words 4 .. 7 of its row."""
+        return self.sha256_rows_t(ctx, [chat_t, ci2_t, a_t, b_t])[:, 4:8].contiguous()
+
+    @_int_args
+    def dleq_prove_t(self, cts_t, partials_t, n: int, v_bases: Sequence[int], ctx: bytes, x_t, rho_bits: int, kw: int,
+                     rng=None, rho_t=None, _stages: Optional[List[Any]] = None):
+        """The proofs (a, b, z) that ``partials_t`` = c^(2x) were made with the exponent x behind w = v^x (threshold.py;
+        tools/proof_model.py is the model): a = chat^rho, b = v^rho, e = H(ctx, chat, c_i^2, a, b), z = rho + e x, for
+        chat = c^4 and one draw rho of ``rho_bits`` bits per row — from ``rng`` (a ``DeviceRng``), or the rows ``rho_t``
+        a test passes.  Rows of rho and z are ``pieces = len(v_bases)`` pieces of ``kw`` words; ``v_bases`` are the public
+        v^(2^(32 kw j)) mod n^2; ``x_t`` is the secret exponent as ONE device row.  Nothing per row leaves the device.
+        Returns ``(a_t, b_t, z_t)``.  `_stages`, a list, receives (name, end event) pairs for tools/proof_probe.py."""
+        count, limbs2 = self._word_rows(cts_t, "ciphertext rows")
+        _check_modulus(n)
+        _check_rows_n2(n, limbs2)
+        if self._word_rows(partials_t, "partial rows", limbs2)[0] != count:
+            raise ValueError("one partial decryption per ciphertext expected")
+        pieces = len(v_bases)
+        zw = pieces * kw
+        if pieces < 1 or kw < 1 or 32 * kw > 2 * n.bit_length() + 64 or not 1 <= rho_bits < 32 * zw:
+            raise ValueError("pieces of 1 .. (2 bits(n) + 64) / 32 words that hold rho_bits + 1 bits expected")
+        if (rng is None) == (rho_t is None):
+            raise ValueError("exactly one of rng and rho_t expected")
+        if rho_t is None:
+            rho_t = rng.rows_t(self, count, rho_bits, zw)
+        elif self._word_rows(rho_t, "rho rows", zw)[0] != count:
+            raise ValueError("one rho row per ciphertext expected")
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        bases = self._dleq_bases_t(cts_t, n, pieces, kw)
+        ci2_t = self.mulmod_t(partials_t, partials_t, n * n)
+        mark("squarings")
+        a_t = self._dleq_powers_t(bases, rho_t, n, kw)
+        mark("multiexp")
+        b_t = self._dleq_fixed_t(v_bases, rho_t, n, kw)
+        mark("fixed_base")
+        e_t = self._dleq_challenge_t(ctx, bases[0], ci2_t, a_t, b_t)
+        mark("hash")
+        z_t, _ = self.dleq_response_t(rho_t, e_t, x_t)        # (rho_bits + 1 <= 32 zw and e x < 2^rho_bits: it fits)
+        mark("response")
+        return a_t, b_t, z_t
+
+    def _event(self):
+        ev = self.torch.cuda.Event(enable_timing=True)
+        ev.record(self.torch.cuda.current_stream(self.device))
+        return ev
+
+    @_int_args
+    def dleq_verify_t(self, cts_t, partials_t, a_t, b_t, z_t, n: int, v_bases: Sequence[int], w: int, ctx: bytes, z_bits: int,
+                      kw: int, _stages: Optional[List[Any]] = None):
+        """bool ``[count]``: row r is True iff a, b, c_i (and c) are below n^2, z below 2^z_bits, chat^z = a (c_i^2)^e and
+        v^z = b w^e with e recomputed from the hash — the verdicts of the proofs of ``dleq_prove_t``, one per row; a bad
+        row never raises.  Out-of-range rows are replaced by 1 (z by 0) before anything is computed from them.  No
+        inverse of anything the prover sent is taken."""
+        torch = self.torch
+        count, limbs2 = self._word_rows(cts_t, "ciphertext rows")
+        _check_modulus(n)
+        _check_rows_n2(n, limbs2)
+        pieces = len(v_bases)
+        zw = pieces * kw
+        if pieces < 1 or kw < 1 or 32 * kw > 2 * n.bit_length() + 64 or not 1 <= z_bits <= 32 * zw:
+            raise ValueError("pieces of 1 .. (2 bits(n) + 64) / 32 words that hold z_bits bits expected")
+        for t, what in ((partials_t, "partial rows"), (a_t, "a rows"), (b_t, "b rows")):
+            if self._word_rows(t, what, limbs2)[0] != count:
+                raise ValueError(f"one of the {what} per ciphertext expected")
+        if self._word_rows(z_t, "z rows", zw)[0] != count:
+            raise ValueError("one z row per ciphertext expected")
+        if count == 0:
+            return torch.ones(0, dtype=torch.bool, device=self.device)
+        n2 = n * n
+        ok = self._rows_below(z_t, 1 << z_bits)
+        for t in (cts_t, partials_t, a_t, b_t):
+            ok = ok & self._rows_below(t, n2)
+        one = torch.zeros((1, limbs2), dtype=torch.int32, device=self.device)
+        one[0, 0] = 1
+        keep = ok.view(-1, 1)
+        cts_t, partials_t, a_t, b_t = (torch.where(keep, t, one).contiguous() for t in (cts_t, partials_t, a_t, b_t))
+        z_t = torch.where(keep, z_t, torch.zeros_like(z_t)).contiguous()
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        bases = self._dleq_bases_t(cts_t, n, pieces, kw)
+        ci2_t = self.mulmod_t(partials_t, partials_t, n2)
+        mark("squarings")
+        e_t = self._dleq_challenge_t(ctx, bases[0], ci2_t, a_t, b_t)
+        mark("hash")
+        left_t = self._dleq_powers_t(bases, z_t, n, kw)
+        own = torch.arange(count, device=self.device, dtype=torch.int32).view(-1, 1).contiguous()
+        right_t = self.mulmod_t(a_t, self.multiexp_nsquare_rows_t(ci2_t, own, e_t, 1, 128, n, _checked=True), n2)
+        mark("multiexp")
+        left_v = self._dleq_fixed_t(v_bases, z_t, n, kw)
+        right_v = self.fixed_base_randomize_t(self.fixed_base_table(n, w, 128), e_t, b_t)
+        mark("fixed_base")
+        verdict = ok & (left_t == right_t).all(dim=1) & (left_v == right_v).all(dim=1)
+        mark("compare")
+        return verdict
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):
