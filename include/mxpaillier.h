@@ -950,6 +950,47 @@ int mx_sha256_rows(const uint8_t prefix[32], const uint32_t* const* d_rows, cons
 int mx_dleq_response(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z, uint8_t* d_status,
                      int wz, int ew, int wx, int64_t count, void* stream);
 
+/* ---- range proofs: multi-exponentiation over a generic odd modulus, per-row responses (ABI 4.4, additions) -----------
+ * csrc/mx_multiexp.hpp, csrc/mx_response.hpp; tools/range_model.py is the model of the proofs that
+ * protocols/distributed_keygen_amd/range_proof.py composes from them.
+ *
+ * mx_multiexp_run:  d_out[r] = prod_{t < terms} d_inputs[d_index[r][t]] ^ d_weights[r][t]  mod M,  r < n_outputs.
+ *   h_mod: the odd modulus M >= 3, `limbs` HOST words (free on return).  d_inputs [n_inputs][limbs] residues below M,
+ *   d_index int32 [n_outputs][terms] in [0, n_inputs) (an index outside it is clamped, never followed), d_weights
+ *   [n_outputs][terms][ceil(weight_bits / 32)] little-endian words of NON-NEGATIVE weights, d_out [n_outputs][limbs]
+ *   canonical residues in [0, M).  weight_bits, 1 .. MX_MULTIEXP_MAX_WEIGHT_BITS, is NOT tied to bits(M); bits of a
+ *   weight at and above weight_bits, where the last word holds any, are read as part of the top window and must be 0.
+ *   h_term_bits: NULL, or a HOST array of `terms` lengths in 0 .. weight_bits — the weights of term t are below
+ *   2^h_term_bits[t] in EVERY row, and the windows above that length skip the term (a property of the launch, so control
+ *   flow stays the same for every row); the entry of term 0 is prefetched, so the longest term goes first.
+ *   0^0 = 1.  window 1 .. 8 (mx_multiexp_shape proposes one).  Interleaved fixed-window (Straus) form: a table pass (one
+ *   group of lanes per input) and a main pass (one group per output) on `stream`, no synchronisation; control flow is
+ *   the same for every row, only table addresses depend on the weights.  The workspace holds M, R mod M, the term lengths and the tables.
+ * mx_multiexp_shape: lanes per element and limbs per lane of the instance that serves a modulus of mod_bits bits, and
+ *   the window (the caller's when window > 0, else the one with the fewest Montgomery products whose tables stay within
+ *   1 GiB).  mx_multiexp_workspace_bytes: bytes mx_multiexp_run needs for rows of `limbs` words and `terms` terms.
+ * mx_multiexp_instances: the selectable (lanes, limbs per lane) pairs; returns their number and fills at most
+ *   max_entries of them.
+ * mx_response_rows:  d_z[r] = d_rho[r] + d_e[r] * d_x[r]  over the integers,  r < count: mx_dleq_response with a secret
+ *   row PER PROOF, d_x [count][wx]; everything else — widths, status byte, data-independent control flow and addresses —
+ *   as there.  A count of 0 returns MX_OK without a launch.
+ * MX_ERR_ARG for a null pointer, limbs, n_inputs, n_outputs or terms below 1 (or above MX_MULTIEXP_MAX_TERMS, 2^31 - 1
+ * rows), weight_bits outside 1 .. MX_MULTIEXP_MAX_WEIGHT_BITS, a term length outside 0 .. weight_bits, a window outside
+ * 1 .. 8 (0 .. 8 for the shape query) — the shape and the workspace query refuse the same counts as the run —;
+ * MX_ERR_MODULUS for an even modulus or one below 3; MX_ERR_SIZE for a modulus beyond the engine's widest;
+ * MX_ERR_WORKSPACE.  A refused call launches nothing. */
+#define MX_MULTIEXP_MAX_WEIGHT_BITS 16384
+#define MX_MULTIEXP_MAX_TERMS 65536
+int mx_multiexp_instances(int* lanes, int* limbs_per_lane, int max_entries);
+int mx_multiexp_shape(int mod_bits, int64_t n_inputs, int64_t n_outputs, int terms, int weight_bits, int window,
+                      int* lanes, int* limbs_per_lane_out, int* window_out);
+int64_t mx_multiexp_workspace_bytes(int mod_bits, int limbs, int64_t n_inputs, int terms, int window);
+int mx_multiexp_run(const uint32_t* h_mod, int limbs, const uint32_t* d_inputs, int64_t n_inputs, const int32_t* d_index,
+                    const uint32_t* d_weights, int terms, int weight_bits, const int32_t* h_term_bits, uint32_t* d_out,
+                    int64_t n_outputs, int window, void* d_workspace, int64_t workspace_bytes, void* stream);
+int mx_response_rows(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z, uint8_t* d_status,
+                     int wz, int ew, int wx, int64_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

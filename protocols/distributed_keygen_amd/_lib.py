@@ -55,6 +55,7 @@ class CrtEncPlan(ctypes.Structure):
 MX_PLAN_FIXED_WINDOW = 1      # include/mxpaillier.h
 MX_GEN_MAX_PARTIES = 16       # include/mxpaillier.h
 MX_SHA256_MAX_SETS = 8        # include/mxpaillier.h
+MX_MULTIEXP_MAX_WEIGHT_BITS = 16384      # include/mxpaillier.h
 MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
 
 _P4 = [POINTER(c_int)] * 4
@@ -174,6 +175,11 @@ SYMBOLS = {
     "mx_safe_double": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "mx_sha256_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "mx_dleq_response": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "mx_multiexp_instances": (c_int, [POINTER(c_int), POINTER(c_int), c_int]),
+    "mx_multiexp_shape": (c_int, [c_int, c_int64, c_int64, c_int, c_int, c_int, *[POINTER(c_int)] * 3]),
+    "mx_multiexp_workspace_bytes": (c_int64, [c_int, c_int, c_int64, c_int, c_int]),
+    "mx_multiexp_run": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_response_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
 }
 
 

@@ -2733,6 +2733,318 @@ class Engine:
         mark("compare")
         return verdict
 
+    # ------------------------------------------------------------------ range proofs of ciphertexts (range_proof.py)
+    def multiexp_mod_shape(self, mod: int, n_inputs: int, n_outputs: int, terms: int, weight_bits: int, window: int = 0) -> Tuple[int, int, int]:
+        """(lanes per element, limbs per lane, window) of mx_multiexp_shape for the modulus `mod`."""
+        return self._query("mx_multiexp_shape", int(mod).bit_length(), n_inputs, n_outputs, terms, weight_bits, int(window), outs=_INTS[:3])
+
+    @_int_args
+    def multiexp_mod_t(self, inputs_t, index_t, weights_t, terms: int, weight_bits: int, mod: int, window: int = 0,
+                       term_bits: Optional[Sequence[int]] = None, _checked: bool = False):
+        """out[r] = prod_{j < terms} inputs[index[r][j]] ^ w[r][j] mod `mod` for ANY odd modulus >= 3 (mx_multiexp_run,
+        csrc/mx_multiexp.hpp: the Straus form on the generic Montgomery arithmetic, a table pass and a main pass).
+        ``inputs_t`` ``[n_inputs, limbs]`` residues below `mod`, ``index_t`` int32 ``[rows, terms]`` in [0, n_inputs),
+        ``weights_t`` int32 ``[rows, terms * ww]`` (or any contiguous view of it) of non-negative weights of
+        ww = ceil(weight_bits / 32) little-endian words whose bits at and above ``weight_bits`` are 0; ``weight_bits``
+        in 1 .. 16384 whatever bits(mod) is.  ``term_bits``: one length per term, 0 .. weight_bits — the caller's promise
+        that the weights of term j are below 2^term_bits[j] in EVERY row; the windows above it skip that term (put the
+        longest term first: its table entry is fetched ahead of the squarings).  0^0 = 1.  Shared bases (every row the
+        same index) and per-row bases go through the same kernel.  Canonical residues ``[rows, limbs]``."""
+        _check_modulus(mod)
+        n_inputs, limbs = self._word_rows(inputs_t, "inputs")
+        if _limbs.limbs_for(mod) > limbs:
+            raise ValueError("rows narrower than the modulus")
+        if terms < 1 or not 1 <= weight_bits <= _lib.MX_MULTIEXP_MAX_WEIGHT_BITS:
+            raise ValueError(f"terms >= 1 and weight_bits in 1 .. {_lib.MX_MULTIEXP_MAX_WEIGHT_BITS} expected")
+        if not 0 <= window <= 8:
+            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
+        rows, _ = self._word_rows(index_t, "the index", terms)
+        ww = (weight_bits + 31) // 32
+        if (not _is_device_rows(weights_t) or weights_t.dtype != self.torch.int32 or not weights_t.is_contiguous()
+                or weights_t.device != self.device or weights_t.dim() < 2 or weights_t.shape[0] != rows or weights_t.numel() != rows * terms * ww):
+            raise ValueError(f"contiguous int32 device weights of {terms} x {ww} words per row expected")
+        if n_inputs < 1:
+            raise ValueError("at least one input expected")
+        c_term_bits = None
+        if term_bits is not None:
+            if len(term_bits) != terms or any(not 0 <= int(b) <= weight_bits for b in term_bits):
+                raise ValueError("one length in 0 .. weight_bits per term expected")
+            c_term_bits = (_ctypes.c_int32 * terms)(*[int(b) for b in term_bits])
+        out_t = self._empty_rows(limbs, rows)
+        if rows == 0:
+            return out_t
+        if not _checked and bool(((index_t < 0) | (index_t >= n_inputs)).any()):
+            raise ValueError("index out of range")
+        bits = mod.bit_length()
+        if window == 0:
+            window = self.multiexp_mod_shape(mod, n_inputs, rows, terms, weight_bits)[2]
+        h_mod = _limbs.pack_one(mod, limbs)
+        self._call("mx_multiexp_run", h_mod.ctypes.data, limbs, inputs_t.data_ptr(), n_inputs, index_t.data_ptr(), weights_t.data_ptr(),
+                   terms, weight_bits, c_term_bits, out_t.data_ptr(), rows, window,
+                   workspace=("mx_multiexp_workspace_bytes", bits, limbs, n_inputs, terms, window))
+        return out_t
+
+    @_int_args
+    def multiexp_mod_batch(self, bases: Sequence[Sequence[int]], weights: Sequence[Sequence[int]], mod: int, window: int = 0) -> List[int]:
+        """[prod_j bases[r][j] ^ weights[r][j] mod `mod` for r]: every row its own bases (taken modulo `mod`) and
+        non-negative weights, the same number of terms in every row — the int-level entry of ``multiexp_mod_t``."""
+        _check_modulus(mod)
+        if len(bases) != len(weights):
+            raise ValueError("one row of weights per row of bases expected")
+        if not bases:
+            return []
+        terms = len(bases[0])
+        if terms < 1 or any(len(b) != terms for b in bases) or any(len(w) != terms for w in weights):
+            raise ValueError("the same number of terms (at least one) in every row expected")
+        flat_w = [int(w) for row in weights for w in row]
+        if any(w < 0 for w in flat_w):
+            raise ValueError("non-negative weights expected")
+        weight_bits = max(1, max(w.bit_length() for w in flat_w))
+        ww = (weight_bits + 31) // 32
+        limbs = _limbs.limbs_for(mod)
+        rows = len(bases)
+        inputs_t = self._upload_ints([b for row in bases for b in row], limbs, mod)
+        index_t = self.torch.arange(rows * terms, device=self.device, dtype=self.torch.int32).view(rows, terms).contiguous()
+        weights_t = self.to_device(_limbs.pack(flat_w, ww).reshape(rows, terms * ww))
+        return self._download_ints(self.multiexp_mod_t(inputs_t, index_t, weights_t, terms, weight_bits, mod, window, _checked=True))
+
+    def response_rows_t(self, rho_t, e_t, x_t, out_t=None):
+        """(z, status): z[r] = rho[r] + e[r] * x[r] over the integers on the device (mx_response_rows,
+        csrc/mx_response.hpp) — ``dleq_response_t`` with a secret row PER PROOF: ``rho_t`` ``[count, wz]``, ``e_t``
+        ``[count, ew]``, ``x_t`` ``[count, wx]``, z ``[count, wz]`` (``out_t``), status uint8 ``[count]``: 1 where the sum
+        does not fit wz words (z then holds its low words)."""
+        count, wz = self._word_rows(rho_t, "rho rows")
+        _, ew = self._word_rows(e_t, "challenge rows")
+        _, wx = self._word_rows(x_t, "secret rows")
+        if e_t.shape[0] != count or x_t.shape[0] != count:
+            raise ValueError("one challenge row and one secret row per rho row expected")
+        if out_t is None:
+            out_t = self.torch.empty_like(rho_t)
+        elif self._word_rows(out_t, "z rows", wz)[0] != count:
+            raise ValueError("one z row per rho row expected")
+        status_t = self.torch.empty(count, dtype=self.torch.uint8, device=self.device)
+        if count:
+            self._call("mx_response_rows", rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(),
+                       wz, ew, wx, count)
+        return out_t, status_t
+
+    def _widened(self, rows_t, words: int):
+        """The rows zero-extended to `words` words (a copy only when they are narrower)."""
+        have = rows_t.shape[1]
+        if have == words:
+            return rows_t
+        out_t = self.torch.zeros((rows_t.shape[0], words), dtype=self.torch.int32, device=self.device)
+        out_t[:, :have] = rows_t
+        return out_t
+
+    def _term_weights(self, parts, ww: int):
+        """[count, len(parts), ww] weights from one row tensor per term, each zero-extended to ww words."""
+        return self.torch.stack([self._widened(p, ww) for p in parts], dim=1).contiguous()
+
+    def _const_rows(self, values: Sequence[int], words: int):
+        return self.to_device(_limbs.pack([int(v) for v in values], words).reshape(len(values), words))
+
+    # Which route a product of two powers of the range proofs takes (DESIGN §4.26 (b): measured at 10 000 rows).  With SHARED
+    # bases multiexp_kernel beats one modexp per term joined by a product from the 16-lane instances on (moduli above 2084
+    # bits: 87.8 against 89.9 ms at 4096) and loses below (17.2 against 14.5 ms at 2048); with per-row bases and a 128-bit
+    # exponent it loses at both lengths, so those products never take it.
+    RANGE_MULTIEXP_MIN_BITS = 2085
+
+    @classmethod
+    def range_uses_multiexp(cls, mod: int) -> bool:
+        """True iff the shared-base products modulo `mod` of the range proofs run through ``multiexp_mod_t``."""
+        return int(mod).bit_length() >= cls.RANGE_MULTIEXP_MIN_BITS
+
+    def _repeated_row(self, value: int, words: int, count: int):
+        return self._const_rows([value], words).repeat(count, 1).contiguous()
+
+    def _shared_pair_t(self, base0: int, base1: int, w0_t, w1_t, mod: int, bits0: int, bits1: int, route: Optional[str] = None):
+        """base0^(w0[r]) * base1^(w1[r]) mod `mod` for weights below 2^bits0 and 2^bits1.  Route "multiexp": ONE
+        ``multiexp_mod_t`` launch whose two tables every row shares, the longer term first and the windows above the shorter
+        one skipping it.  Route "modexps": one ``powmod_multi_t`` per term — a group per row, the modulus row repeated — and
+        ``mulmod_t`` to join them.  None: whichever measured faster at this length (``range_uses_multiexp``)."""
+        if bits1 > bits0:
+            base0, base1, w0_t, w1_t, bits0, bits1 = base1, base0, w1_t, w0_t, bits1, bits0
+        count = w0_t.shape[0]
+        lm = _limbs.limbs_for(mod)
+        if route is None:
+            route = "multiexp" if self.range_uses_multiexp(mod) else "modexps"
+        if route == "modexps":
+            mods = (self._repeated_row(mod, lm, count), mod.bit_length())
+            out_t = self.powmod_multi_t(self._repeated_row(base0 % mod, lm, count), mods, (w0_t, bits0), 1)
+            return self.mulmod_t(out_t, self.powmod_multi_t(self._repeated_row(base1 % mod, lm, count), mods, (w1_t, bits1), 1), mod, out_t=out_t)
+        ww = max(w0_t.shape[1], w1_t.shape[1])
+        index_t = self.torch.tensor([[0, 1]], dtype=self.torch.int32, device=self.device).repeat(count, 1).contiguous()
+        return self.multiexp_mod_t(self._const_rows([base0 % mod, base1 % mod], lm), index_t, self._term_weights([w0_t, w1_t], ww), 2, 32 * ww,
+                                   mod, term_bits=(bits0, bits1), _checked=True)
+
+    def _own_pair_index(self, count: int):
+        """index (r, count + r): row r of the first and of the second block of a two-block input tensor."""
+        torch = self.torch
+        own = torch.arange(count, device=self.device, dtype=torch.int32).view(-1, 1)
+        return torch.cat([own, own + count], dim=1).contiguous()
+
+    def _one_and(self, e_t):
+        """[count, 2, ew] weights (1, e[r])."""
+        one_t = self.torch.zeros_like(e_t)
+        one_t[:, 0] = 1
+        return self._term_weights([one_t, e_t], e_t.shape[1])
+
+    def _own_pair_t(self, first_t, second_t, e_t, mod: int, route: str = "modexps"):
+        """first[r] * second[r]^(e[r]) mod `mod`, per-row bases.  Route "modexps" (what the proofs take: it measured faster
+        at every length): ``powmod_multi_t`` with a group per row and ``mulmod_t``.  Route "multiexp": ONE ``multiexp_mod_t``
+        launch, the 128-bit term first and the term of weight 1 confined to the lowest window."""
+        torch = self.torch
+        count, ew = e_t.shape
+        if route == "modexps":
+            mods = (self._repeated_row(mod, first_t.shape[1], count), mod.bit_length())
+            return self.mulmod_t(first_t, self.powmod_multi_t(second_t, mods, (e_t, 32 * ew), 1), mod)
+        one_t = torch.zeros_like(e_t)
+        one_t[:, 0] = 1
+        own = torch.arange(count, device=self.device, dtype=torch.int32).view(-1, 1)
+        index_t = torch.cat([own + count, own], dim=1).contiguous()
+        return self.multiexp_mod_t(torch.cat([first_t, second_t]), index_t, self._term_weights([e_t, one_t], ew), 2, 32 * ew,
+                                   mod, term_bits=(32 * ew, 1), _checked=True)
+
+    def _one_plus_mn_t(self, m_t, n: int):
+        """1 + m[r] n as rows of the width of n^2, for m[r] below n — (1 + n)^m mod n^2 without an exponentiation: one
+        multiply-add modulo n^2 (mx_fma_mod)."""
+        count = m_t.shape[0]
+        limbs2 = _limbs.limbs_for(n * n)
+        return self.shamir_fma_t(self._widened(m_t, limbs2), self._repeated_row(n, limbs2, count), self._repeated_row(1, limbs2, count), n * n)
+
+    def _reduce_wide_t(self, rows_t, n: int):
+        """rows below 2^(bits(n) + 64) -> their residues modulo n as ``[count, limbs(n)]`` rows: the row is cut at the
+        highest word boundary k below bits(n) (lo < 2^k < n, hi < 2^96) and hi * 2^k + lo goes through mx_fma_mod."""
+        ln = _limbs.limbs_for(n)
+        kw = (n.bit_length() - 1) // 32
+        if kw < 1 or ln < 3 or rows_t.shape[1] < kw + 3:
+            raise ValueError("a modulus of at least 96 bits expected")
+        lo_t = self._widened(rows_t[:, :kw].contiguous(), ln)
+        hi_t = self._widened(rows_t[:, kw : kw + 3].contiguous(), ln)
+        pow_t = self._const_rows([1 << (32 * kw)], ln).repeat(rows_t.shape[0], 1).contiguous()
+        return self.shamir_fma_t(hi_t, pow_t, lo_t, n)
+
+    @staticmethod
+    def range_shape(n: int, nh: int, bits: int) -> Dict[str, int]:
+        """Bit lengths and row widths of a range proof (tools/range_model.py: shape).  ValueError unless
+        1 <= bits and bits + 258 <= bits(n) - 1."""
+        nb, hb = int(n).bit_length(), int(nh).bit_length()
+        if bits < 1 or bits + 258 > nb - 1:
+            raise ValueError(f"a claimed length of 1 .. bits(N) - 259 = {nb - 259} bits expected (l + E + K + 2 <= bits(N) - 1)")
+        out = dict(alpha_bits=bits + 256, mu_bits=hb + 128, gamma_bits=hb + 384, rho_bits=nb + 64, z1_bits=bits + 257, z3_bits=hb + 385)
+        out.update(z1_words=(out["z1_bits"] + 31) // 32, z3_words=(out["z3_bits"] + 31) // 32, limbs_n=_limbs.limbs_for(n),
+                   limbs2=_limbs.limbs_for(n * n), limbs_h=_limbs.limbs_for(nh))
+        return out
+
+    def _range_challenge_t(self, ctx: bytes, cts_t, s_t, a_t, c_t):
+        """The 128-bit challenge rows over four row sets of two widths."""
+        return self.sha256_rows_t(ctx, [cts_t, s_t, a_t, c_t])[:, 4:8].contiguous()
+
+    @_int_args
+    def range_prove_t(self, cts_t, messages_t, randomness_t, n: int, nh: int, s: int, t: int, bits: int, ctx: bytes, rng=None,
+                      draws=None, message_bits: Optional[int] = None, _stages: Optional[List[Any]] = None):
+        """The proofs (S, A, C, z1, z2, z3) that the ciphertexts ``cts_t`` = (1 + n)^m r^n hold messages of ``bits``
+        bits (range_proof.py; tools/range_model.py is the model): ``messages_t`` ``[count, z1_words]`` rows of m,
+        ``randomness_t`` ``[count, limbs(n)]`` rows of r below n, (nh, s, t) the verifier's parameters.  The four
+        draws alpha, mu, gamma, rho' come from ``rng`` (a ``DeviceRng``: four consecutive calls in this order) or are the
+        rows ``draws`` a test passes.  ``message_bits``: a bound on the length of every message, ``bits`` .. 32 z1_words
+        (default: the row width — the rows may hold messages beyond 2^bits, which the proof's slack admits); the modexp
+        of the message term is as long as it says, and a message beyond it is a ValueError.  Nothing per row leaves the
+        device.  `_stages`, a list, receives (name, end event) pairs for tools/range_proof_probe.py."""
+        sh = self.range_shape(n, nh, bits)
+        _check_modulus(nh)
+        message_bits = 32 * sh["z1_words"] if message_bits is None else int(message_bits)
+        if not bits <= message_bits <= 32 * sh["z1_words"]:
+            raise ValueError("message_bits in bits .. 32 z1_words expected")
+        count, _ = self._word_rows(cts_t, "ciphertext rows", sh["limbs2"])
+        if self._word_rows(messages_t, "message rows", sh["z1_words"])[0] != count:
+            raise ValueError("one message row per ciphertext expected")
+        if self._word_rows(randomness_t, "randomness rows", sh["limbs_n"])[0] != count:
+            raise ValueError("one randomness row per ciphertext expected")
+        if (rng is None) == (draws is None):
+            raise ValueError("exactly one of rng and draws expected")
+        if draws is None:
+            draws = (rng.rows_t(self, count, sh["alpha_bits"], sh["z1_words"]), rng.rows_t(self, count, sh["mu_bits"]),
+                     rng.rows_t(self, count, sh["gamma_bits"], sh["z3_words"]), rng.rows_t(self, count, sh["rho_bits"], sh["limbs2"]))
+        alpha_t, mu_t, gamma_t, rho_t = draws
+        if count and message_bits < 32 * sh["z1_words"] and not bool(self._rows_below(messages_t, 1 << message_bits).all()):
+            raise ValueError("a message is longer than message_bits")
+        for d_t, what, words in ((alpha_t, "alpha rows", sh["z1_words"]), (mu_t, "mu rows", (sh["mu_bits"] + 31) // 32),
+                                 (gamma_t, "gamma rows", sh["z3_words"]), (rho_t, "rho rows", sh["limbs2"])):
+            if self._word_rows(d_t, what, words)[0] != count:
+                raise ValueError(f"one of the {what} per ciphertext expected")
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        s_t = self._shared_pair_t(s, t, messages_t, mu_t, nh, message_bits, sh["mu_bits"])
+        c_t = self._shared_pair_t(s, t, alpha_t, gamma_t, nh, sh["alpha_bits"], sh["gamma_bits"])
+        mark("multiexp_aux")
+        a_t = self.powmod_nsquare_t(rho_t, n, n)
+        mark("r_pow_n")
+        a_t = self.mulmod_t(a_t, self._one_plus_mn_t(alpha_t, n), n * n, out_t=a_t)          # (alpha < 2^(bits + 256) < n)
+        mark("multiexp_n2")
+        e_t = self._range_challenge_t(ctx, cts_t, s_t, a_t, c_t)
+        mark("hash")
+        z1_t, _ = self.response_rows_t(alpha_t, e_t, messages_t)
+        z3_t, _ = self.response_rows_t(gamma_t, e_t, mu_t)
+        mark("response")
+        z2_t = self._own_pair_t(self._reduce_wide_t(rho_t, n), randomness_t, e_t, n)
+        mark("multiexp_n")
+        return s_t, a_t, c_t, z1_t, z2_t, z3_t
+
+    @_int_args
+    def range_bounds_t(self, cts_t, s_t, a_t, c_t, z1_t, z2_t, z3_t, n: int, nh: int, bits: int):
+        """bool ``[count]``: the range checks of ``range_verify_t`` — S, C < nh, A, c < n^2, z2 < n, z1 < 2^(bits + 257),
+        z3 < 2^(bits(nh) + 385) — as row compares in torch; what fails them is never read by a kernel."""
+        sh = self.range_shape(n, nh, bits)
+        n2 = n * n
+        return (self._rows_below(s_t, nh) & self._rows_below(c_t, nh) & self._rows_below(a_t, n2) & self._rows_below(cts_t, n2)
+                & self._rows_below(z2_t, n) & self._rows_below(z1_t, 1 << sh["z1_bits"]) & self._rows_below(z3_t, 1 << sh["z3_bits"]))
+
+    @_int_args
+    def range_verify_t(self, cts_t, s_t, a_t, c_t, z1_t, z2_t, z3_t, n: int, nh: int, s: int, t: int, bits: int, ctx: bytes,
+                       _stages: Optional[List[Any]] = None):
+        """bool ``[count]``: row r is True iff S, C < nh, A, c < n^2, z2 < n, z1 < 2^(bits + 257), z3 < 2^(bits(nh) + 385),
+        (1 + n)^z1 z2^n = A c^e (mod n^2) and s^z1 t^z3 = C S^e (mod nh) with e recomputed from the hash — the verdicts
+        of the proofs of ``range_prove_t``, one per row; a bad row never raises.  Out-of-range rows are replaced by 1
+        (z1 and z3 by 0) before anything is computed from them.  No inverse of anything the prover sent is taken."""
+        torch = self.torch
+        sh = self.range_shape(n, nh, bits)
+        _check_modulus(nh)
+        count, _ = self._word_rows(cts_t, "ciphertext rows", sh["limbs2"])
+        for r_t, what, words in ((s_t, "S rows", sh["limbs_h"]), (a_t, "A rows", sh["limbs2"]), (c_t, "C rows", sh["limbs_h"]),
+                                 (z1_t, "z1 rows", sh["z1_words"]), (z2_t, "z2 rows", sh["limbs_n"]), (z3_t, "z3 rows", sh["z3_words"])):
+            if self._word_rows(r_t, what, words)[0] != count:
+                raise ValueError(f"one of the {what} per ciphertext expected")
+        if count == 0:
+            return torch.ones(0, dtype=torch.bool, device=self.device)
+        n2 = n * n
+        ok = self.range_bounds_t(cts_t, s_t, a_t, c_t, z1_t, z2_t, z3_t, n, nh, bits)
+        keep = ok.view(-1, 1)
+
+        def harmless(rows_t, value: int):
+            fill = torch.zeros((1, rows_t.shape[1]), dtype=torch.int32, device=self.device)
+            fill[0, 0] = value
+            return torch.where(keep, rows_t, fill).contiguous()
+
+        cts_t, s_t, a_t, c_t, z2_t = (harmless(r_t, 1) for r_t in (cts_t, s_t, a_t, c_t, z2_t))
+        z1_t, z3_t = harmless(z1_t, 0), harmless(z3_t, 0)
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        e_t = self._range_challenge_t(ctx, cts_t, s_t, a_t, c_t)
+        mark("hash")
+        left_t = self.powmod_nsquare_t(self._widened(z2_t, sh["limbs2"]), n, n)
+        mark("r_pow_n")
+        left_t = self.mulmod_t(left_t, self._one_plus_mn_t(z1_t, n), n2, out_t=left_t)          # (z1 < 2^(bits + 257) < n past the range check)
+        right_t = self.multiexp_nsquare_rows_t(torch.cat([a_t, cts_t]), self._own_pair_index(count), self._one_and(e_t), 2, 128, n, _checked=True)
+        mark("multiexp_n2")
+        left_h = self._shared_pair_t(s, t, z1_t, z3_t, nh, sh["z1_bits"], sh["z3_bits"])
+        right_h = self._own_pair_t(c_t, s_t, e_t, nh)
+        mark("multiexp_aux")
+        verdict = ok & (left_t == right_t).all(dim=1) & (left_h == right_h).all(dim=1)
+        mark("compare")
+        return verdict
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):
