@@ -149,8 +149,39 @@ typedef struct mx_nsquare_plan {
                            * before this field carried it): the pivot of the knob at the time of the run. */
   int32_t n_slot_reads;   /* pair slots (2 * limbs_per_lane words per lane) one exponentiation reads from ... */
   int32_t n_slot_writes;  /* ... and writes to the workspace: the kernel's HBM traffic model */
+  /* The lifted tape.  For a = b (mod N), a^N = b^N (mod N^2); so with exp = e1 N + e0, 0 <= e0 < N,
+   *     x^exp = (x^e1 mod N)^N * x^e0   (mod N^2):
+   * x^e1 modulo N is the chain of FIRST digits of the pair arithmetic — pass 1 of a squaring or multiplication, no pass
+   * 2 — and y^N x^e0 is one two-base sliding-window exponentiation whose bits(N) squarings both bases share.  For the
+   * 4197-bit share exponent of key_length 2048 that is ~2145 first-digit and ~2050 pair squarings instead of 4196 pair
+   * squarings: ~0.81 of the instructions by the planner's model.  prepare builds this tape NEXT TO the classic one whenever
+   * exp >= N (never for MX_PLAN_FIXED_WINDOW plans, whose point is a sequence that depends on the exponent's length
+   * only, and never for exp < N, which covers every encryption-type exponent) and marks it as preferred where its
+   * estimated cost is lower; mx_powmod_nsquare_run takes it for one-wavefront launches (wavefronts_per_group 1) as
+   * MX_KNOB_N2_LIFT says.  The two-wavefront, time-sliced and five-wavefront forms always read the classic tape.
+   * n_sqr, n_mul, n_slot_reads and n_slot_writes above describe the tape a one-wavefront launch runs by default: the
+   * lifted one where `lift` has bit 1 set (n_sqr and n_mul then count its PAIR operations only), else the classic one.
+   * Same results bit for bit either way.  A descriptor with these fields zero is a plan without a lifted tape. */
+  int32_t n_sqr_first;    /* first-digit squarings of that tape (0: the classic tape) */
+  int32_t n_mul_first;    /* first-digit multiplications of that tape */
+  int32_t table_rows;     /* pair slots of the table region (from slot 8 on) that the largest of the plan's tapes needs */
+  int32_t lift;           /* bit 0: the plan holds a lifted tape; bit 1: the planner's cost model prefers it */
+  int32_t ntape_lift;     /* words of the lifted tape */
+  int32_t n_sqr_classic;  /* pair squarings and ... */
+  int32_t n_mul_classic;  /* ... multiplications of the classic tape, whichever is the default */
+  int32_t lift_positions; /* lifted tape: squarings of either kind (tape positions), ... */
+  int32_t lift_pos1;      /* ... those in front of its second phase, and ... */
+  int32_t lift_share1;    /* ... their share of the tape's estimated cost, in 1/65536: run cuts segments by cost */
 } mx_nsquare_plan;
 int64_t mx_nsquare_plan_bytes(int limbs_n, int exp_limbs);
+/* Host only (no device, no stream): the tape prepare_ex would write for (N, exp, flags) — lifted = 0 the classic tape,
+ * 1 the lifted one — into h_tape[0 .. max_words), and the descriptor's counting fields into *plan (d_plan = NULL).
+ * Word = (op << 28) | argument; ops 0 SQR k, 1 MUL slot, 2 ADD slot, 3 LOAD slot, 4 STORE slot, 5 MULC slot (the last
+ * product), 6 SQR0 k, 7 MUL0 slot (first-digit forms), 8 CLR1 (second digit := 0); slots 0-7 constants and scratch,
+ * 8.. table rows.  Returns the number of words (0: no such tape for this plan), MX_ERR_WORKSPACE if max_words is too
+ * small, or the error prepare_ex would return.  For checking the schedule on a machine without a GPU. */
+int mx_nsquare_tape(const uint32_t* h_n, const uint32_t* h_exp, int limbs_n, int exp_limbs, int flags, int lifted,
+                    uint32_t* h_tape, int max_words, mx_nsquare_plan* plan);
 int mx_powmod_nsquare_prepare(mx_nsquare_plan* plan, const uint32_t* h_n, const uint32_t* h_exp, int limbs_n,
                               int exp_limbs, void* d_plan, int64_t plan_bytes, void* stream);
 /* The same with options (flags = 0: exactly mx_powmod_nsquare_prepare).
@@ -161,7 +192,9 @@ int mx_powmod_nsquare_prepare(mx_nsquare_plan* plan, const uint32_t* h_n, const 
  * kernel-trace of a profiler, depend on the exponent's LENGTH only.  The table row a window reads is still selected by
  * the secret digit (addresses, not timing of the instruction stream).  Cost: 728 instead of 592 pair multiplications
  * for a 4197-bit exponent (w = 7: a 127-row table instead of 64 odd powers, twice the workspace) = +3.6 % instructions.  plan->window then reports w + 1 (the
- * table region is sized as 2^(window - 1) rows either way).  Same results bit for bit. */
+ * table region is sized as 2^(window - 1) rows either way).  Same results bit for bit.  A fixed-window plan holds no
+ * lifted tape (mx_nsquare_plan): the split of the exponent at N and the merged windows of its second phase would make
+ * the sequence of operations depend on more than the exponent's length. */
 #define MX_PLAN_FIXED_WINDOW 1
 int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_t* h_n, const uint32_t* h_exp, int limbs_n,
                                  int exp_limbs, int flags, void* d_plan, int64_t plan_bytes, void* stream);
@@ -329,6 +362,9 @@ int mx_selftest_lanes(void* stream);
 #define MX_KNOB_LAT_LANES 8         /* 3-limb latency forms of the generic kernel: at least this many lanes per element (0 = the smallest group that holds the number) */
 #define MX_KNOB_N2_BIPAIR 9         /* 1 = mx_powmod_nsquare_run never chooses the five-wavefront latency form by itself (A/B runs) */
 #define MX_KNOB_BI_PIVOT 7          /* bipartite form of the generic kernel: multiplier limbs on the Montgomery wavefront (0 = the library's pivot) */
+#define MX_KNOB_N2_LIFT 10          /* the lifted tape of mx_powmod_nsquare_run's one-wavefront launches (mx_nsquare_plan): 0 = never, 1 = whenever the plan
+                                     * holds one, 2 = where the planner's cost model prefers it — the default, so for THIS knob 2, not 0, restores it.  Read
+                                     * by run, not by prepare: a plan prepared under one value runs correctly under any other */
 int mx_debug_knob(int knob, int value);
 /* Enqueues a kernel of ONE wavefront that idles for `microseconds` (0..1 000 000) on `stream` and touches no
  * memory.  A concurrency probe: two streams that the HIP runtime has mapped to the same hardware queue run

@@ -21,6 +21,11 @@ class NsquarePlan(ctypes.Structure):
         ("exp_bits", ctypes.c_int32), ("window", ctypes.c_int32), ("ntape", ctypes.c_int32),
         ("n_sqr", ctypes.c_int32), ("n_mul", ctypes.c_int32), ("geometries", ctypes.c_int32),
         ("n_slot_reads", ctypes.c_int32), ("n_slot_writes", ctypes.c_int32),
+        # the lifted tape (one-wavefront launches; header of mx_nsquare_plan)
+        ("n_sqr_first", ctypes.c_int32), ("n_mul_first", ctypes.c_int32), ("table_rows", ctypes.c_int32),
+        ("lift", ctypes.c_int32), ("ntape_lift", ctypes.c_int32), ("n_sqr_classic", ctypes.c_int32),
+        ("n_mul_classic", ctypes.c_int32), ("lift_positions", ctypes.c_int32), ("lift_pos1", ctypes.c_int32),
+        ("lift_share1", ctypes.c_int32),
     ]
 
 
@@ -75,6 +80,7 @@ SYMBOLS = {
     "mx_nsquare_plan_bytes": (c_int64, [c_int, c_int]),
     "mx_powmod_nsquare_prepare": (c_int, [POINTER(NsquarePlan), c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_powmod_nsquare_prepare_ex": (c_int, [POINTER(NsquarePlan), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "mx_nsquare_tape": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, POINTER(NsquarePlan)]),
     "mx_powmod_nsquare_run_workspace_bytes": (c_int64, [POINTER(NsquarePlan), c_int64]),
     "mx_powmod_nsquare_run": (c_int, [POINTER(NsquarePlan), c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mx_nsquare_launch_shape": (c_int, [c_int, c_int64, c_int, c_int, *_P4, POINTER(c_int)]),

@@ -42,7 +42,8 @@ inline int max_lanes(int lpl, int wpg) {
 
 constexpr int N2_TIMESLICE_MAX_SEGMENTS = mx::N2_TS_LEVELS;      // units per group of a time-sliced launch, at most
 
-bool shape_n2(int n_bits, int window, int64_t batch, int limbs_per_lane, int wpg, N2Shape& p) {
+// table_rows: pair slots of the table region (2^(window - 1) odd powers for a classic tape; the shape queries pass 1)
+bool shape_n2(int n_bits, int table_rows, int64_t batch, int limbs_per_lane, int wpg, N2Shape& p) {
   if (wpg == 4) {                                                // the five-wavefront latency form (mx_bipair.hpp) shares the
     if (limbs_per_lane != LIMBS_PER_LANE_LAT) return false;      // slots of the two-wavefront 3-limb form
     wpg = 2;
@@ -53,7 +54,7 @@ bool shape_n2(int n_bits, int window, int64_t batch, int limbs_per_lane, int wpg
   int gpw = (64 / p.geo.K) * (wpg == 2 ? mx::N2_SPLIT_PAIRS : 1);      // elements per workgroup
   p.nblocks = (batch + gpw - 1) / gpw;
   p.nlanes = p.nblocks * 64 * (wpg == 2 ? mx::N2_SPLIT_PAIRS : 1);
-  p.nslots = mx::N2_SLOT_TABLE + (1 << (window - 1));
+  p.nslots = mx::N2_SLOT_TABLE + table_rows;
   p.table_bytes = align256((int64_t)p.nslots * 2 * p.geo.L * p.nlanes * 4);
   p.groups = (batch + 64 / p.geo.K - 1) / (64 / p.geo.K);
   p.sched_bytes = wpg == 2 ? align256((mx::N2_TS_HEADER + p.groups * (N2_TIMESLICE_MAX_SEGMENTS - 1)) * 4) : 0;
@@ -285,6 +286,9 @@ inline int64_t bipair_fold_bytes() { return align256((int64_t)mx::BI_ROWS * 3 * 
 inline int64_t bipair_quot_bytes() { return align256((int64_t)mx::BP_QROWS * 3 * 64 * 4); }
 inline int64_t bipair_section_bytes(int limbs_n) { return n2_consts_bytes(limbs_n) + bipair_fold_bytes() + bipair_quot_bytes(); }
 inline int64_t bipair_section_offset(int limbs_n) { return N2_GEOS * n2_consts_bytes(limbs_n) + align256((int64_t)MAX_SLIDING_OPS * 4); }
+// the lifted tape of a plan (mx_nsquare_plan::lift), behind that section: the layout in front of it is that of older plans
+inline int64_t n2_tape_bytes() { return align256((int64_t)MAX_SLIDING_OPS * 4); }
+inline int64_t lifted_tape_offset(int limbs_n) { return bipair_section_offset(limbs_n) + bipair_section_bytes(limbs_n); }
 constexpr int N2_GEO_BIPAIR = 8;      // mx_nsquare_plan::geometries: the plan holds the constants of the five-wavefront form
 constexpr int N2_GEO_PIVOT_SHIFT = 8; // ... and, in bits 8-15, the pivot those constants were built with (0: a plan of an older library)
 
@@ -297,14 +301,14 @@ struct N2Launch {
 };
 // Refuses, in this order: a batch, limbs_per_lane or wavefronts_per_group that no launch takes (MX_ERR_ARG), then a
 // combination without an instance for this modulus (MX_ERR_SIZE).
-int resolve_n2(int n_bits, int64_t batch, int limbs_per_lane, int wpg, int window, N2Launch& r) {
+int resolve_n2(int n_bits, int64_t batch, int limbs_per_lane, int wpg, int table_rows, N2Launch& r) {
   if (batch <= 0) return MX_ERR_ARG;
   if (limbs_per_lane != 0 && geo_index(limbs_per_lane) < 0) return MX_ERR_ARG;
   if (wpg < 0 || (wpg > 2 && wpg != 4)) return MX_ERR_ARG;
   if (wpg == 4 && limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) return MX_ERR_SIZE;      // explicit only with 3 limbs
   r.ch = n2_auto_shape(n_bits, batch, limbs_per_lane, wpg);
   if (r.ch.wpg == 4 && !bipair_geometry(n_bits, r.bi)) return MX_ERR_SIZE;
-  if (!shape_n2(n_bits, window, batch, r.ch.lpl, r.ch.wpg, r.p)) return MX_ERR_SIZE;
+  if (!shape_n2(n_bits, table_rows, batch, r.ch.lpl, r.ch.wpg, r.p)) return MX_ERR_SIZE;
   r.friendly = r.ch.wpg == 4 || n2_friendly_instance(r.p.geo, r.ch.wpg, n_bits);
   return MX_OK;
 }
@@ -463,7 +467,7 @@ extern "C" int mx_nsquare_geometry(int n_bits, int64_t batch, int* k, int* l, in
 
 extern "C" int64_t mx_nsquare_plan_bytes(int limbs_n, int exp_limbs) {
   if (limbs_n <= 0 || exp_limbs <= 0) return MX_ERR_ARG;
-  return bipair_section_offset(limbs_n) + bipair_section_bytes(limbs_n);
+  return lifted_tape_offset(limbs_n) + n2_tape_bytes();
 }
 
 extern "C" int mx_powmod_nsquare_prepare(mx_nsquare_plan* plan, const uint32_t* h_n, const uint32_t* h_exp,
@@ -520,6 +524,224 @@ static int prepare_bipair_section(const u32* h_n, int limbs_n, int bits, char* b
   return MX_OK;
 }
 
+// ---- the tapes of a plan (mx_powmod_n2.hpp): host arithmetic only
+namespace {
+struct N2Tape {
+  std::vector<u32> words;
+  int n_sqr = 0, n_mul = 0, n_sqr0 = 0, n_mul0 = 0;
+  int half_reads = 0, n_writes = 6;          // digits read from slots; the prologue writes 4 constant pairs and x_lo, x_hi
+  int top_slot = mx::N2_SLOT_TABLE;          // the highest slot the tape touches
+  int64_t cost = 0;                          // N2_COST_* units (mx_host.hpp)
+  void emit(u32 op, int arg) {
+    words.push_back((op << 28) | (u32)arg);
+    switch (op) {
+      case mx::N2_SQR: n_sqr += arg; cost += (int64_t)arg * N2_COST_SQR; return;
+      case mx::N2_SQR0: n_sqr0 += arg; cost += (int64_t)arg * N2_COST_SQR0; return;
+      case mx::N2_CLR1: return;
+      case mx::N2_MUL: case mx::N2_MULC: n_mul += 1; half_reads += 2; cost += N2_COST_MUL; break;
+      case mx::N2_MUL0: n_mul0 += 1; half_reads += 1; cost += N2_COST_MUL0; break;
+      case mx::N2_STORE: n_writes += 1; break;
+      default: half_reads += 2; break;       // N2_ADD, N2_LOAD
+    }
+    if (arg > top_slot) top_slot = arg;
+  }
+  int reads() const { return (half_reads + 1) / 2; }
+  int rows() const { return top_slot - mx::N2_SLOT_TABLE + 1; }
+  // x = (x_lo, 0) * K1 + (x_hi, 0) * K2, the first row of the table of every schedule
+  void convert() {
+    emit(mx::N2_LOAD, mx::N2_SLOT_LO); emit(mx::N2_MUL, mx::N2_SLOT_K1); emit(mx::N2_STORE, mx::N2_SLOT_TMP);
+    emit(mx::N2_LOAD, mx::N2_SLOT_HI); emit(mx::N2_MUL, mx::N2_SLOT_K2); emit(mx::N2_ADD, mx::N2_SLOT_TMP);
+    emit(mx::N2_STORE, mx::N2_SLOT_TABLE);
+  }
+  // the odd powers 3, 5, .. of the accumulator — which row `first` holds already — into the rows behind it
+  void odd_powers(int first, int nodd) {
+    if (nodd <= 1) return;
+    emit(mx::N2_SQR, 1); emit(mx::N2_STORE, mx::N2_SLOT_SQ); emit(mx::N2_LOAD, first);
+    for (int t = 1; t < nodd; ++t) { emit(mx::N2_MUL, mx::N2_SLOT_SQ); emit(mx::N2_STORE, first + t); }
+  }
+};
+struct N2Tapes {
+  N2Tape classic, lifted;      // lifted.words empty: none
+  int ebits = 0, window = 1;
+  bool prefer_lifted = false;
+  int lift_pos1 = 0, lift_share1 = 0;
+};
+
+// Rows that the table region of a plan may have: what a fixed-window plan of a long exponent takes today (2^7), so that
+// the lifted tape — two tables — never asks a caller for a larger workspace per element than the engine already hands out.
+// Where both tables at their best widths would not fit, the planner narrows them (the window for N first in its search:
+// width 5 instead of 7 costs ~1 % more instructions).
+constexpr int N2_MAX_TABLE_ROWS = 128;
+
+// The lifted tape (header of mx_nsquare_plan) for exp = e1 N + e0, e1 >= 1:
+//   conversion and the odd powers of x | phase 1: sliding window over e1 with first-digit operations, multipliers the
+//   first digits of that table | second digit := 0, the pair (Y0, 0) — a representative of x^e1 modulo N — and its odd
+//   powers into a second table | phase 2: ONE chain of max(bits N, bits e0) - 1 pair squarings, a multiplication from the
+//   y-table where a window of N ends and from the x-table where a window of e0 ends | times E.
+// The three window widths are those that minimise the cost in N2_COST_* units, by exhaustive search over the exact
+// recodings (8^3 candidates of a few thousand bits: microseconds).
+void build_lifted(const u32* h_n, int limbs_n, const u32* h_exp, int exp_limbs, N2Tapes& tp) {
+  std::vector<u32> e1(exp_limbs, 0u), e0(limbs_n, 0u);
+  divmod_words(e1.data(), e0.data(), h_exp, exp_limbs, h_n, limbs_n);
+  const bool has0 = bit_length(e0.data(), limbs_n) > 0;
+  if (bit_length(e1.data(), exp_limbs) < (has0 ? 1 : 2)) return;      // exp <= N: nothing to lift
+  constexpr int WMAX = 8;
+  std::vector<SlidingWin> r1[WMAX + 1], rn[WMAX + 1], r0[WMAX + 1];
+  for (int w = 1; w <= WMAX; ++w) {
+    r1[w] = sliding_windows(e1.data(), exp_limbs, w);
+    rn[w] = sliding_windows(h_n, limbs_n, w);
+    if (has0) r0[w] = sliding_windows(e0.data(), limbs_n, w);
+  }
+  auto table_cost = [](int nodd) { return nodd > 1 ? (int64_t)N2_COST_SQR + (int64_t)(nodd - 1) * N2_COST_MUL : (int64_t)0; };
+  int b1 = 0, bn = 0, b0 = 0;
+  int64_t best = -1;
+  for (int w1 = 1; w1 <= WMAX; ++w1)
+    for (int w0 = 1; w0 <= (has0 ? WMAX : 1); ++w0)
+      for (int wn = 1; wn <= WMAX; ++wn) {
+        const int rows_x = 1 << (std::max(w1, has0 ? w0 : 1) - 1), rows_y = 1 << (wn - 1);
+        if (rows_x + rows_y > N2_MAX_TABLE_ROWS) continue;
+        const int chain = std::max(rn[wn][0].low, has0 ? r0[w0][0].low : 0);
+        const int64_t c = table_cost(rows_x) + table_cost(rows_y) + (int64_t)r1[w1][0].low * N2_COST_SQR0 +
+                          (int64_t)(r1[w1].size() - 1) * N2_COST_MUL0 + (int64_t)chain * N2_COST_SQR +
+                          (int64_t)(rn[wn].size() + (has0 ? r0[w0].size() : 0) - 1) * N2_COST_MUL;
+        if (best < 0 || c < best) { best = c; b1 = w1; b0 = w0; bn = wn; }
+      }
+  N2Tape& t = tp.lifted;
+  const int rows_x = 1 << (std::max(b1, has0 ? b0 : 1) - 1), rows_y = 1 << (bn - 1);
+  const int xtab = mx::N2_SLOT_TABLE, ytab = mx::N2_SLOT_TABLE + rows_x;
+  t.convert();
+  t.odd_powers(xtab, rows_x);
+  // phase 1 (N2_LOAD brings the row's second digit along: nothing reads it, N2_CLR1 drops it)
+  const std::vector<SlidingWin>& s1 = r1[b1];
+  t.emit(mx::N2_LOAD, xtab + (int)s1[0].index1 - 1);
+  for (size_t i = 1; i < s1.size(); ++i) {
+    t.emit(mx::N2_SQR0, s1[i - 1].low - s1[i].low);
+    t.emit(mx::N2_MUL0, xtab + (int)s1[i].index1 - 1);
+  }
+  if (s1.back().low) t.emit(mx::N2_SQR0, s1.back().low);
+  t.emit(mx::N2_CLR1, 0);
+  t.emit(mx::N2_STORE, ytab);
+  t.odd_powers(ytab, rows_y);
+  tp.lift_pos1 = t.n_sqr + t.n_sqr0;
+  const int64_t cost1 = t.cost;
+  // phase 2: the windows of N and of e0 merged by the position of their lowest bit (N first where they coincide)
+  const std::vector<SlidingWin>& sn = rn[bn];
+  const std::vector<SlidingWin> none;
+  const std::vector<SlidingWin>& s0 = has0 ? r0[b0] : none;
+  size_t in = 0, i0 = 0;
+  int pos = -1;
+  while (in < sn.size() || i0 < s0.size()) {
+    const bool take_n = i0 >= s0.size() || (in < sn.size() && sn[in].low >= s0[i0].low);
+    const SlidingWin& win = take_n ? sn[in] : s0[i0];
+    const int slot = (take_n ? ytab : xtab) + (int)win.index1 - 1;
+    if (pos < 0) {
+      t.emit(mx::N2_LOAD, slot);
+    } else {
+      if (pos > win.low) t.emit(mx::N2_SQR, pos - win.low);
+      t.emit(mx::N2_MUL, slot);
+    }
+    pos = win.low;
+    (take_n ? in : i0) += 1;
+  }
+  if (pos > 0) t.emit(mx::N2_SQR, pos);
+  t.emit(mx::N2_MULC, mx::N2_SLOT_E);
+  tp.lift_share1 = (int)(cost1 * 65536 / t.cost);
+  if ((int)t.words.size() > MAX_SLIDING_OPS) { tp.lifted = N2Tape(); return; }
+  // the lifted tape has to pay: 2 % by the model, or the plan stays classic by default
+  tp.prefer_lifted = t.cost * 100 < tp.classic.cost * 98;
+}
+
+int plan_tapes(const u32* h_n, const u32* h_exp, int limbs_n, int exp_limbs, int flags, N2Tapes& tp) {
+  const int ebits = bit_length(h_exp, exp_limbs);
+  tp.ebits = ebits;
+  // ---- the classic tape: conversion, table of odd powers, sliding window, times E
+  N2Tape& c = tp.classic;
+  int w = 1;
+  if (ebits > 0) c.convert();
+  if (ebits == 0) {
+    c.emit(mx::N2_LOAD, mx::N2_SLOT_ONE);
+  } else if (flags & MX_PLAN_FIXED_WINDOW) {
+    // Fixed windows of fw bits from the least significant end: the SEQUENCE of operations — fw squarings and one
+    // multiplication per window, whatever the digits — depends on the exponent's bit length only, not on its bits
+    // (the sliding schedule's run lengths and multiplication count do).  Which table row a window reads still does.
+    const int fw = fixed_window_n2(ebits);
+    auto digit = [&](int d) {
+      u32 v = 0;
+      for (int b = fw - 1; b >= 0; --b) {
+        const int i = d * fw + b;
+        v = (v << 1) | ((i < 32 * exp_limbs) ? ((h_exp[i >> 5] >> (i & 31)) & 1u) : 0u);
+      }
+      return (int)v;
+    };
+    auto slot_of = [&](int dg) { return dg ? mx::N2_SLOT_TABLE + dg - 1 : mx::N2_SLOT_ONE; };
+    for (int t = 2; t < (1 << fw); ++t) { c.emit(mx::N2_MUL, mx::N2_SLOT_TABLE); c.emit(mx::N2_STORE, mx::N2_SLOT_TABLE + t - 1); }
+    const int nwin = (ebits + fw - 1) / fw;
+    c.emit(mx::N2_LOAD, slot_of(digit(nwin - 1)));
+    for (int d = nwin - 2; d >= 0; --d) { c.emit(mx::N2_SQR, fw); c.emit(mx::N2_MUL, slot_of(digit(d))); }
+    w = fw + 1;                              // the table region: 2^(w - 1) = 2^fw pair slots (one more than used)
+  } else {
+    w = sliding_window(ebits);
+    std::vector<SlidingOp> ops = sliding_schedule(h_exp, exp_limbs, w);
+    c.odd_powers(mx::N2_SLOT_TABLE, 1 << (w - 1));
+    c.emit(mx::N2_LOAD, mx::N2_SLOT_TABLE + (int)ops[0].index1 - 1);
+    for (size_t t = 1; t < ops.size(); ++t) {
+      if (ops[t].squarings) c.emit(mx::N2_SQR, ops[t].squarings);     // 28-bit repeat count on the tape
+      if (ops[t].index1) c.emit(mx::N2_MUL, mx::N2_SLOT_TABLE + (int)ops[t].index1 - 1);
+    }
+  }
+  c.emit(mx::N2_MULC, mx::N2_SLOT_E);          // the last product: digits below 2N for the epilogue (mx_powmod_n2.hpp)
+  if ((int)c.words.size() > MAX_SLIDING_OPS) return MX_ERR_SIZE;
+  tp.window = w;
+  // ---- the lifted tape: sliding-window plans whose exponent reaches N (a fixed-window plan's sequence of operations
+  // must depend on the exponent's length only: it stays classic)
+  if (!(flags & MX_PLAN_FIXED_WINDOW) && ebits >= bit_length(h_n, limbs_n)) build_lifted(h_n, limbs_n, h_exp, exp_limbs, tp);
+  return MX_OK;
+}
+
+// the counting fields of a plan descriptor
+void fill_plan_counts(mx_nsquare_plan* plan, const N2Tapes& tp) {
+  const bool have = !tp.lifted.words.empty();
+  const N2Tape& d = have && tp.prefer_lifted ? tp.lifted : tp.classic;       // what a one-wavefront launch runs by default
+  plan->exp_bits = tp.ebits;
+  plan->window = tp.window;
+  plan->ntape = (int)tp.classic.words.size();
+  plan->n_sqr = d.n_sqr;
+  plan->n_mul = d.n_mul;
+  plan->n_slot_reads = d.reads();
+  plan->n_slot_writes = d.n_writes;
+  plan->n_sqr_first = d.n_sqr0;
+  plan->n_mul_first = d.n_mul0;
+  plan->table_rows = std::max(1 << (tp.window - 1), have ? tp.lifted.rows() : 0);
+  plan->lift = have ? (tp.prefer_lifted ? 3 : 1) : 0;
+  plan->ntape_lift = (int)tp.lifted.words.size();
+  plan->n_sqr_classic = tp.classic.n_sqr;
+  plan->n_mul_classic = tp.classic.n_mul;
+  plan->lift_positions = tp.lifted.n_sqr + tp.lifted.n_sqr0;
+  plan->lift_pos1 = tp.lift_pos1;
+  plan->lift_share1 = tp.lift_share1;
+}
+}  // namespace
+
+extern "C" int mx_nsquare_tape(const uint32_t* h_n, const uint32_t* h_exp, int limbs_n, int exp_limbs, int flags, int lifted,
+                               uint32_t* h_tape, int max_words, mx_nsquare_plan* plan) {
+  if (!h_n || !h_exp || !h_tape || !plan || max_words < 0 || (lifted != 0 && lifted != 1)) return MX_ERR_ARG;
+  if (flags & ~MX_PLAN_FIXED_WINDOW) return MX_ERR_ARG;
+  if (limbs_n <= 0 || exp_limbs <= 0) return MX_ERR_ARG;
+  if (!(h_n[0] & 1u)) return MX_ERR_MODULUS;
+  const int bits = bit_length(h_n, limbs_n);
+  if (bits < 2) return MX_ERR_MODULUS;
+  N2Tapes tp;
+  MX_TRY(plan_tapes(h_n, h_exp, limbs_n, exp_limbs, flags, tp));
+  std::memset(plan, 0, sizeof(*plan));
+  plan->limbs_n = limbs_n;
+  plan->n_bits = bits;
+  fill_plan_counts(plan, tp);
+  const std::vector<u32>& words = lifted ? tp.lifted.words : tp.classic.words;
+  if ((int)words.size() > max_words) return MX_ERR_WORKSPACE;
+  std::memcpy(h_tape, words.data(), words.size() * 4);
+  return (int)words.size();
+}
+
 extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_t* h_n, const uint32_t* h_exp,
                                             int limbs_n, int exp_limbs, int flags, void* d_plan, int64_t plan_bytes,
                                             void* stream) {
@@ -537,62 +759,9 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
     if (choose_geometry(bits, geos[g], lpls[g]) && geos[g].K <= max_lanes(lpls[g], 2)) geometries |= 1 << g;
   if (!(geometries & 1)) return MX_ERR_SIZE;
   if (mx_nsquare_plan_bytes(limbs_n, exp_limbs) > plan_bytes) return MX_ERR_WORKSPACE;
-  const int ebits = bit_length(h_exp, exp_limbs);
   const int k = bits - 1;                                      // x = x_lo + 2^k x_hi
-  // ---- the tape (mx_powmod_n2.hpp): conversion, table of odd powers, sliding window, times E
-  std::vector<u32> tape;
-  int n_sqr = 0, n_mul = 0, w = 1;
-  int n_reads = 0, n_writes = 6;                               // the prologue writes 4 constant pairs and x_lo, x_hi
-  auto emit = [&](u32 op, int arg) {
-    tape.push_back((op << 28) | (u32)arg);
-    if (op == mx::N2_SQR) n_sqr += arg;
-    if (op == mx::N2_MUL || op == mx::N2_MULC) n_mul += 1;
-    if (op == mx::N2_STORE) n_writes += 1;
-    if (op == mx::N2_MUL || op == mx::N2_MULC || op == mx::N2_ADD || op == mx::N2_LOAD) n_reads += 1;
-  };
-  if (ebits > 0) {            // x = (x_lo, 0) * K1 + (x_hi, 0) * K2, the first row of the table of either schedule
-    emit(mx::N2_LOAD, mx::N2_SLOT_LO); emit(mx::N2_MUL, mx::N2_SLOT_K1); emit(mx::N2_STORE, mx::N2_SLOT_TMP);
-    emit(mx::N2_LOAD, mx::N2_SLOT_HI); emit(mx::N2_MUL, mx::N2_SLOT_K2); emit(mx::N2_ADD, mx::N2_SLOT_TMP);
-    emit(mx::N2_STORE, mx::N2_SLOT_TABLE);
-  }
-  if (ebits == 0) {
-    emit(mx::N2_LOAD, mx::N2_SLOT_ONE);
-  } else if (flags & MX_PLAN_FIXED_WINDOW) {
-    // Fixed windows of fw bits from the least significant end: the SEQUENCE of operations — fw squarings and one
-    // multiplication per window, whatever the digits — depends on the exponent's bit length only, not on its bits
-    // (the sliding schedule's run lengths and multiplication count do).  Which table row a window reads still does.
-    const int fw = fixed_window_n2(ebits);
-    auto digit = [&](int d) {
-      u32 v = 0;
-      for (int b = fw - 1; b >= 0; --b) {
-        const int i = d * fw + b;
-        v = (v << 1) | ((i < 32 * exp_limbs) ? ((h_exp[i >> 5] >> (i & 31)) & 1u) : 0u);
-      }
-      return (int)v;
-    };
-    auto slot_of = [&](int dg) { return dg ? mx::N2_SLOT_TABLE + dg - 1 : mx::N2_SLOT_ONE; };
-    for (int t = 2; t < (1 << fw); ++t) { emit(mx::N2_MUL, mx::N2_SLOT_TABLE); emit(mx::N2_STORE, mx::N2_SLOT_TABLE + t - 1); }
-    const int nwin = (ebits + fw - 1) / fw;
-    emit(mx::N2_LOAD, slot_of(digit(nwin - 1)));
-    for (int d = nwin - 2; d >= 0; --d) { emit(mx::N2_SQR, fw); emit(mx::N2_MUL, slot_of(digit(d))); }
-    w = fw + 1;                              // the table region: 2^(w - 1) = 2^fw pair slots (one more than used)
-  } else {
-    w = sliding_window(ebits);
-    std::vector<SlidingOp> ops = sliding_schedule(h_exp, exp_limbs, w);
-    const int nodd = 1 << (w - 1);
-    if (nodd > 1) {
-      emit(mx::N2_SQR, 1); emit(mx::N2_STORE, mx::N2_SLOT_SQ); emit(mx::N2_LOAD, mx::N2_SLOT_TABLE);
-      for (int t = 1; t < nodd; ++t) { emit(mx::N2_MUL, mx::N2_SLOT_SQ); emit(mx::N2_STORE, mx::N2_SLOT_TABLE + t); }
-    }
-    emit(mx::N2_LOAD, mx::N2_SLOT_TABLE + (int)ops[0].index1 - 1);
-    for (size_t t = 1; t < ops.size(); ++t) {
-      if (ops[t].squarings) emit(mx::N2_SQR, ops[t].squarings);     // 28-bit repeat count on the tape
-      if (ops[t].index1) emit(mx::N2_MUL, mx::N2_SLOT_TABLE + (int)ops[t].index1 - 1);
-    }
-  }
-  emit(mx::N2_MULC, mx::N2_SLOT_E);          // the last product: digits below 2N for the epilogue (mx_powmod_n2.hpp)
-  if ((int)tape.size() > MAX_SLIDING_OPS) return MX_ERR_SIZE;
-
+  N2Tapes tp;
+  MX_TRY(plan_tapes(h_n, h_exp, limbs_n, exp_limbs, flags, tp));
   const int64_t cb = n2_consts_bytes(limbs_n);
   hipStream_t s = (hipStream_t)stream;
   char* dp = (char*)d_plan;
@@ -612,7 +781,8 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
     }
     MX_TRY(upload_words(dp + g * cb, rows[g].data(), rows[g].size(), s));
   }
-  MX_TRY(upload_words(dp + N2_GEOS * cb, tape.data(), tape.size(), s));
+  MX_TRY(upload_words(dp + N2_GEOS * cb, tp.classic.words.data(), tp.classic.words.size(), s));
+  if (!tp.lifted.words.empty()) MX_TRY(upload_words(dp + lifted_tape_offset(limbs_n), tp.lifted.words.data(), tp.lifted.words.size(), s));
   int pivot = 0;
   MX_TRY(prepare_bipair_section(h_n, limbs_n, bits, dp + bipair_section_offset(limbs_n), s, pivot));
   if (pivot) geometries |= N2_GEO_BIPAIR | (pivot << N2_GEO_PIVOT_SHIFT);      // the plan carries the pivot its constants were built with
@@ -620,24 +790,21 @@ extern "C" int mx_powmod_nsquare_prepare_ex(mx_nsquare_plan* plan, const uint32_
   plan->plan_bytes = plan_bytes;
   plan->limbs_n = limbs_n;
   plan->n_bits = bits;
-  plan->exp_bits = ebits;
-  plan->window = w;
-  plan->ntape = (int)tape.size();
-  plan->n_sqr = n_sqr;
-  plan->n_mul = n_mul;
   plan->geometries = geometries;
-  plan->n_slot_reads = n_reads;
-  plan->n_slot_writes = n_writes;
+  fill_plan_counts(plan, tp);
   return MX_OK;
 }
 
 extern "C" int64_t mx_powmod_nsquare_run_workspace_bytes(const mx_nsquare_plan* plan, int64_t batch) {
   if (!plan || batch <= 0 || plan->window < 1) return MX_ERR_ARG;
   // the largest table any launch shape of this batch needs (the caller may leave the choice to the library)
+  // (the lifted tape, one-wavefront launches only, has two tables: sized whatever MX_KNOB_N2_LIFT says now, so that a
+  // workspace sized under one value of the knob serves a run under another)
   int64_t most = -1;
   for (int l : N2_LPLS) {
     N2Shape p;
-    if (shape_n2(plan->n_bits, plan->window, batch, l, 2, p) && p.table_bytes + p.sched_bytes > most) most = p.table_bytes + p.sched_bytes;
+    if (shape_n2(plan->n_bits, 1 << (plan->window - 1), batch, l, 2, p) && p.table_bytes + p.sched_bytes > most) most = p.table_bytes + p.sched_bytes;
+    if ((plan->lift & 1) && shape_n2(plan->n_bits, plan->table_rows, batch, l, 1, p) && p.table_bytes > most) most = p.table_bytes;
   }
   return most < 0 ? MX_ERR_SIZE : most;
 }
@@ -691,8 +858,20 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   // this entry alone: MX_ERR_ARG where the shape queries say MX_ERR_SIZE
   if (wavefronts_per_group == 4 && limbs_per_lane != 0 && limbs_per_lane != LIMBS_PER_LANE_LAT) return MX_ERR_ARG;
   N2Launch r;
-  MX_TRY(resolve_n2(bits, batch, limbs_per_lane, wavefronts_per_group, plan->window, r));
+  const int classic_rows = 1 << (plan->window - 1);
+  MX_TRY(resolve_n2(bits, batch, limbs_per_lane, wavefronts_per_group, classic_rows, r));
   if (r.ch.wpg == 4 && wavefronts_per_group != 4 && !(plan->geometries & N2_GEO_BIPAIR)) r.ch.wpg = 2;      // a plan of an older layout
+  // The lifted tape (header of mx_nsquare_plan): one-wavefront launches of a plan that holds one, as MX_KNOB_N2_LIFT says,
+  // where the workspace has room for its two tables (a caller that sized it by mx_powmod_nsquare_run_workspace_bytes
+  // does); every other form reads the classic tape and its squaring count.
+  const int classic_n_sqr = (plan->lift & 1) ? plan->n_sqr_classic : plan->n_sqr;
+  bool lifted = r.ch.wpg == 1 && (plan->lift & 1) && plan->ntape_lift > 0 && g_knob_n2_lift != 1 && ((plan->lift & 2) || g_knob_n2_lift == 2);
+  if (lifted) {
+    N2Shape pl;
+    if (shape_n2(bits, plan->table_rows, batch, r.ch.lpl, 1, pl) && pl.table_bytes <= ws_bytes) r.p = pl; else lifted = false;
+  }
+  // squarings, of either kind, of the tape this run executes: the positions of its segments
+  const int run_n_sqr = !lifted ? classic_n_sqr : plan->lift_positions;
   const N2Choice& ch = r.ch;
   const N2Shape& p = r.p;
   const bool five = ch.wpg == 4;
@@ -700,6 +879,10 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   if (p.table_bytes + (ch.resident ? p.sched_bytes : 0) > ws_bytes) return MX_ERR_WORKSPACE;
   if (2 * p.geo.K * p.geo.L + 8 < limbs2 + 2) return MX_ERR_ARG;   // row wider than the staging area
   mx::PowmodN2Args a = n2_run_args(plan, d_bases, d_out, limbs2, batch, d_ws, r);
+  if (lifted) {
+    a.tape = (const u32*)((const char*)plan->d_plan + lifted_tape_offset(plan->limbs_n));
+    a.ntape = plan->ntape_lift;
+  }
   hipStream_t s = (hipStream_t)stream;
   if (five) {
     // the five-wavefront latency form: its own kernel for everything in front of the last product, then the last product and
@@ -730,18 +913,18 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   }
   // segments: consecutive launches that each execute a stretch of the tape (mx_powmod_n2.hpp); positions
   // are counted in squarings, the accumulator travels through a scratch slot of the workspace
-  int nseg = segments > 0 ? segments : n2_auto_segments(plan->n_sqr, p.nlanes / 64 * ch.wpg);
-  if (nseg > plan->n_sqr / 16) nseg = plan->n_sqr / 16;
+  int nseg = segments > 0 ? segments : n2_auto_segments(run_n_sqr, p.nlanes / 64 * ch.wpg);
+  if (nseg > run_n_sqr / 16) nseg = run_n_sqr / 16;
   if (nseg < 1) nseg = 1;
   MxKernelTimer timer(s);                        // one timed interval per exponentiation (all its segments)
   if (ch.resident > 0) {
     // time-sliced: one launch of resident workgroups, the segments are units of its own scheduler
     nseg = segments > 0 ? segments : ch.units;
     if (nseg > N2_TIMESLICE_MAX_SEGMENTS) nseg = N2_TIMESLICE_MAX_SEGMENTS;
-    if (nseg > plan->n_sqr / 16) nseg = plan->n_sqr / 16;
+    if (nseg > classic_n_sqr / 16) nseg = classic_n_sqr / 16;
     if (nseg < 1) nseg = 1;
     a.sched = (u32*)((char*)d_ws + p.table_bytes);
-    a.sched_groups = (int)p.groups; a.sched_segments = nseg; a.sched_n_sqr = plan->n_sqr;
+    a.sched_groups = (int)p.groups; a.sched_segments = nseg; a.sched_n_sqr = classic_n_sqr;
     MX_HIP(hipMemsetAsync(a.sched, 0, (size_t)(mx::N2_TS_HEADER + p.groups * (nseg - 1)) * 4, s));
     // no more workgroups than there are groups for their pairs
     int64_t wgs = (int64_t)ch.resident * device_cus();
@@ -752,12 +935,24 @@ extern "C" int mx_powmod_nsquare_run(const mx_nsquare_plan* plan, const uint32_t
   // tape up to, not including, its last product (N2_MULC, tape position n_sqr + 1); that product and the epilogue run as
   // one more segment on the plain instance (mx_powmod_n2.hpp).
   const bool fr_tape = ch.wpg == 1 && a.friendly;
+  // Where segment sg begins.  Classic tape: by squaring count — its multiplications are spread evenly.  Lifted tape: by
+  // estimated cost — a first-digit squaring costs ~0.45 of a pair squaring, so equal counts would make the segments of
+  // phase 1 less than half as long as the others and a burst of launches would drain unevenly.  The
+  // planner walked the tape with its cost constants and left the summary: lift_pos1 positions in front of phase 2 carry
+  // lift_share1 / 65536 of the cost; within either stretch cost is linear in position to within a window.
+  auto segment_begin = [&](int sg) -> int {
+    if (!lifted) return (int)((int64_t)run_n_sqr * sg / nseg);
+    const double f = (double)sg / nseg, f1 = plan->lift_share1 / 65536.0;
+    const int p1 = plan->lift_pos1, p2 = run_n_sqr - p1;
+    if (f1 <= 0.0 || f1 >= 1.0) return (int)((int64_t)run_n_sqr * sg / nseg);
+    return f <= f1 ? (int)(p1 * f / f1) : p1 + (int)(p2 * (f - f1) / (1.0 - f1));
+  };
   for (int sg = 0; sg < nseg; ++sg) {
     const bool final_sg = sg == nseg - 1;
     a.first = sg == 0;
     a.last = final_sg && !fr_tape;
-    a.pos_begin = (int)((int64_t)plan->n_sqr * sg / nseg);
-    a.pos_end = final_sg ? (fr_tape ? plan->n_sqr + 1 : 0x7FFFFFFF) : (int)((int64_t)plan->n_sqr * (sg + 1) / nseg);
+    a.pos_begin = segment_begin(sg);
+    a.pos_end = final_sg ? (fr_tape ? run_n_sqr + 1 : 0x7FFFFFFF) : segment_begin(sg + 1);
     MX_TRY(launch_n2(a, p, ch.wpg, s));
   }
   if (fr_tape) {
@@ -774,6 +969,8 @@ extern "C" int64_t mx_powmod_nsquare_workspace_bytes(int limbs_n, int exp_limbs,
   mx_nsquare_plan sizing{};
   sizing.n_bits = sizing_bits(limbs_n);
   sizing.window = sliding_window(32 * exp_limbs);
+  sizing.lift = 1;                                 // room for the two tables of a lifted tape, whatever the exponent turns out to be
+  sizing.table_rows = N2_MAX_TABLE_ROWS;
   int64_t run = mx_powmod_nsquare_run_workspace_bytes(&sizing, batch);
   if (run < 0) return run;
   return mx_nsquare_plan_bytes(limbs_n, exp_limbs) + run;

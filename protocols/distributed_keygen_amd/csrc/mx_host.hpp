@@ -40,7 +40,8 @@ extern Knob g_knob_generic_latency;    // MX_KNOB_GENERIC_LATENCY: 0 = the autom
 extern Knob g_knob_jacobi_max_batches; // MX_KNOB_JACOBI_MAX_BATCHES: 0 = the kernel's own bound, v = at most v - 1 batches
 extern Knob g_knob_lat_lanes;          // MX_KNOB_LAT_LANES: 0 = the smallest group that holds the number, v = at least v lanes per element for the 3-limb latency forms of the generic kernel
 extern Knob g_knob_n2_bipair;          // MX_KNOB_N2_BIPAIR: 0 = small launches of the pair kernel take the five-wavefront latency form where it exists, 1 = never
-extern Knob g_knob_bi_pivot;           // MX_KNOB_BI_PIVOT: 0 = the library's pivot of the bipartite form, v = v multiplier limbs on wavefront L (rounded down to a multiple of 3)
+extern Knob g_knob_n2_lift;            // MX_KNOB_N2_LIFT, stored as (value + 1) % 3: 0 = the planner's choice (value 2), 1 = the one-wavefront kernel never runs a plan's lifted tape (value 0), 2 = whenever the plan has one (value 1)
+extern Knob g_knob_bi_pivot;          // MX_KNOB_BI_PIVOT: 0 = the library's pivot of the bipartite form, v = v multiplier limbs on wavefront L (rounded down to a multiple of 3)
 
 struct Geometry {
   int K = 0;      // lanes per element
@@ -236,6 +237,35 @@ inline std::vector<SlidingOp> sliding_schedule(const u32* e, int limbs, int w) {
   if (pending) ops.push_back(SlidingOp{pending, 0u});
   return ops;
 }
+
+// The same recoding by bit position: the windows from the most significant one down, each with the position of its
+// lowest bit — x = sum (2 index1 - 1) 2^low.  Two exponents recoded this way share one squaring chain when their windows
+// are merged by `low` (the lifted tape of the N^2 modexp, mx_capi_n2.hip).
+struct SlidingWin {
+  int low;
+  u32 index1;
+};
+inline std::vector<SlidingWin> sliding_windows(const u32* e, int limbs, int w) {
+  std::vector<SlidingWin> out;
+  int pos = bit_length(e, limbs);
+  for (const SlidingOp& op : sliding_schedule(e, limbs, w)) {
+    if (!op.index1) break;                                   // trailing squarings
+    if (out.empty()) {                                       // step 0 carries no squarings: the length of its window
+      for (u32 v = 2 * op.index1 - 1; v; v >>= 1) --pos;
+    } else {
+      pos -= op.squarings;
+    }
+    out.push_back(SlidingWin{pos, op.index1});
+  }
+  return out;
+}
+
+// Cost of the pair kernel's tape operations, in VALU wave-instructions of the friendly 18-limb, 4-block instance (key_length
+// 2048): pair squaring and multiplication from profiles/r06_instr_model.json, the first-digit forms — pass 1 alone, and
+// for the multiplication the load of one digit instead of two — solved from SQ_INSTS_VALU of eight launches with
+// different e1 (profiles/r26_instruction_counters.json: residual 0).  Only their ratios matter: the planner of the lifted
+// tape weighs schedules with them and mx_powmod_nsquare_run cuts the segments of a lifted tape by them.
+constexpr int N2_COST_SQR = 5718, N2_COST_MUL = 7746, N2_COST_SQR0 = 2615, N2_COST_MUL0 = 3367;
 
 // The schedule as the words powmod_kernel<..., SLIDING> reads: (squarings << 16) | index1.  A run of
 // more than 65535 squarings (an exponent with that many consecutive zero bits) is split into

@@ -28,12 +28,16 @@ namespace mx {
 
 // The kernel is an interpreter of a short "tape" built by the host (the same for every lane, so
 // control flow is uniform): conversion into pair form, the table of odd powers and the
-// sliding-window exponentiation are all sequences of five operations on one pair register `acc`
+// sliding-window exponentiation are all sequences of a few operations on one pair register `acc`
 // and pair slots in device memory.  This keeps ONE squaring and ONE multiplication call site in
 // the kernel (each is two inlined Montgomery passes), which is what bounds code size and registers.
 // N2_MULC: a multiplication whose digits must come out below 2N (the last one, by (1, 0)); kernels without the friendly
 // passes treat it as N2_MUL
-enum : u32 { N2_SQR = 0, N2_MUL = 1, N2_ADD = 2, N2_LOAD = 3, N2_STORE = 4, N2_MULC = 5 };
+// N2_SQR0 / N2_MUL0 / N2_CLR1 (the lifted tape): first-digit operations.  For a = b (mod N), a^N = b^N
+// (mod N^2), so with e = e1 N + e0 the kernel may compute c^e1 modulo N ONLY — the chain of first digits, pass 1 of a
+// squaring or multiplication, which never reads a second digit — clear the second digit (any representative of c^e1
+// modulo N will do) and raise that to N, times c^e0, with pair operations.  The one-wavefront kernel alone reads them.
+enum : u32 { N2_SQR = 0, N2_MUL = 1, N2_ADD = 2, N2_LOAD = 3, N2_STORE = 4, N2_MULC = 5, N2_SQR0 = 6, N2_MUL0 = 7, N2_CLR1 = 8 };
 // tape word = (op << 28) | argument   (argument: repeat count for SQR, slot index otherwise)
 // slots: 0 K1 (represents R), 1 K2 (represents 2^k R), 2 E = (1, 0), 3 ONE, 4 (x_lo, 0), 5 (x_hi, 0),
 //        6 scratch, 7 x^2, 8.. odd powers x^(2k+1)
@@ -152,10 +156,11 @@ struct PairArithT {
     }
   }
 
-  // (z0, z1) = (x0, x1) * (y0, y1); outputs may alias inputs
+  // (z0, z1) = (x0, x1) * (y0, y1); outputs may alias inputs.  first_only (uniform over the wavefront): pass 1 alone,
+  // z0 = the first digit of the product, z1 untouched (z1 must be x1 then) — a step of the first-digit chain
   template <bool FR = false>
   __device__ __forceinline__ void mul(u32 (&z0)[L], u32 (&z1)[L], u32 (&x0)[L], u32 (&x1)[L],
-                                      const u32 (&y0)[L], const u32 (&y1)[L]) {
+                                      const u32 (&y0)[L], const u32 (&y1)[L], bool first_only = false) {
     // both multipliers go to LDS once: pass 1 reads y0, pass 2 reads y0 (row X1*Y0) and y1 (row X0*Y1)
     M.stage_multipliers(y0, y1);
     u32 t0[L], q[L];
@@ -165,17 +170,17 @@ struct PairArithT {
     // registers of the 18-limb instances (round 3: 116 B of scratch).  Pinned here, Z0 crosses the loop as L words.
 #pragma unroll
     for (int j = 0; j < L; ++j) asm volatile("" : "+v"(t0[j]));
-    mul_pass2<FR>(z1, x0, x1, q);
+    if (!first_only) mul_pass2<FR>(z1, x0, x1, q);
 #pragma unroll
     for (int j = 0; j < L; ++j) z0[j] = t0[j];
   }
 
-  // (z0, z1) = (x0, x1)^2
+  // (z0, z1) = (x0, x1)^2; first_only as for mul
   template <bool FR = false>
-  __device__ __forceinline__ void sqr(u32 (&z0)[L], u32 (&z1)[L], u32 (&x0)[L], u32 (&x1)[L]) {
+  __device__ __forceinline__ void sqr(u32 (&z0)[L], u32 (&z1)[L], u32 (&x0)[L], u32 (&x1)[L], bool first_only = false) {
     u32 t0[L], q[L];
     sqr_pass1<FR>(t0, q, x0);
-    sqr_pass2<FR>(z1, x0, x1, q);
+    if (!first_only) sqr_pass2<FR>(z1, x0, x1, q);
 #pragma unroll
     for (int j = 0; j < L; ++j) z0[j] = t0[j];
   }
@@ -432,10 +437,11 @@ __global__ void __launch_bounds__(64, (L > 9 ? 2 : 3)) powmod_n2_kernel(PowmodN2
     const u32 op = word >> 28;
     const int arg = (int)(word & 0x0FFFFFFFu);
     if (op == N2_MULC) pos += 1;                       // the last product: a position (and possibly a segment) of its own
-    if (op == N2_SQR) {
+    const bool first_only = op == N2_SQR0 || op == N2_MUL0;   // a step of the first-digit chain: pass 1 alone
+    if (op == N2_SQR || op == N2_SQR0) {
       const int lo = pos > A.pos_begin ? pos : A.pos_begin;
       const int hi = pos + arg < A.pos_end ? pos + arg : A.pos_end;
-      for (int s = lo; s < hi; ++s) P.template sqr<FR>(acc0, acc1, acc0, acc1);
+      for (int s = lo; s < hi; ++s) P.template sqr<FR>(acc0, acc1, acc0, acc1, first_only);
       pos += arg;
       continue;
     }
@@ -443,12 +449,22 @@ __global__ void __launch_bounds__(64, (L > 9 ? 2 : 3)) powmod_n2_kernel(PowmodN2
     if (op == N2_STORE) {
 #pragma unroll
       for (int j = 0; j < L; ++j) { slot_at(arg, 0, j) = acc0[j]; slot_at(arg, 1, j) = acc1[j]; }
+    } else if (op == N2_CLR1) {
+#pragma unroll
+      for (int j = 0; j < L; ++j) acc1[j] = 0;
     } else {
       u32 f0[L], f1[L];
 #pragma unroll
-      for (int j = 0; j < L; ++j) { f0[j] = slot_at(arg, 0, j); f1[j] = slot_at(arg, 1, j); }
-      if (op == N2_MUL || op == N2_MULC) {
-        P.template mul<FR>(acc0, acc1, acc0, acc1, f0, f1);
+      for (int j = 0; j < L; ++j) f0[j] = slot_at(arg, 0, j);
+      if (first_only) {                                      // N2_MUL0 never reads the slot's second digit
+#pragma unroll
+        for (int j = 0; j < L; ++j) f1[j] = 0;
+      } else {
+#pragma unroll
+        for (int j = 0; j < L; ++j) f1[j] = slot_at(arg, 1, j);
+      }
+      if (op == N2_MUL || op == N2_MULC || op == N2_MUL0) {
+        P.template mul<FR>(acc0, acc1, acc0, acc1, f0, f1, first_only);
       } else if (op == N2_ADD) {
         M.add(acc0, acc0, f0);
         M.add(acc1, acc1, f1);

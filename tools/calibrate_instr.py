@@ -171,11 +171,16 @@ def run(cfg_path: str) -> None:
                         n2 = n * n
                         rows = eng.to_device(Lm.pack([rng.randrange(n2) for _ in range(batch)], Lm.limbs_for(n2)))
                         plan = eng.nsquare_plan(n, e)
+                        # the model's constants are those of PAIR operations: the classic tape (the smallest moduli here are
+                        # shorter than the exponents, and a plan then counts its lifted tape's operations by default)
+                        eng.debug_knob("n2_lift", 0)
+                        d = plan.desc
+                        n_sqr, n_mul = (d.n_sqr_classic, d.n_mul_classic) if d.lift & 1 else (d.n_sqr, d.n_mul)
                         eng.powmod_nsquare_t(rows, n, e, segments=1)
                         # a friendly one-wavefront exponentiation is two dispatches of powmod_n2_kernel: the tape on the
                         # friendly instance, its last product and the epilogue on the plain one
                         configs.append({"kind": kind, "L": L, "nblk": nblk, "K": k, "waves": WAVES, "dispatches": 2 if friendly_1w else 1,
-                                        "n_sqr": int(plan.desc.n_sqr), "n_mul": int(plan.desc.n_mul)})
+                                        "n_sqr": int(n_sqr), "n_mul": int(n_mul)})
                     else:
                         assert eng.geometry(bits, batch * 2, 2) == (k, L, W, nblk)
                         groups = 2
