@@ -34,6 +34,11 @@ static void square(const std::vector<uint32_t>& a, std::vector<uint32_t>& out) {
 }
 
 int main() {
+  // Before the first GPU call of the process: the HIP runtime reads GPU_MAX_HW_QUEUES once, and with its default of 4 —
+  // or an inherited 4 — streams that are meant to run side by side share hardware queues and serialise.  This program has
+  // one stream; a caller with several launches in flight needs it (mx_stream_census tells what the streams really got).
+  const int queues = mx_configure_hw_queues(16);
+  if (queues < 0) { std::fprintf(stderr, "mx_configure_hw_queues -> %s\n", mx_error_string(queues)); return 3; }
   const int limbs_n = 65, limbs2 = 130, exp_limbs = 132;       // key_length 2048: N < 2^2051, exponent < 2^4224
   const int64_t batch = 2048;
   std::mt19937_64 rng(2048);

@@ -15,7 +15,8 @@
  *   - d_* pointers are DEVICE pointers (e.g. torch.Tensor.data_ptr()), h_* are HOST pointers.
  *   - The caller owns every buffer, including the workspace; the library allocates nothing that
  *     outlives a call (the one exception is explicit: mx_stream_create_cu_slice hands out a stream that
- *     the caller destroys), keeps no state between calls and reads no environment variable.  All work is enqueued on `stream` (a hipStream_t, NULL = default stream);
+ *     the caller destroys), keeps no state between calls and reads no environment variable (the one exception is
+ *     explicit too: mx_configure_hw_queues, the process set-up a caller opts into).  All work is enqueued on `stream` (a hipStream_t, NULL = default stream);
  *     calls return after enqueueing and NEVER synchronise the stream or the device.  Host arrays
  *     (h_*) travel by value in kernel-argument blocks and may be freed/reused on return; operand
  *     sets of thousands of moduli should use the *_dev entry points (device-resident operands).
@@ -39,6 +40,7 @@ extern "C" {
 #define MX_ERR_MODULUS (-3)      /* even or < 3 modulus */
 #define MX_ERR_WORKSPACE (-4)    /* workspace too small */
 #define MX_ERR_HIP (-5)          /* a HIP runtime call failed (see mx_last_hip_error) */
+#define MX_ERR_STATE (-6)        /* too late: the library has already used the GPU in this process */
 
 /* ABI version (major*100 + minor). */
 int mx_version(void);
@@ -370,8 +372,38 @@ int mx_debug_knob(int knob, int value);
  * memory.  A concurrency probe: two streams that the HIP runtime has mapped to the same hardware queue run
  * their spins one after the other, two streams on different queues run them side by side — which is what
  * decides whether chunks of a batch launched on those streams fill the machine together or serialise
- * (GPU_MAX_HW_QUEUES is read once when the runtime initialises and cannot be queried).  Never synchronises. */
+ * (GPU_MAX_HW_QUEUES is read once when the runtime initialises and cannot be queried: mx_configure_hw_queues sets it
+ * in time, mx_stream_census below is this probe run over a set of streams).  Never synchronises. */
 int mx_spin(int64_t microseconds, void* stream);
+/* Process set-up for callers that keep several launches in flight on streams of their own: the HIP runtime maps the
+ * streams of a process onto GPU_MAX_HW_QUEUES hardware queues — 4 when the variable is unset, and job runners commonly
+ * export 4 as well —, two streams on one queue serialise their kernels, and four launches of this library that were
+ * meant to fill the machine together then run 2.3 at a time (profiles/r27_overlap_before.txt).  Call it BEFORE the
+ * first GPU call of the process (of anybody: the runtime reads the variable once, when it initialises).  Makes no HIP
+ * call.  `queues` is clamped to 1..32 and written to GPU_MAX_HW_QUEUES (setenv, process-wide, inherited by child
+ * processes) when the variable is unset, is not a positive number, or is SMALLER than the request: an inherited
+ * value does not silently undercut what the caller asked for; a larger inherited value stays.  The library never
+ * writes a value above 32.  MX_HW_QUEUES_KEEP=1 in the environment is the opt-out of a user who really wants fewer
+ * queues: nothing is changed.  Returns the value the environment holds afterwards (0: unset — the runtime's default),
+ * or MX_ERR_STATE without changing anything if this library has already made a GPU call in the process (it cannot
+ * see the GPU calls of others: a caller that initialised the runtime by other means gets the value back, and the
+ * census tells what it really got). */
+int mx_configure_hw_queues(int queues);
+/* What mx_configure_hw_queues last wrote or found in this process; 0 if it was never called (or found nothing and
+ * was told to keep that). */
+int mx_hw_queues_configured(void);
+/* Which of the caller's `n` (1..64) streams run side by side, measured with mx_spin: stream 0 is accepted and sets
+ * the time of one spin of `spin_us` microseconds (1..1 000 000; best of four rounds); every further stream spins
+ * together with the streams accepted so far and is accepted if the set still takes less than 1.6 spins.  group_of[i]
+ * = i for an accepted stream; for a stream that was not accepted the index of the first accepted stream it
+ * serialises with when the two spin alone, or -1 if it runs beside each of them alone and only the whole set was
+ * slower (a limit on the set, not a shared queue — the one case in which no accepted stream can be named).  Naming
+ * the partner costs every stream that is NOT accepted ceil(log2(accepted)) + 1 further probes of two rounds each (the
+ * accepted streams are halved until one is left); accepted streams cost nothing extra.  Returns the number of accepted
+ * streams or MX_ERR_ARG / MX_ERR_HIP.  Unlike every
+ * other entry point it WAITS: for the device first, then for the given streams after every round — a set-up call,
+ * not one for the hot path. */
+int mx_stream_census(void* const* streams, int n, int64_t spin_us, int* group_of);
 /* Streams confined to a slice of the compute units, for callers that keep several SMALL launches in flight: the
  * dispatcher places concurrent launches of a few dozen workgroups each on the same CUs of every XCD (four 64-workgroup
  * launches on four ordinary streams ran 1.7x longer than one of them alone), while launches on streams whose CU

@@ -11,7 +11,7 @@ from pathlib import Path
 LIB_PATH = Path(__file__).resolve().parent / "libmxpaillier.so"
 
 MX_OK = 0
-ERRORS = {-1: "MX_ERR_ARG", -2: "MX_ERR_SIZE", -3: "MX_ERR_MODULUS", -4: "MX_ERR_WORKSPACE", -5: "MX_ERR_HIP"}
+ERRORS = {-1: "MX_ERR_ARG", -2: "MX_ERR_SIZE", -3: "MX_ERR_MODULUS", -4: "MX_ERR_WORKSPACE", -5: "MX_ERR_HIP", -6: "MX_ERR_STATE"}
 
 class NsquarePlan(ctypes.Structure):
     """mx_nsquare_plan (include/mxpaillier.h)."""
@@ -118,6 +118,9 @@ SYMBOLS = {
     "mx_selftest_lanes": (c_int, [c_void_p]),
     "mx_debug_knob": (c_int, [c_int, c_int]),
     "mx_spin": (c_int, [c_int64, c_void_p]),
+    "mx_configure_hw_queues": (c_int, [c_int]),
+    "mx_hw_queues_configured": (c_int, []),
+    "mx_stream_census": (c_int, [POINTER(c_void_p), c_int, c_int64, POINTER(c_int)]),
     "mx_clock_probe": (c_int, [c_int64, c_void_p, c_void_p]),
     "mx_stream_create_cu_slice": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "mx_stream_destroy": (c_int, [c_void_p]),

@@ -150,5 +150,23 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     return out
 
 
+def ensure_built() -> Path:
+    """build(force=False) for callers that may be several processes at once (the ranks of a multi-GPU run all pass
+    configure_hw_queues before their first GPU call): a fresh library costs one digest of the sources and nothing else;
+    a missing or stale one is compiled by ONE process, under an exclusive lock on build/.lock, while the others wait and
+    then find it fresh."""
+    if not needs_build():
+        return LIB
+    import fcntl
+
+    (PKG / "build").mkdir(exist_ok=True)
+    with open(PKG / "build" / ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            return build(force=False)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))

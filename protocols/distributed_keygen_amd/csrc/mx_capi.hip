@@ -12,11 +12,15 @@
 #include "mx_field.hpp"
 #include "mx_modinv.hpp"
 #include "mx_bimont.hpp"
+#include "mx_queues.hpp"
 #include <cstring>
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 
 namespace mxh {
 thread_local hipError_t g_last_hip = hipSuccess;
+std::atomic<bool> g_gpu_touched{false};
 Knob g_knob_n2_segments;
 Knob g_knob_n2_timeslice;
 Knob g_knob_n2_friendly_1w;
@@ -314,11 +318,36 @@ const char* mx_error_string(int code) {
     case MX_ERR_MODULUS: return "modulus must be odd and >= 3";
     case MX_ERR_WORKSPACE: return "workspace too small";
     case MX_ERR_HIP: return "HIP runtime error";
+    case MX_ERR_STATE: return "too late: the library has already used the GPU in this process";
   }
   return "unknown error";
 }
 
 const char* mx_last_hip_error(void) { return hipGetErrorString(g_last_hip); }
+
+namespace {
+std::mutex g_hw_queues_mu;
+int g_hw_queues_configured = 0;      // what mx_configure_hw_queues last wrote or found; 0 = never called
+}
+
+int mx_configure_hw_queues(int queues) {
+  std::lock_guard<std::mutex> lock(g_hw_queues_mu);
+  if (g_gpu_touched.load(std::memory_order_relaxed)) return MX_ERR_STATE;
+  const mxq::QueueDecision d = mxq::decide_hw_queues(queues, std::getenv("GPU_MAX_HW_QUEUES"),
+                                                     mxq::keep_requested(std::getenv("MX_HW_QUEUES_KEEP")));
+  if (d.write) {
+    char text[16];
+    std::snprintf(text, sizeof text, "%d", d.value);
+    if (setenv("GPU_MAX_HW_QUEUES", text, 1) != 0) return MX_ERR_ARG;
+  }
+  g_hw_queues_configured = d.value;
+  return d.value;
+}
+
+int mx_hw_queues_configured(void) {
+  std::lock_guard<std::mutex> lock(g_hw_queues_mu);
+  return g_hw_queues_configured;
+}
 
 int mx_debug_knob(int knob, int value) {
   if (value < 0) return MX_ERR_ARG;
@@ -345,6 +374,7 @@ int mx_profile(int enable) {
 
 int mx_profile_collect(double* total_ms, int* launches) {
   if (!total_ms || !launches) return MX_ERR_ARG;
+  touch_gpu();
   std::lock_guard<std::mutex> lock(g_mx_profile.mu);
   double sum = 0;
   int n = 0, rc = MX_OK;
@@ -454,6 +484,60 @@ int mx_spin(int64_t microseconds, void* stream) {
   return mx_launch(spin_kernel, 1, 64, 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull);
 }
 
+int mx_stream_census(void* const* streams, int n, int64_t spin_us, int* group_of) {
+  if (!streams || !group_of || n < 1 || n > 64 || spin_us < 1 || spin_us > 1000000) return MX_ERR_ARG;
+  // one spin on every stream of `trial`, all waited for: wall time of the best of `rounds` rounds (four where a stream
+  // may be new: its first launch binds its queue)
+  int rc = MX_OK;
+  auto spin_all = [&](const std::vector<int>& trial, int rounds = 4) -> double {
+    double best = -1;
+    for (int rep = 0; rep < rounds && rc == MX_OK; ++rep) {
+      const auto t0 = std::chrono::steady_clock::now();
+      for (int i : trial)
+        if (rc == MX_OK) rc = mx_spin(spin_us, streams[i]);
+      for (int i : trial)                                  // (also after a failed launch: nothing stays in flight)
+        if (!hip_ok(hipStreamSynchronize((hipStream_t)streams[i])) && rc == MX_OK) rc = MX_ERR_HIP;
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (best < 0 || dt < best) best = dt;
+    }
+    return best;
+  };
+  MX_HIP(hipDeviceSynchronize());
+  std::vector<int> accepted;
+  double one = 0;      // what ONE spin costs here and now (launch + clock ramp included)
+  for (int i = 0; i < n; ++i) {
+    group_of[i] = i;
+    if (accepted.empty()) {
+      one = std::max(spin_all({i}), 1e-6 * (double)spin_us);
+      if (rc != MX_OK) return rc;
+      accepted.push_back(i);
+      continue;
+    }
+    // side by side: about one spin; sharing a queue with an accepted stream: two
+    std::vector<int> trial = accepted;
+    trial.push_back(i);
+    const bool beside = spin_all(trial) < 1.6 * one;
+    if (rc != MX_OK) return rc;
+    if (beside) { accepted.push_back(i); continue; }
+    // whom it serialises with: halve the accepted streams (the half that still takes two spins together with stream i
+    // holds the partner; the earlier half is asked first, so the first partner is found), then confirm the pair alone —
+    // ceil(log2(accepted)) + 1 probes of two rounds, every stream's queue being bound by now
+    size_t lo = 0, hi = accepted.size();
+    while (hi - lo > 1) {
+      const size_t mid = lo + (hi - lo) / 2;
+      std::vector<int> half(accepted.begin() + lo, accepted.begin() + mid);
+      half.push_back(i);
+      const bool in_first = spin_all(half, 2) >= 1.6 * one;
+      if (rc != MX_OK) return rc;
+      if (in_first) hi = mid; else lo = mid;
+    }
+    const bool pair_serial = spin_all({accepted[lo], i}, 2) >= 1.6 * one;
+    if (rc != MX_OK) return rc;
+    group_of[i] = pair_serial ? accepted[lo] : -1;
+  }
+  return (int)accepted.size();
+}
+
 int mx_stream_create_cu_slice(int slice, int n_slices, int reserved, void** stream_out) {
   // CU mask bit i is CU (i / n_xcd) of XCD (i % n_xcd) (tools/ubench/cu_mask_probe.hip: 32 consecutive bits = 4 CUs
   // in each of the 8 XCDs; a mask that leaves an XCD without any CU is ignored by the runtime).  A slice is a
@@ -481,6 +565,7 @@ int mx_stream_destroy(void* stream) {
 
 int mx_clock_probe(int64_t microseconds, uint64_t* d_ticks, void* stream) {
   if (microseconds <= 0 || microseconds > 1000000 || !d_ticks) return MX_ERR_ARG;
+  touch_gpu();
   hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long)microseconds * 100ull,
                      (unsigned long long*)d_ticks);
   MX_HIP(hipGetLastError());

@@ -24,7 +24,7 @@ constexpr int LIMBS_PER_LANE_BI = 6;
 
 // Limbs per lane (3 latency / 9 narrow / 18 wide) and the other launch-shape choices are per-call ARGUMENTS of the
 // entry points; the entry points without such an argument leave the choice to the library.  The library reads NO
-// environment variable and keeps no tuning state that a production caller can set: what remains process-wide are the
+// environment variable (but for the process set-up a caller opts into, mx_configure_hw_queues) and keeps no tuning state that a production caller can set: what remains process-wide are the
 // developer knobs below (explicit mx_debug_knob calls, for A/B runs and for tests that must reach a fallback path), held
 // in atomics so that a knob flipped by one thread while another launches is a defined read of the old or the new value.
 struct Knob {
@@ -282,8 +282,18 @@ inline std::vector<u32> pack_sliding_ops(const std::vector<SlidingOp>& ops) {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
+// Set where the library touches the HIP runtime — every launch (mx_launch.hpp), every checked call (hip_ok) and the few
+// calls beside them (the timer's events, the device queries of mx_upload.hpp, mx_profile_collect, mx_clock_probe, the
+// developer build's mx_debug_pad_faults) —, never cleared: from then on the runtime has read its settings and
+// mx_configure_hw_queues is too late.  Read first, written once: launches from many threads do not pass the line around.
+extern std::atomic<bool> g_gpu_touched;
+inline void touch_gpu() {
+  if (!g_gpu_touched.load(std::memory_order_relaxed)) g_gpu_touched.store(true, std::memory_order_relaxed);
+}
+
 extern thread_local hipError_t g_last_hip;
 inline bool hip_ok(hipError_t e) {
+  touch_gpu();
   if (e != hipSuccess) { g_last_hip = e; return false; }
   return true;
 }

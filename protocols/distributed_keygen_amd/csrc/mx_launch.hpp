@@ -16,6 +16,7 @@ inline int mx_dispatch_lanes(int K, F&& f) {
 
 template <class Kern, class Args>
 inline int mx_launch(Kern kern, int64_t nblocks, int threads, size_t lds, hipStream_t s, const Args& a) {
+  mxh::touch_gpu();
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3((unsigned)threads), lds, s, a);
   MX_HIP(hipGetLastError());
   return MX_OK;

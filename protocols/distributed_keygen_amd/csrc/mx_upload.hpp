@@ -57,6 +57,7 @@ struct MxKernelTimer {
     std::lock_guard<std::mutex> lock(g_mx_profile.mu);
     if (!g_mx_profile.on) return;
     hipEvent_t start;
+    touch_gpu();
     if (hipEventCreate(&start) != hipSuccess || hipEventCreate(&stop) != hipSuccess) { stop = nullptr; return; }
     hipEventRecord(start, s);
     g_mx_profile.events.emplace_back(start, stop);
@@ -71,6 +72,7 @@ namespace {
 constexpr int MX_MAX_DEVICES = 64;
 inline int mx_current_device() {
   int dev = 0;
+  touch_gpu();
   return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MX_MAX_DEVICES) ? dev : -1;
 }
 // Opt a kernel into more than 64 KB of dynamic LDS per workgroup, once per (instance, device): the attribute belongs

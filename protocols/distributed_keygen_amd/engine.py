@@ -733,36 +733,27 @@ class Engine:
         on one queue serialise.  Measured, not assumed: every candidate stream gets one idle one-wavefront
         kernel (mx_spin) together with the streams accepted so far; if the set takes about one spin it is
         concurrent, if it takes two the newcomer shares a queue with an accepted stream and is dropped.
+        The measurement is the native library's (mx_stream_census: C callers get the same answer; it also names the
+        stream a dropped one serialises with, which costs a dropped stream log2(accepted) + 1 short probes more than
+        the prefix test alone — a few milliseconds, on the set-up path of _chunk_streams only).
         Waits for the device first (one-time cost when the chunk streams are created)."""
-        import time as _t
+        streams = list(streams)
+        return [st for k, (st, g) in enumerate(zip(streams, self.stream_census(streams, spin_us))) if g == k]
 
-        torch = self.torch
-        accepted: List[Any] = []
+    def stream_census(self, streams: Sequence[Any], spin_us: int = 400) -> List[int]:
+        """mx_stream_census (include/mxpaillier.h) over torch streams: for every stream its own index if it runs beside
+        the streams accepted before it, else the index of the first accepted stream it serialises with (-1: with none
+        of them alone, only with the set).  Waits for the device and the streams."""
+        import ctypes as _ctypes
 
-        def spin_all(trial) -> float:
-            best = None
-            for _ in range(4):                           # the first launch on a fresh stream binds its queue; best of the rest
-                t0 = _t.perf_counter()
-                for st in trial:
-                    _lib.check(self.lib.mx_spin(spin_us, int(st.cuda_stream)), "mx_spin")
-                for st in trial:
-                    st.synchronize()
-                dt = _t.perf_counter() - t0
-                best = dt if best is None else min(best, dt)
-            return best
-
-        with torch.cuda.device(self.device):
-            torch.cuda.synchronize(self.device)
-            one = None                                   # what ONE spin costs here and now (launch + clock ramp included)
-            for cand in streams:
-                if one is None:
-                    one = max(spin_all([cand]), 1e-6 * spin_us)
-                    accepted.append(cand)
-                    continue
-                # side by side: about one spin; sharing a queue with an accepted stream: two
-                if spin_all(accepted + [cand]) < 1.6 * one:
-                    accepted.append(cand)
-        return accepted
+        streams = list(streams)
+        if not streams:
+            return []
+        ptrs = (_ctypes.c_void_p * len(streams))(*[int(st.cuda_stream) for st in streams])
+        groups = (_ctypes.c_int * len(streams))()
+        with self.torch.cuda.device(self.device):
+            _lib.check(self.lib.mx_stream_census(ptrs, len(streams), int(spin_us), groups), "mx_stream_census")
+        return list(groups)
 
     RECHECK_CAPPED_EVERY = 16       # a capped engine probes again every so many long batches (the cap may have been a hiccup)
 

@@ -132,8 +132,9 @@ def install(engine: Any = None, package: str = DEFAULT_PACKAGE, scalars: bool = 
     parties), which needs more HIP hardware queues than the runtime's default of 4; they can only be chosen before
     the process first touches the GPU.  Default (None): when install() is left to create the engine itself
     (``engine=None`` — the engine is then made on first use, so the runtime is not up yet) it asks for 16 through
-    ``configure_hw_queues`` — which sets GPU_MAX_HW_QUEUES in os.environ unless the user set it, a process-wide setting
-    that child processes inherit; when the caller passes an engine, the runtime is initialised already and install()
+    ``configure_hw_queues`` — which raises GPU_MAX_HW_QUEUES to that number unless the environment already holds a larger
+    one or MX_HW_QUEUES_KEEP=1 (an inherited smaller value, such as the 4 that job runners export, no longer wins), a
+    process-wide setting that child processes inherit; when the caller passes an engine, the runtime is initialised already and install()
     leaves the environment alone (call ``configure_hw_queues()`` yourself before creating the engine — INTEGRATION.md
     "call order").  An explicit number asks for that many and warns — once per process — when it is too late; 0 never
     touches the environment.  Either way the engine measures what it has and uses no more streams than run side by side.

@@ -1,7 +1,7 @@
 # usage (on the GPU box, from the repo root): bash tools/profile_round.sh <tag>
 # Runs the bench lines and rocprofv3 passes whose summaries are copied into profiles/ (tools/prof_summary.py,
-# tools/hbm_traffic.py, tools/calibrate_instr.py, tools/sweep_shapes.py).  The library reads no environment; the
-# bench opts into 16 HIP hardware queues itself (protocols.distributed_keygen_amd.configure_hw_queues).
+# tools/hbm_traffic.py, tools/calibrate_instr.py, tools/sweep_shapes.py).  The library reads no tuning from the environment; the
+# bench opts into 16 HIP hardware queues itself (protocols.distributed_keygen_amd.configure_hw_queues -> mx_configure_hw_queues).
 tag=${1:-r06}
 export PROFILE_TAG=$tag
 export TMPDIR=/tmp
