@@ -3,7 +3,7 @@
 
 Threshold Paillier with a dealer and the auxiliary moduli of range proofs want p = 2 p' + 1 and q = 2 q' + 1 with p', q'
 prime.  Such primes are rare — one odd candidate in about 190 000 at 1024 bits — so the search draws halves p' in large
-batches, drops those where a small prime divides p' or 2 p' + 1 in ONE pass (csrc/mx_safe.hpp: safe_sieve_kernel), runs the
+batches, drops those where a small prime divides p' or 2 p' + 1 in ONE pass (csrc/mx_sieve.hpp: sieve_kernel<true>), runs the
 base 2 on p' and on p, and 64 random bases on p' alone (Pocklington: with p' prime, the base 2 proves p).
    python examples/safe_prime_key.py [--key-length 2048] [--messages 1000]
 """

@@ -3,7 +3,7 @@
 
 A dealer makes a key of two safe primes on the GPU and shares it among five parties so that any three decrypt
 (threshold.deal: Damgård–Jurik / Shoup).  Every party sends c_i = c^(2 x_i) with a proof that it used its dealt share
-(csrc/mx_sha256.hpp: the challenges, csrc/mx_proof.hpp: the responses; everything else is the engine's modexps, its
+(csrc/mx_sha256.hpp: the challenges, csrc/mx_response.hpp: the responses; everything else is the engine's modexps, its
 multi-exponentiation and its fixed-base tables).  Party 3 spoils one of its partial decryptions: its proof for that row
 fails, decrypt_verified names it and decrypts from the others; without the proofs the combination would only have
 reported that SOMETHING is wrong.

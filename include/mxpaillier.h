@@ -971,7 +971,7 @@ int mx_mr_base2(const uint32_t* d_cands, const uint32_t* h_cands, uint8_t* d_pas
                 void* stream);
 
 /* ---- the safe-prime search: p = 2h + 1 with h and p prime (ABI 4.4, additions) ---------------------------------------
- * For the party that makes or vets a key of two safe primes (csrc/mx_safe.hpp; tools/mr_model.py is the model).
+ * For the party that makes or vets a key of two safe primes (csrc/mx_sieve.hpp, csrc/mx_safe.hpp; tools/mr_model.py is the model).
  *
  * mx_safe_sieve: the joint sieve of h and 2h + 1 over `batch` DEVICE rows d_halves [batch][limbs] of h:  d_out[e] = 1 iff
  *   some h_primes[k] = l has h ≡ 0 (l divides h) or h ≡ (l - 1) / 2 (l divides 2h + 1) modulo l.  The geometry, the tables
@@ -991,7 +991,7 @@ int mx_safe_double(const uint32_t* d_in, uint32_t* d_out, int limbs, int64_t row
 
 /* ---- decryption proofs of a dealt threshold key: challenge and response (ABI 4.4, additions) -------------------------
  * The two steps of a proof of equal discrete logarithms that no other entry point covers (csrc/mx_sha256.hpp,
- * csrc/mx_proof.hpp; tools/proof_model.py is the model; protocols/distributed_keygen_amd/threshold.py composes them with
+ * csrc/mx_response.hpp; tools/proof_model.py is the model; protocols/distributed_keygen_amd/threshold.py composes them with
  * the modexps, the multi-exponentiation and the fixed-base tables above).
  *
  * mx_sha256_rows:  d_out[r] = SHA-256(prefix | BE(rows_0[r]) | .. | BE(rows_{n_sets-1}[r])),  r < count  (FIPS 180-4).

@@ -592,54 +592,20 @@ int mx_selftest_lanes(void* stream) {
 }  // extern "C"
 
 // ---- sieve ---------------------------------------------------------------------------------
-namespace {
-struct SievePlan { int np_pad; int64_t off_primes, off_pw, off_inv, off_lim, total; };
-SievePlan plan_sieve(int limbs, int np) {
-  SievePlan p;
-  p.np_pad = (np + 63) / 64 * 64;
-  int64_t o = 0;
-  p.off_primes = o; o += align256((int64_t)np * 4);
-  p.off_pw = o;     o += align256((int64_t)limbs * p.np_pad * 4);
-  p.off_inv = o;    o += align256((int64_t)p.np_pad * 8);
-  p.off_lim = o;    o += align256((int64_t)p.np_pad * 8);
-  p.total = o;
-  return p;
-}
-}  // namespace
-
 extern "C" int64_t mx_sieve_workspace_bytes(int limbs, int n_primes) {
   if (limbs <= 0 || n_primes <= 0) return MX_ERR_ARG;
-  return plan_sieve(limbs, n_primes).total;
+  return mx::plan_sieve(limbs, n_primes).total;
 }
 
 extern "C" int mx_sieve(const uint32_t* d_cands, uint8_t* d_out, const uint32_t* h_primes, int n_primes, int limbs,
                         int64_t batch, void* d_ws, int64_t ws_bytes, void* stream) {
   if (!d_cands || !d_out || !h_primes || !d_ws || limbs <= 0 || n_primes <= 0 || batch <= 0) return MX_ERR_ARG;
   if (limbs > 1024) return MX_ERR_SIZE;
-  uint32_t top = 3;
-  for (int k = 0; k < n_primes; ++k) {
-    if (!(h_primes[k] & 1u) || h_primes[k] < 3 || h_primes[k] >= (1u << 31)) return MX_ERR_ARG;
-    if (h_primes[k] > top) top = h_primes[k];
-  }
-  hipStream_t s = (hipStream_t)stream;
-  SievePlan p = plan_sieve(limbs, n_primes);
+  uint32_t top;
+  if (!mx::sieve_primes_ok(h_primes, n_primes, top)) return MX_ERR_ARG;
+  const mx::SievePlan p = mx::plan_sieve(limbs, n_primes);
   if (p.total > ws_bytes) return MX_ERR_WORKSPACE;
-  char* ws = (char*)d_ws;
-  MX_TRY(upload_words(ws + p.off_primes, h_primes, (size_t)n_primes, s));
-  mx::SieveArgs a;
-  a.cands = d_cands; a.out = d_out;
-  a.primes = (const u32*)(ws + p.off_primes);
-  a.pw = (u32*)(ws + p.off_pw);
-  a.inv = (u64*)(ws + p.off_inv);
-  a.lim = (u64*)(ws + p.off_lim);
-  a.batch = batch; a.limbs = limbs; a.np = n_primes; a.np_pad = p.np_pad;
-  // limbs a 64-bit column takes between two folds (mx_sieve.hpp): 2^32 ((chunk + 1) top + 1) < 2^64
-  const int64_t chunk = (int64_t)(0xFFFFFFFEull / top) - 1;          // >= 1 for top < 2^31
-  a.chunk = (int)std::min<int64_t>(chunk, limbs);
-  MX_TRY(mx_launch(mx::sieve_setup_kernel, p.np_pad / 64, 64, 0, s, a));
-  int64_t nblocks = (batch + mx::SIEVE_C - 1) / mx::SIEVE_C;
-  size_t lds = (size_t)limbs * mx::SIEVE_C * 4;
-  return mx_launch(mx::sieve_kernel, nblocks, 64, lds, s, a);
+  return mx::run_sieve<false>(d_cands, d_out, h_primes, n_primes, top, limbs, batch, p, d_ws, (hipStream_t)stream);
 }
 
 // ---- share recombination -------------------------------------------------------------------

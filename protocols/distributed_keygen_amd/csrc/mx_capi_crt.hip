@@ -39,28 +39,19 @@ extern "C" int mx_crt_prepare(mx_crt_plan* plan, const uint32_t* h_p, const uint
                               int64_t plan_bytes, void* stream) {
   if (!plan || !h_p || !h_q || !h_hp || !h_hq || !h_pinv || !d_plan) return MX_ERR_ARG;
   if (limbs <= 0 || limbs2 <= 0) return MX_ERR_ARG;
-  if (!(h_p[0] & 1u) || !(h_q[0] & 1u)) return MX_ERR_MODULUS;
-  const int p_bits = bit_length(h_p, limbs), q_bits = bit_length(h_q, limbs);
-  if (p_bits < 2 || q_bits < 2) return MX_ERR_MODULUS;
-  if (same_words(h_p, h_q, limbs)) return MX_ERR_ARG;
-  // p^2, q^2 and N; the rows must hold N^2
-  const int sq_words = 2 * limbs;
-  std::vector<u32> p2(sq_words), q2(sq_words), n(sq_words), n2(2 * sq_words);
-  mul_words(p2.data(), h_p, limbs, h_p, limbs);
-  mul_words(q2.data(), h_q, limbs, h_q, limbs);
-  mul_words(n.data(), h_p, limbs, h_q, limbs);
-  mul_words(n2.data(), n.data(), sq_words, n.data(), sq_words);
-  if ((bit_length(n2.data(), 2 * sq_words) + 31) / 32 > limbs2) return MX_ERR_ARG;      // rows too narrow for N^2
-  const int rw = (std::max(bit_length(p2.data(), sq_words), bit_length(q2.data(), sq_words)) + 31) / 32;
+  CrtKey key;
+  MX_TRY(crt_key(key, h_p, h_q, limbs));
+  if (key.limbs_n2() > limbs2) return MX_ERR_ARG;      // rows too narrow for N^2
+  const int rw = key.rw;
   CrtShape sh;
-  MX_TRY(crt_shape(p_bits, q_bits, limbs2, rw, sh));
+  MX_TRY(crt_shape(key.p_bits, key.q_bits, limbs2, rw, sh));
   if (mx_crt_plan_bytes(limbs, limbs2) > plan_bytes) return MX_ERR_WORKSPACE;
 
   std::vector<u32> c((size_t)mx::CRT_ROWS * rw, 0u);
   auto row = [&](int r) { return &c[(size_t)r * rw]; };
   const int rs = sh.split.W * sh.split.L * sh.split.nblk;
   const int r1 = sh.recombine.W * sh.recombine.L * sh.nblk1;
-  const std::vector<u32>* squares[2] = {&p2, &q2};
+  const std::vector<u32>* squares[2] = {&key.p2, &key.q2};
   for (int half = 0; half < 2; ++half) {
     const u32* sq = squares[half]->data();            // zero above its own words: rw words of it are the modulus
     std::vector<u32> m(sq, sq + rw);
@@ -80,9 +71,9 @@ extern "C" int mx_crt_prepare(mx_crt_plan* plan, const uint32_t* h_p, const uint
   plan->limbs = limbs;
   plan->limbs2 = limbs2;
   plan->limbs_half = rw;
-  plan->limbs_n = (bit_length(n.data(), sq_words) + 31) / 32;
-  plan->p_bits = p_bits;
-  plan->q_bits = q_bits;
+  plan->limbs_n = key.limbs_n;
+  plan->p_bits = key.p_bits;
+  plan->q_bits = key.q_bits;
   return MX_OK;
 }
 
@@ -90,16 +81,10 @@ extern "C" int mx_crt_split_run(const mx_crt_plan* plan, const uint32_t* d_cts, 
   if (!plan || !plan->d_plan || !d_cts || !d_out || batch <= 0) return MX_ERR_ARG;
   CrtShape sh;
   MX_TRY(crt_shape(plan->p_bits, plan->q_bits, plan->limbs2, plan->limbs_half, sh));
-  if (crt_blocks(batch, sh.split.K) > 0x7FFFFFFF) return MX_ERR_SIZE;
   mx::CrtSplitArgs a;
   a.cts = d_cts; a.out = d_out; a.plan = (const u32*)plan->d_plan;
   a.batch = batch; a.limbs2 = plan->limbs2; a.rw = plan->limbs_half; a.nblk = sh.split.nblk; a.split_bit = sh.split_bit;
-  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(sh.split.K, [&](auto k) {
-    constexpr int K = decltype(k)::value;
-    using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-    const size_t lds = (size_t)(64 / K) * M_t::LDS_WORDS * 4;
-    return mx_launch(mx::crt_split_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, crt_blocks(batch, K), 64, lds, (hipStream_t)stream, a);
-  });
+  return launch_crt_split(a, sh.split.K, (hipStream_t)stream);
 }
 
 extern "C" int mx_crt_recombine_run(const mx_crt_plan* plan, const uint32_t* d_xp, const uint32_t* d_xq, uint32_t* d_out,

@@ -40,20 +40,11 @@ extern "C" int mx_crt_enc_prepare(mx_crt_enc_plan* plan, const uint32_t* h_p, co
                                   int limbs, int limbs_r, void* d_plan, int64_t plan_bytes, void* stream) {
   if (!plan || !h_p || !h_q || !h_p2inv || !d_plan) return MX_ERR_ARG;
   if (limbs <= 0 || limbs_r <= 0) return MX_ERR_ARG;
-  if (!(h_p[0] & 1u) || !(h_q[0] & 1u)) return MX_ERR_MODULUS;
-  const int p_bits = bit_length(h_p, limbs), q_bits = bit_length(h_q, limbs);
-  if (p_bits < 2 || q_bits < 2) return MX_ERR_MODULUS;
-  if (same_words(h_p, h_q, limbs)) return MX_ERR_ARG;
-  const int sq_words = 2 * limbs;
-  std::vector<u32> p2(sq_words), q2(sq_words), n(sq_words), n2(2 * sq_words);
-  mul_words(p2.data(), h_p, limbs, h_p, limbs);
-  mul_words(q2.data(), h_q, limbs, h_q, limbs);
-  mul_words(n.data(), h_p, limbs, h_q, limbs);
-  mul_words(n2.data(), n.data(), sq_words, n.data(), sq_words);
-  const int rw = (std::max(bit_length(p2.data(), sq_words), bit_length(q2.data(), sq_words)) + 31) / 32;
-  const int limbs_n = (bit_length(n.data(), sq_words) + 31) / 32;
+  CrtKey key;
+  MX_TRY(crt_key(key, h_p, h_q, limbs));
+  const int rw = key.rw;
   CrtEncShape sh;
-  MX_TRY(crt_enc_shape(p_bits, q_bits, limbs_r, rw, limbs_n, sh));
+  MX_TRY(crt_enc_shape(key.p_bits, key.q_bits, limbs_r, rw, key.limbs_n, sh));
   if (mx_crt_enc_plan_bytes(limbs, limbs_r) > plan_bytes) return MX_ERR_WORKSPACE;
 
   std::vector<u32> c((size_t)mx::ENC_ROWS * rw, 0u);
@@ -62,7 +53,7 @@ extern "C" int mx_crt_enc_prepare(mx_crt_enc_plan* plan, const uint32_t* h_p, co
   const int rp = sh.split.W * sh.split.L * sh.split.nblk;
   const int r2 = sh.lift.W * sh.lift.L * sh.lift.nblk;
   const u32* primes[2] = {h_p, h_q};
-  const std::vector<u32>* squares[2] = {&p2, &q2};
+  const std::vector<u32>* squares[2] = {&key.p2, &key.q2};
   for (int half = 0; half < 2; ++half) {
     const int r0 = mx::ENC_ROW_PSPLIT + 3 * half;
     std::memcpy(row(r0), primes[half], (size_t)lw * 4);
@@ -72,21 +63,21 @@ extern "C" int mx_crt_enc_prepare(mx_crt_enc_plan* plan, const uint32_t* h_p, co
     const int s0 = half ? mx::ENC_ROW_Q : mx::ENC_ROW_P;
     const u32* sq = squares[half]->data();
     std::memcpy(row(s0), sq, (size_t)rw * 4);
-    scaled_residue(row(s0 + 1), n.data(), sq, rw, 2 * r2);
+    scaled_residue(row(s0 + 1), key.n.data(), sq, rw, 2 * r2);
     two_pow_mod(row(s0 + 2), sq, rw, r2);
     two_pow_mod(row(s0 + 3), sq, rw, 2 * r2);
   }
-  scaled_residue(row(mx::ENC_ROW_Q + 4), h_p2inv, q2.data(), rw, r2);
+  scaled_residue(row(mx::ENC_ROW_Q + 4), h_p2inv, key.q2.data(), rw, r2);
   MX_TRY(upload_words(d_plan, c.data(), c.size(), (hipStream_t)stream));
   plan->d_plan = d_plan;
   plan->plan_bytes = plan_bytes;
   plan->limbs = limbs;
   plan->limbs_r = limbs_r;
-  plan->limbs2 = (bit_length(n2.data(), 2 * sq_words) + 31) / 32;
+  plan->limbs2 = key.limbs_n2();
   plan->limbs_half = rw;
-  plan->limbs_n = limbs_n;
-  plan->p_bits = p_bits;
-  plan->q_bits = q_bits;
+  plan->limbs_n = key.limbs_n;
+  plan->p_bits = key.p_bits;
+  plan->q_bits = key.q_bits;
   return MX_OK;
 }
 
@@ -95,16 +86,10 @@ extern "C" int mx_crt_prime_split_run(const mx_crt_enc_plan* plan, const uint32_
   if (!plan || !plan->d_plan || !d_rows || !d_out || batch <= 0) return MX_ERR_ARG;
   CrtEncShape sh;
   MX_TRY(crt_enc_shape(plan->p_bits, plan->q_bits, plan->limbs_r, plan->limbs_half, plan->limbs_n, sh));
-  if (crt_blocks(batch, sh.split.K) > 0x7FFFFFFF) return MX_ERR_SIZE;
   mx::CrtSplitArgs a;
   a.cts = d_rows; a.out = d_out; a.plan = (const u32*)plan->d_plan + (size_t)mx::ENC_ROW_PSPLIT * plan->limbs_half;
   a.batch = batch; a.limbs2 = plan->limbs_r; a.rw = plan->limbs_half; a.nblk = sh.split.nblk; a.split_bit = sh.split_bit;
-  return mx_dispatch_lanes<1, 2, 4, 8, 16, 32, 64>(sh.split.K, [&](auto k) {
-    constexpr int K = decltype(k)::value;
-    using M_t = mx::Mont<K, LIMBS_PER_LANE, LIMB_BITS, true>;
-    const size_t lds = (size_t)(64 / K) * M_t::LDS_WORDS * 4;
-    return mx_launch(mx::crt_split_kernel<K, LIMBS_PER_LANE, LIMB_BITS>, crt_blocks(batch, K), 64, lds, (hipStream_t)stream, a);
-  });
+  return launch_crt_split(a, sh.split.K, (hipStream_t)stream);
 }
 
 extern "C" int mx_crt_lift_run(const mx_crt_enc_plan* plan, const uint32_t* d_rho_p, const uint32_t* d_rho_q,

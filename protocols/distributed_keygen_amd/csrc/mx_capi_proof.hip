@@ -1,8 +1,8 @@
 // mx_sha256_rows / mx_dleq_response: the Fiat-Shamir challenge and the response of the decryption proofs (mx_sha256.hpp,
-// mx_proof.hpp) behind the C ABI (translation unit of its own, built in parallel with the others).
+// mx_response.hpp) behind the C ABI (translation unit of its own, built in parallel with the others).
 #include "mx_launch.hpp"
 #include "mx_sha256.hpp"
-#include "mx_proof.hpp"
+#include "mx_response.hpp"
 
 extern "C" int mx_sha256_rows(const uint8_t prefix[32], const uint32_t* const* d_rows, const int* limbs, int n_sets,
                               int64_t count, uint32_t* d_out, void* stream) {
@@ -30,14 +30,5 @@ extern "C" int mx_sha256_rows(const uint8_t prefix[32], const uint32_t* const* d
 
 extern "C" int mx_dleq_response(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z,
                                 uint8_t* d_status, int wz, int ew, int wx, int64_t count, void* stream) {
-  if (!d_rho || !d_e || !d_x || !d_z || !d_status || wz < 1 || ew < 1 || wx < 1 || count < 0) return MX_ERR_ARG;
-  if (wz > MX_DLEQ_MAX_WORDS || ew > MX_DLEQ_MAX_WORDS || wx > MX_DLEQ_MAX_WORDS) return MX_ERR_SIZE;
-  const int64_t nblocks = (count + mx::DLEQ_THREADS - 1) / mx::DLEQ_THREADS;
-  if (nblocks > 0x7FFFFFFF) return MX_ERR_SIZE;
-  if (count == 0) return MX_OK;
-  mx::DleqResponseArgs a;
-  a.rho = d_rho; a.e = d_e; a.x = d_x; a.z = d_z; a.status = d_status;
-  a.count = count;
-  a.wz = wz; a.ew = ew; a.wx = wx;
-  return mx_launch(mx::dleq_response_kernel, nblocks, mx::DLEQ_THREADS, 0, (hipStream_t)stream, a);
+  return mx::run_response<false>(d_rho, d_e, d_x, d_z, d_status, wz, ew, wx, count, stream);
 }

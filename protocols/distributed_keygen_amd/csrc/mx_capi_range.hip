@@ -129,14 +129,5 @@ extern "C" int mx_multiexp_run(const uint32_t* h_mod, int limbs, const uint32_t*
 
 extern "C" int mx_response_rows(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z,
                                 uint8_t* d_status, int wz, int ew, int wx, int64_t count, void* stream) {
-  if (!d_rho || !d_e || !d_x || !d_z || !d_status || wz < 1 || ew < 1 || wx < 1 || count < 0) return MX_ERR_ARG;
-  if (wz > MX_DLEQ_MAX_WORDS || ew > MX_DLEQ_MAX_WORDS || wx > MX_DLEQ_MAX_WORDS) return MX_ERR_SIZE;
-  const int64_t nblocks = (count + mx::RESPONSE_THREADS - 1) / mx::RESPONSE_THREADS;
-  if (nblocks > 0x7FFFFFFF) return MX_ERR_SIZE;
-  if (count == 0) return MX_OK;
-  mx::ResponseRowsArgs a;
-  a.rho = d_rho; a.e = d_e; a.x = d_x; a.z = d_z; a.status = d_status;
-  a.count = count;
-  a.wz = wz; a.ew = ew; a.wx = wx;
-  return mx_launch(mx::response_rows_kernel, nblocks, mx::RESPONSE_THREADS, 0, (hipStream_t)stream, a);
+  return mx::run_response<true>(d_rho, d_e, d_x, d_z, d_status, wz, ew, wx, count, stream);
 }

@@ -1,4 +1,4 @@
-// SHA-256 (FIPS 180-4) over limb rows on the device: the Fiat-Shamir challenge of the decryption proofs (mx_proof.hpp,
+// SHA-256 (FIPS 180-4) over limb rows on the device: the Fiat-Shamir challenge of the decryption proofs (mx_response.hpp,
 // threshold.py) without fetching the rows.  tools/proof_model.py (sha256_rows) is the model; DESIGN.md §4.25.
 //
 //   digest[r] = SHA-256(prefix | BE(rows_0[r]) | .. | BE(rows_{k-1}[r])),   r < count,   k <= 8 row sets

@@ -12,11 +12,21 @@
 // one every 63 limbs at 2^26, one per limb only above 2^30.  Primes < 2^31.
 // One wavefront handles SIEVE_C candidates: lanes run over primes (coalesced table reads), the
 // candidates' limbs are staged transposed in LDS so that one ds_read_b128 feeds four MACs.
+//
+// JOINT, the sieve of the safe-prime search (p = 2h + 1 with h and p prime) over rows h: out[e] = 1 iff some prime l of
+// the list has h ≡ 0 (l divides h) or h ≡ (l - 1) / 2 (l divides 2h + 1) modulo l.  Limbs, table rows and MACs are read
+// and issued once for the two conditions.  What is added per (candidate, block of 64 primes) comes after the loop: the
+// column acc ≡ h is folded once more with the table's own w1 = 2^32 mod l,
+//     x = lo32(acc) + hi32(acc) * w1  <=  (2^32 - 1) + (2^32 - 1)(l - 1)  <  2^32 l  <  2^63      for l < 2^31,
+// so 2x + 1 < 2^64 is exact in a register, and the exact-division test decides both v = x and v = 2x + 1; the second
+// product is 2 (x l^-1) + l^-1, one shift and one add.  Rows of one word have no table row 1 and need none: their
+// column is the word itself, below 2^32.  The plain form reads row 1 inside its fold only, which one-word rows never reach.
 #pragma once
 #include "mx_sieve_setup.hpp"
 
 namespace mx {
 
+template <bool JOINT>
 __global__ void __launch_bounds__(64) sieve_kernel(SieveArgs A) {
   extern __shared__ u32 smem[];   // [limbs][SIEVE_C]
   const int lane = threadIdx.x;
@@ -34,6 +44,8 @@ __global__ void __launch_bounds__(64) sieve_kernel(SieveArgs A) {
   for (int c = 0; c < SIEVE_C; ++c) hit[c] = 0;
   for (int k0 = 0; k0 < A.np_pad; k0 += 64) {
     const int k = k0 + lane;
+    u32 w1 = 0u;          // 2^32 mod l
+    if constexpr (JOINT) w1 = A.limbs > 1 ? A.pw[(long long)A.np_pad + k] : 0u;
     u64 acc[SIEVE_C];
 #pragma unroll
     for (int c = 0; c < SIEVE_C; ++c) acc[c] = 0;
@@ -47,20 +59,50 @@ __global__ void __launch_bounds__(64) sieve_kernel(SieveArgs A) {
         acc[4] += (u64)hi.x * w; acc[5] += (u64)hi.y * w; acc[6] += (u64)hi.z * w; acc[7] += (u64)hi.w * w;
       }
       if (j1 < A.limbs) {          // more limbs to come: fold the columns (limbs >= 2 here, so row 1 of the table exists)
-        const u32 w1 = A.pw[(long long)A.np_pad + k];          // 2^32 mod l
+        if constexpr (!JOINT) w1 = A.pw[(long long)A.np_pad + k];
 #pragma unroll
         for (int c = 0; c < SIEVE_C; ++c) acc[c] = (acc[c] & 0xFFFFFFFFull) + (acc[c] >> 32) * w1;
       }
     }
     const u64 inv = A.inv[k], lim = A.lim[k];
 #pragma unroll
-    for (int c = 0; c < SIEVE_C; ++c) hit[c] |= (k < A.np && acc[c] * inv <= lim) ? 1u : 0u;
+    for (int c = 0; c < SIEVE_C; ++c) {
+      if constexpr (JOINT) {
+        const u64 x = (acc[c] & 0xFFFFFFFFull) + (acc[c] >> 32) * w1;          // < 2^63: 2x + 1 does not wrap
+        const u64 t = x * inv;                                                   // l | x      iff t <= lim
+        const u64 t2 = (t << 1) + inv;                                           // l | 2x + 1 iff (2x + 1) l^-1 <= lim
+        hit[c] |= (k < A.np && (t <= lim || t2 <= lim)) ? 1u : 0u;
+      } else {
+        hit[c] |= (k < A.np && acc[c] * inv <= lim) ? 1u : 0u;
+      }
+    }
   }
 #pragma unroll
   for (int c = 0; c < SIEVE_C; ++c) {
     bool any = __any(hit[c] != 0);
     if (lane == 0 && e0 + c < A.batch) A.out[e0 + c] = any ? 1 : 0;
   }
+}
+
+// What mx_sieve (JOINT = false) and mx_safe_sieve (true) run once their own checks have passed: the primes into the
+// workspace, the argument block, the tables of the list (sieve_setup_kernel) and the sieve.
+template <bool JOINT>
+int run_sieve(const u32* d_rows, unsigned char* d_out, const u32* h_primes, int n_primes, u32 top, int limbs,
+              int64_t batch, const SievePlan& p, void* d_ws, hipStream_t s) {
+  char* ws = (char*)d_ws;
+  MX_TRY(upload_words(ws + p.off_primes, h_primes, (size_t)n_primes, s));
+  SieveArgs a;
+  a.cands = d_rows; a.out = d_out;
+  a.primes = (const u32*)(ws + p.off_primes);
+  a.pw = (u32*)(ws + p.off_pw);
+  a.inv = (u64*)(ws + p.off_inv);
+  a.lim = (u64*)(ws + p.off_lim);
+  a.batch = batch; a.limbs = limbs; a.np = n_primes; a.np_pad = p.np_pad;
+  // limbs a 64-bit column takes between two folds: 2^32 ((chunk + 1) top + 1) < 2^64
+  const int64_t chunk = (int64_t)(0xFFFFFFFEull / top) - 1;          // >= 1 for top < 2^31
+  a.chunk = (int)std::min<int64_t>(chunk, limbs);
+  MX_TRY(mx_launch(sieve_setup_kernel, p.np_pad / 64, 64, 0, s, a));
+  return mx_launch(sieve_kernel<JOINT>, sieve_blocks(batch), 64, (size_t)limbs * SIEVE_C * 4, s, a);
 }
 
 }  // namespace mx

@@ -1,7 +1,9 @@
-// What the sieves share (mx_sieve.hpp: sieve_kernel; mx_safe.hpp: safe_sieve_kernel): the argument block, the number of
-// candidates per wavefront and the kernel that fills the per-prime tables of the workspace.
+// What the two forms of the sieve share beside the kernel itself (mx_sieve.hpp: sieve_kernel<JOINT>, run_sieve<JOINT>): the
+// argument block, the number of candidates per wavefront, the kernel that fills the per-prime tables of the workspace,
+// and on the host the layout of that workspace and the check of the list of primes.
 #pragma once
 #include "mx_lanes.hpp"
+#include "mx_upload.hpp"
 
 namespace mx {
 
@@ -42,6 +44,32 @@ __global__ void sieve_setup_kernel(SieveArgs A) {
   A.inv[k] = x;
   A.lim[k] = ~0ull / l;
 }
+
+// the workspace, region for region: primes | 2^(32 j) mod l | l^-1 mod 2^64 | floor((2^64 - 1) / l)
+struct SievePlan { int np_pad; int64_t off_primes, off_pw, off_inv, off_lim, total; };
+SievePlan plan_sieve(int limbs, int np) {
+  SievePlan p;
+  p.np_pad = (np + 63) / 64 * 64;
+  int64_t o = 0;
+  p.off_primes = o; o += align256((int64_t)np * 4);
+  p.off_pw = o;     o += align256((int64_t)limbs * p.np_pad * 4);
+  p.off_inv = o;    o += align256((int64_t)p.np_pad * 8);
+  p.off_lim = o;    o += align256((int64_t)p.np_pad * 8);
+  p.total = o;
+  return p;
+}
+
+// every listed prime odd and in [3, 2^31); top = the largest of them
+bool sieve_primes_ok(const u32* h_primes, int n_primes, u32& top) {
+  top = 3;
+  for (int k = 0; k < n_primes; ++k) {
+    if (!(h_primes[k] & 1u) || h_primes[k] < 3 || h_primes[k] >= (1u << 31)) return false;
+    if (h_primes[k] > top) top = h_primes[k];
+  }
+  return true;
+}
+
+int64_t sieve_blocks(int64_t batch) { return (batch + SIEVE_C - 1) / SIEVE_C; }
 }  // namespace
 
 }  // namespace mx

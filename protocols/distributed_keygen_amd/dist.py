@@ -17,12 +17,13 @@ for callers that hold the whole list anyway, as the reference's loops do.  Shard
 uploads 1/world of the batch; the result is the same full, ordered tensor on every rank.
 
 The functions take the tensor-level engine API, so they are backend-agnostic: the tests drive
-them with the ``gloo`` backend on CPU tensors and a test double of the engine.
+them with the ``gloo`` backend on CPU tensors and a test double of the engine.  All of them are
+``_sharded`` below with what varies passed as data.
 """
 
 from __future__ import annotations
 
-from typing import Any, Optional, Sequence, Tuple
+from typing import Any, Callable, Optional, Sequence, Tuple
 
 
 def shard_bounds(total: int, rank: int, world: int) -> Tuple[int, int]:
@@ -45,16 +46,16 @@ def _world(group: Any) -> Tuple[int, int]:
     return dist.get_rank(group), dist.get_world_size(group)
 
 
-def _pad_rows(t, rows: int):
-    """Pad dim 0 of `t` to `rows` by repeating the last row (padding results are discarded)."""
+def _pad_rows(t, rows: int, dim: int = 0, empty: int = 0):
+    """Pad dimension `dim` of `t` to `rows` by repeating its last row (padding results are discarded)."""
     import torch
 
-    if t.shape[0] == rows:
+    have = t.shape[dim]
+    if have == rows:
         return t
-    reps = rows - t.shape[0]
-    if t.shape[0] == 0:        # an empty shard (fewer rows than ranks): nothing to repeat
-        return torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-    return torch.cat([t, t[-1:].expand(reps, *t.shape[1:])], dim=0).contiguous()
+    if have == 0:        # an empty shard (fewer rows than ranks): nothing to repeat
+        return torch.full(tuple(t.shape[:dim]) + (rows,) + tuple(t.shape[dim + 1 :]), empty, dtype=t.dtype, device=t.device)
+    return torch.cat([t, t.narrow(dim, have - 1, 1).repeat_interleave(rows - have, dim=dim)], dim=dim)
 
 
 def _gather_rows(local, world: int, group: Any):
@@ -92,35 +93,45 @@ def _pad_list(seq: Sequence[int], n: int, filler: int = 3) -> list:
     return seq + [seq[-1] if seq else filler] * (n - len(seq))
 
 
-def sharded_powmod_shared(engine: Any, bases_t, mod: int, exp: int, group: Any = None, total: Optional[int] = None):
-    """Full-batch ``engine.powmod_shared_t`` computed as world slices + one all-gather."""
+def _sharded(group: Any, total: Optional[int], whole: Callable, run: Callable, t, *, dim: int = 0, unit: int = 1,
+             out_unit: int = 1, lists: Sequence[Tuple[Sequence[int], int]] = (), empty: int = 0, per_unit: str = "",
+             unpack: Optional[Callable] = None):
+    """What every sharded_* function is.  World 1: ``whole()``, the engine call itself.  Otherwise this rank's units of
+    `t` — `unit` rows of dimension `dim` each; the slice of a replicated `t` (total None), or a shard-only `t` checked
+    against `total` — and of the per-unit host `lists` (pairs of a list and its filler for an empty shard), padded to
+    ceil(total / world) units by repeating the last one, so that a padding unit is a valid operand (an empty shard has
+    none to repeat: rows of `empty`, the fillers); ``run(rows, *lists)`` on them, whose result has `out_unit` rows per
+    unit; ONE all-gather; the padding trimmed; ``unpack`` where the result travelled as one row.  `per_unit` ends the
+    refusal of shard-only lists that do not match the shard's rows."""
     rank, world = _world(group)
     if world == 1:
-        return engine.powmod_shared_t(bases_t, mod, exp)
-    if total is not None:
-        per = _check_shard(bases_t.shape[0], total, rank, world)
-        return _gather_rows(engine.powmod_shared_t(_pad_rows(bases_t, per), mod, exp), world, group)[:total]
-    batch = bases_t.shape[0]
-    per = -(-batch // world)
-    padded = _pad_rows(bases_t, per * world)
-    local = engine.powmod_shared_t(padded[rank * per : (rank + 1) * per].contiguous(), mod, exp)
-    return _gather_rows(local, world, group)[:batch]
+        return whole()
+    if total is None:
+        total = t.shape[dim] // unit
+        per = -(-total // world)
+        t = _pad_rows(t, per * world * unit, dim, empty).narrow(dim, rank * per * unit, per * unit)
+        lists = [_pad_list(seq, per * world, filler)[rank * per : (rank + 1) * per] for seq, filler in lists]
+    else:
+        per = _check_shard(t.shape[dim], total, rank, world, unit)
+        if any(len(seq) * unit != t.shape[dim] for seq, _ in lists):
+            raise ValueError("shard-only input: " + per_unit)
+        t = _pad_rows(t, per * unit, dim, empty)
+        lists = [_pad_list(seq, per, filler) for seq, filler in lists]
+    full = _gather_rows(run(t.contiguous(), *lists), world, group)[: total * out_unit]
+    return unpack(full) if unpack else full
+
+
+def sharded_powmod_shared(engine: Any, bases_t, mod: int, exp: int, group: Any = None, total: Optional[int] = None):
+    """Full-batch ``engine.powmod_shared_t`` computed as world slices + one all-gather."""
+    return _sharded(group, total, lambda: engine.powmod_shared_t(bases_t, mod, exp),
+                    lambda rows: engine.powmod_shared_t(rows, mod, exp), bases_t)
 
 
 def sharded_powmod_nsquare(engine: Any, bases_t, n: int, exp: int, group: Any = None, total: Optional[int] = None):
     """Full-batch ``engine.powmod_nsquare_t`` (partial decryptions modulo n^2) as world slices + one
     all-gather — the multi-GPU form of the loop distributed_keygen.py:463-466."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.powmod_nsquare_t(bases_t, n, exp)
-    if total is not None:
-        per = _check_shard(bases_t.shape[0], total, rank, world)
-        return _gather_rows(engine.powmod_nsquare_t(_pad_rows(bases_t, per), n, exp), world, group)[:total]
-    batch = bases_t.shape[0]
-    per = -(-batch // world)
-    padded = _pad_rows(bases_t, per * world)
-    local = engine.powmod_nsquare_t(padded[rank * per : (rank + 1) * per].contiguous(), n, exp)
-    return _gather_rows(local, world, group)[:batch]
+    return _sharded(group, total, lambda: engine.powmod_nsquare_t(bases_t, n, exp),
+                    lambda rows: engine.powmod_nsquare_t(rows, n, exp), bases_t)
 
 
 def sharded_powmod_multi(
@@ -129,69 +140,26 @@ def sharded_powmod_multi(
 ):
     """``engine.powmod_multi_t`` with the candidate groups split across ranks (`total` = candidate groups of the whole
     batch when the caller passes only its shard's bases, moduli and exponents)."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.powmod_multi_t(bases_t, mods, exps, group_size)
-    if total is not None:
-        per = _check_shard(bases_t.shape[0], total, rank, world, group_size)
-        if len(mods) * group_size != bases_t.shape[0] or len(exps) != len(mods):
-            raise ValueError("shard-only input: one modulus and one exponent per candidate group of the shard")
-        local = engine.powmod_multi_t(_pad_rows(bases_t, per * group_size), _pad_list(mods, per), _pad_list(exps, per, 1), group_size)
-        return _gather_rows(local, world, group)[: total * group_size]
-    groups = len(mods)
-    per = -(-groups // world)
-    mods_p = list(mods) + [mods[-1]] * (per * world - groups)
-    exps_p = list(exps) + [exps[-1]] * (per * world - groups)
-    padded = _pad_rows(bases_t, per * world * group_size)
-    lo = rank * per
-    local = engine.powmod_multi_t(
-        padded[lo * group_size : (lo + per) * group_size].contiguous(), mods_p[lo : lo + per], exps_p[lo : lo + per], group_size
-    )
-    return _gather_rows(local, world, group)[: groups * group_size]
+    return _sharded(group, total, lambda: engine.powmod_multi_t(bases_t, mods, exps, group_size),
+                    lambda rows, m, e: engine.powmod_multi_t(rows, m, e, group_size), bases_t,
+                    unit=group_size, out_unit=group_size, lists=[(mods, 3), (exps, 1)],
+                    per_unit="one modulus and one exponent per candidate group of the shard")
 
 
 def sharded_sieve(engine: Any, cands_t, primes: Sequence[int], group: Any = None, total: Optional[int] = None):
     """uint8 verdict per candidate; candidates split across ranks, verdict bytes all-gathered."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.sieve_t(cands_t, primes)
-    if total is not None:
-        per = _check_shard(cands_t.shape[0], total, rank, world)
-        return _gather_rows(engine.sieve_t(_pad_rows(cands_t, per), primes), world, group)[:total]
-    batch = cands_t.shape[0]
-    per = -(-batch // world)
-    padded = _pad_rows(cands_t, per * world)
-    local = engine.sieve_t(padded[rank * per : (rank + 1) * per].contiguous(), primes)
-    return _gather_rows(local, world, group)[:batch]
+    return _sharded(group, total, lambda: engine.sieve_t(cands_t, primes), lambda rows: engine.sieve_t(rows, primes), cands_t)
 
 
 def sharded_combine(engine: Any, partials_t, n: int, theta_inv: int, group: Any = None, total: Optional[int] = None):
     """``engine.combine_t`` with the ciphertexts (dim 1 of partials_t) split across ranks.  Plaintext
     and status travel as ONE row per ciphertext (mx_combine_run's packed output), so the exchange is a
-    single all-gather."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.combine_t(partials_t, n, theta_inv)
+    single all-gather.  An empty shard is ones: they recombine to status 1 rows that the trim discards."""
     import torch
 
-    if total is not None:
-        per = _check_shard(partials_t.shape[1], total, rank, world)
-        have = partials_t.shape[1]
-        if have == 0:          # an empty shard: ones recombine to status 1 rows that the trim below discards
-            partials_t = torch.ones((partials_t.shape[0], per, partials_t.shape[2]), dtype=partials_t.dtype, device=partials_t.device)
-        elif have != per:
-            partials_t = torch.cat([partials_t, partials_t[:, -1:].expand(-1, per - have, -1)], dim=1)
-        packed = engine.combine_t(partials_t.contiguous(), n, theta_inv, packed=True)
-        full = _gather_rows(packed, world, group)[:total]
-        return full[:, :-1].contiguous(), full[:, -1].to(torch.uint8)
-    batch = partials_t.shape[1]
-    per = -(-batch // world)
-    if per * world != batch:
-        pad = per * world - batch
-        partials_t = torch.cat([partials_t, partials_t[:, -1:].expand(-1, pad, -1)], dim=1)
-    packed = engine.combine_t(partials_t[:, rank * per : (rank + 1) * per].contiguous(), n, theta_inv, packed=True)
-    full = _gather_rows(packed, world, group)[:batch]
-    return full[:, :-1].contiguous(), full[:, -1].to(torch.uint8)
+    return _sharded(group, total, lambda: engine.combine_t(partials_t, n, theta_inv),
+                    lambda rows: engine.combine_t(rows, n, theta_inv, packed=True), partials_t, dim=1, empty=1,
+                    unpack=lambda full: (full[:, :-1].contiguous(), full[:, -1].to(torch.uint8)))
 
 
 def sharded_biprime_v(engine: Any, g_t, mods: Sequence[int], exps: Sequence[int], group_size: int, keep: int,
@@ -202,58 +170,23 @@ def sharded_biprime_v(engine: Any, g_t, mods: Sequence[int], exps: Sequence[int]
     (``engine.biprime_v_t``; a candidate's modulus, exponent and generators stay on one GPU), then ONE
     all-gather whose rows carry a candidate's `keep` v values and its count of valid ones.
     g_t: int32 [groups*group_size, limbs].  Returns (v rows [groups*keep, limbs], counts [groups])."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.biprime_v_t(g_t, list(mods), list(exps), group_size, keep)
     import torch
 
     limbs = g_t.shape[1]
-    if total is not None:      # shard-only: g_t, mods, exps are this rank's candidates
-        per = _check_shard(g_t.shape[0], total, rank, world, group_size)
-        if len(mods) * group_size != g_t.shape[0] or len(exps) != len(mods):
-            raise ValueError("shard-only input: one modulus and one exponent per candidate of the shard")
-        groups = total
-        v_t, cnt_t = engine.biprime_v_t(_pad_rows(g_t, per * group_size), _pad_list(mods, per), _pad_list(exps, per, 1), group_size, keep)
-    else:
-        groups = len(mods)
-        per = -(-groups // world)
-        mods_p = list(mods) + [mods[-1]] * (per * world - groups)
-        exps_p = list(exps) + [exps[-1]] * (per * world - groups)
-        padded = _pad_rows(g_t, per * world * group_size)
-        lo = rank * per
-        v_t, cnt_t = engine.biprime_v_t(
-            padded[lo * group_size : (lo + per) * group_size].contiguous(), mods_p[lo : lo + per], exps_p[lo : lo + per],
-            group_size, keep,
-        )
-    row = torch.cat([v_t.reshape(per, keep * limbs), cnt_t.reshape(per, 1).to(v_t.dtype)], dim=1)
-    full = _gather_rows(row, world, group)[:groups]
-    return full[:, : keep * limbs].reshape(groups * keep, limbs).contiguous(), full[:, -1].contiguous()
+
+    def run(rows, m, e):
+        v_t, cnt_t = engine.biprime_v_t(rows, m, e, group_size, keep)
+        return torch.cat([v_t.reshape(len(m), keep * limbs), cnt_t.reshape(len(m), 1).to(v_t.dtype)], dim=1)
+
+    return _sharded(group, total, lambda: engine.biprime_v_t(g_t, list(mods), list(exps), group_size, keep), run, g_t,
+                    unit=group_size, lists=[(mods, 3), (exps, 1)],
+                    per_unit="one modulus and one exponent per candidate of the shard",
+                    unpack=lambda full: (full[:, : keep * limbs].reshape(len(full) * keep, limbs).contiguous(), full[:, -1].contiguous()))
 
 
 def sharded_biprime_vote(engine: Any, v_t, mods: Sequence[int], group: Any = None, total: Optional[int] = None):
     """Per-slot pass bytes [groups, n_slots] of ``engine.biprime_verdict_t`` with candidates split
-    across ranks; the pass bytes are all-gathered (the biprimality vote)."""
-    rank, world = _world(group)
-    if world == 1:
-        return engine.biprime_verdict_t(v_t, mods)
-    import torch
-
-    if total is not None:      # shard-only: v_t [parties, shard candidates, slots, limbs] and the shard's moduli
-        per = _check_shard(v_t.shape[1], total, rank, world)
-        if len(mods) != v_t.shape[1]:
-            raise ValueError("shard-only input: one modulus per candidate of the shard")
-        have = v_t.shape[1]
-        if have == 0:
-            v_t = torch.zeros((v_t.shape[0], per) + tuple(v_t.shape[2:]), dtype=v_t.dtype, device=v_t.device)
-        elif have != per:
-            v_t = torch.cat([v_t, v_t[:, -1:].expand(-1, per - have, -1, -1)], dim=1)
-        local = engine.biprime_verdict_t(v_t.contiguous(), _pad_list(mods, per))
-        return _gather_rows(local, world, group)[:total]
-    groups = len(mods)
-    per = -(-groups // world)
-    mods_p = list(mods) + [mods[-1]] * (per * world - groups)
-    if per * world != groups:
-        v_t = torch.cat([v_t, v_t[:, -1:].expand(-1, per * world - groups, -1, -1)], dim=1)
-    lo = rank * per
-    local = engine.biprime_verdict_t(v_t[:, lo : lo + per].contiguous(), mods_p[lo : lo + per])
-    return _gather_rows(local, world, group)[:groups]
+    across ranks (v_t [parties, candidates, slots, limbs]); the pass bytes are all-gathered (the biprimality vote)."""
+    return _sharded(group, total, lambda: engine.biprime_verdict_t(v_t, mods),
+                    lambda rows, m: engine.biprime_verdict_t(rows, m), v_t, dim=1, lists=[(mods, 3)],
+                    per_unit="one modulus per candidate of the shard")

@@ -280,6 +280,14 @@ class Engine:
     def _empty_rows(self, limbs: int, rows: int = 0):
         return self.torch.empty((rows, limbs), dtype=self.torch.int32, device=self.device)
 
+    def _flags_out(self, out_t, n: int):
+        """The caller's uint8 ``[n]`` output once checked, a fresh one when there is none."""
+        if out_t is None:
+            return self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+        if tuple(out_t.shape) != (n,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous():
+            raise ValueError(f"out_t must be contiguous uint8 of the shape ({n},)")
+        return out_t
+
     def _download_ints(self, rows_t) -> List[int]:
         """Device rows -> ints, through a pageable copy."""
         return _limbs.unpack(self.to_host(rows_t))
@@ -2235,11 +2243,7 @@ class Engine:
         `above` (a small host constant); device rows are read for that with two reductions unless the caller made the
         rows itself (`checked`)."""
         torch = self.torch
-        if not _is_device_rows(cands_t) or cands_t.dim() != 2 or cands_t.dtype != torch.int32 or not cands_t.is_contiguous():
-            raise ValueError("candidates must be contiguous int32 device rows [S, limbs]")
-        rows, limbs = cands_t.shape
-        if limbs < 1:
-            raise ValueError("candidates must have at least one word")
+        rows, limbs = self._word_rows(cands_t, "candidates")
         bits = 32 * limbs if bits is None else int(bits)
         if not 2 <= bits <= 32 * limbs:
             raise ValueError("bits must lie in [2, 32 * limbs]")
@@ -2285,10 +2289,7 @@ class Engine:
         total = rows * group_size
         if not _is_device_rows(bases_t) or tuple(bases_t.shape) != (total, limbs) or not bases_t.is_contiguous():
             raise ValueError(f"bases_t must be contiguous rows of the shape ({total}, {limbs})")
-        if out_t is not None and (tuple(out_t.shape) != (total,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
-            raise ValueError(f"out_t must be contiguous uint8 of the shape ({total},)")
-        if out_t is None:
-            out_t = self.torch.empty(total, dtype=self.torch.uint8, device=self.device)
+        out_t = self._flags_out(out_t, total)
         if total:
             d_t, s_t = self.mr_split_t(cands_t, bits, _checked=True)
             x0_t = self.powmod_multi_t(bases_t, (cands_t, bits), (d_t, bits), group_size)
@@ -2302,10 +2303,7 @@ class Engine:
         ``bits``: the bit length of the widest candidate, 32 * limbs when not given.  ValueError — nothing launched —
         for an even candidate, one below 3 or rows of another shape."""
         rows, limbs, bits = self._mr_candidates(cands_t, bits, checked=_checked)
-        if out_t is not None and (tuple(out_t.shape) != (rows,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
-            raise ValueError(f"out_t must be contiguous uint8 of the shape ({rows},)")
-        if out_t is None:
-            out_t = self.torch.empty(rows, dtype=self.torch.uint8, device=self.device)
+        out_t = self._flags_out(out_t, rows)
         if rows:
             self._call("mx_mr_base2", cands_t.data_ptr(), None, out_t.data_ptr(), limbs, bits, rows)
         return out_t
@@ -2332,11 +2330,42 @@ class Engine:
         if left.numel():
             left = left[self.miller_rabin_base2_t(cands_t[left].contiguous(), bits, _checked=True) != 0]
         if left.numel():
-            kept_t = cands_t[left].contiguous()
-            bases_t = self.generator_shares_t((kept_t, bits), rounds, rng=rng)
-            passed = self.miller_rabin_t(kept_t, bases_t, rounds, bits=bits, _checked=True)
-            out_t[left] = passed.view(-1, rounds).min(dim=1).values
+            self._random_rounds(cands_t, left, bits, rounds, rng, out_t)
         return out_t
+
+    def _random_rounds(self, rows_t, left, bits: int, rounds: int, rng, out_t) -> None:
+        """out_t[left] = the AND of `rounds` rounds to random bases on the candidates rows_t[left], at least one of them:
+        ONE generator_shares_t draw of survivors * rounds rows, then miller_rabin_t."""
+        kept_t = rows_t[left].contiguous()
+        bases_t = self.generator_shares_t((kept_t, bits), rounds, rng=rng)
+        passed = self.miller_rabin_t(kept_t, bases_t, rounds, bits=bits, _checked=True)
+        out_t[left] = passed.view(-1, rounds).min(dim=1).values
+
+    def _search(self, count: int, bits: int, rounds: int, batch: Optional[int], default_batch, draw, keep):
+        """`count` rows ``[count, limbs]`` in draw order: ``keep(draw(batch, limbs))`` — the rows that a fresh batch
+        yields — batch after batch while there are fewer.  `rounds` is only checked here.  ValueError — nothing
+        launched — for count < 0, bits < 16, rounds < 1 or batch < 1."""
+        count = int(count)
+        if count < 0 or bits < 16 or rounds < 1:
+            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
+        limbs = _limbs.limbs_for_bits(bits)
+        if count == 0:
+            return self._empty_rows(limbs)
+        batch = default_batch(count, bits) if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be at least 1")
+        found: List[Any] = []
+        have = 0
+        while have < count:
+            found.append(keep(draw(batch, limbs)))
+            have += int(found[-1].shape[0])
+        return self.torch.cat(found)[:count].contiguous()
+
+    @staticmethod
+    def _force_bits(rows_t, bit_positions: Sequence[int]):
+        for b in bit_positions:
+            rows_t[:, b >> 5] |= (1 << (b & 31)) - ((1 << 32) if (b & 31) == 31 else 0)      # the bit as an int32
+        return rows_t
 
     def prime_search_t(self, count: int, bits: int, rng, rounds: int = 64, batch: Optional[int] = None):
         """`count` random probable primes of exactly `bits` bits as rows ``[count, limbs]``: draw `batch` rows of `bits`
@@ -2349,49 +2378,23 @@ class Engine:
         nothing launched — for count < 0, bits < 16 or rounds < 1."""
         from . import primes as _primes
 
-        count, bits, rounds = int(count), int(bits), int(rounds)
-        if count < 0 or bits < 16 or rounds < 1:
-            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
-        limbs = _limbs.limbs_for_bits(bits)
-        if count == 0:
-            return self._empty_rows(limbs)
-        batch = _primes.default_batch(count, bits) if batch is None else int(batch)
-        if batch < 1:
-            raise ValueError("batch must be at least 1")
-        torch = self.torch
-        found: List[Any] = []
-        have = 0
-        while have < count:
-            rows_t = rng.rows_t(self, batch, bits)
-            for b in (bits - 1, bits - 2, 0):
-                rows_t[:, b >> 5] |= (1 << (b & 31)) - ((1 << 32) if (b & 31) == 31 else 0)      # the bit as an int32
-            verdict = self.probable_prime_t(rows_t, bits, rounds, rng, _checked=True)
-            found.append(rows_t[verdict != 0])
-            have += int(found[-1].shape[0])
-        return torch.cat(found)[:count].contiguous()
+        bits, rounds = int(bits), int(rounds)
+        return self._search(
+            count, bits, rounds, batch, _primes.default_batch,
+            lambda batch, limbs: self._force_bits(rng.rows_t(self, batch, bits), (bits - 1, bits - 2, 0)),
+            lambda rows_t: rows_t[self.probable_prime_t(rows_t, bits, rounds, rng, _checked=True) != 0])
 
     # ------------------------------------------------------------------ safe primes p = 2h + 1 (primes.py)
-    def _half_rows(self, halves_t) -> Tuple[int, int]:
-        if not _is_device_rows(halves_t) or halves_t.dim() != 2 or halves_t.dtype != self.torch.int32 or not halves_t.is_contiguous():
-            raise ValueError("halves must be contiguous int32 device rows [S, limbs]")
-        rows, limbs = halves_t.shape
-        if limbs < 1:
-            raise ValueError("halves must have at least one word")
-        return rows, limbs
-
     def safe_sieve_t(self, halves_t, primes: Sequence[int], out_t=None):
         """The joint sieve of h and 2h + 1 over rows of h: uint8 ``[S]``, 1 iff some listed prime l has h = 0 (l divides
         h) or h = (l - 1) / 2 (l divides 2h + 1) modulo l — ``sieve_t(h) | sieve_t(2h + 1)`` from one pass over limbs and
-        tables (mx_safe_sieve, csrc/mx_safe.hpp).  ValueError — nothing launched — for an empty list, a listed prime
+        tables (mx_safe_sieve, csrc/mx_sieve.hpp).  ValueError — nothing launched — for an empty list, a listed prime
         that is even, below 3 or not below 2^31, or rows of another shape."""
-        rows, limbs = self._half_rows(halves_t)
+        rows, limbs = self._word_rows(halves_t, "halves")
         primes = [int(p) for p in primes]
         if not primes or any(p < 3 or p % 2 == 0 or p >= 1 << 31 for p in primes):
             raise ValueError("a list of odd primes in [3, 2^31) expected")
-        if out_t is not None and (tuple(out_t.shape) != (rows,) or out_t.dtype != self.torch.uint8 or not out_t.is_contiguous()):
-            raise ValueError(f"out_t must be contiguous uint8 of the shape ({rows},)")
-        if out_t is None:
-            out_t = self.torch.empty(rows, dtype=self.torch.uint8, device=self.device)
+        out_t = self._flags_out(out_t, rows)
         if rows:
             h_primes = np.ascontiguousarray(np.asarray(primes, dtype=np.uint32))
             self._call("mx_safe_sieve", halves_t.data_ptr(), out_t.data_ptr(), h_primes.ctypes.data, len(h_primes), limbs, rows,
@@ -2402,7 +2405,7 @@ class Engine:
         """2h + 1 for rows of h, as rows of the same width (mx_safe_double: one launch).  ValueError — nothing launched —
         when a row has its top bit (bit 32 * limbs - 1) set, so that 2h + 1 would not fit the width, or for rows of
         another shape."""
-        rows, limbs = self._half_rows(halves_t)
+        rows, limbs = self._word_rows(halves_t, "halves")
         if rows and not _checked and bool((halves_t[:, limbs - 1] < 0).any()):      # the top bit is the int32's sign
             raise ValueError("2h + 1 does not fit the rows' width")
         out_t = self._empty_rows(limbs, rows)
@@ -2431,7 +2434,7 @@ class Engine:
         rounds, bits = int(rounds), int(bits)
         if rounds < 1:
             raise ValueError("rounds must be at least 1")
-        rows, limbs = self._half_rows(halves_t)
+        rows, limbs = self._word_rows(halves_t, "halves")
         if not 3 <= bits <= 32 * limbs:
             raise ValueError("bits must lie in [3, 32 * limbs]")
         self._mr_candidates(halves_t, bits - 1, above=_primes.SIEVE_BOUND, checked=_checked)
@@ -2449,10 +2452,7 @@ class Engine:
             left = left[self.miller_rabin_base2_t(full_t, bits, _checked=True) != 0]
         stages.append(left)
         if left.numel():
-            kept_t = halves_t[left].contiguous()
-            bases_t = self.generator_shares_t((kept_t, bits - 1), rounds, rng=rng)
-            passed = self.miller_rabin_t(kept_t, bases_t, rounds, bits=bits - 1, _checked=True)
-            out_t[left] = passed.view(-1, rounds).min(dim=1).values
+            self._random_rounds(halves_t, left, bits - 1, rounds, rng, out_t)
             left = left[out_t[left] != 0]
         stages.append(left)
         if _stages is not None:
@@ -2472,28 +2472,12 @@ class Engine:
         bits < 16 or rounds < 1."""
         from . import primes as _primes
 
-        count, bits, rounds = int(count), int(bits), int(rounds)
-        if count < 0 or bits < 16 or rounds < 1:
-            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
-        limbs = _limbs.limbs_for_bits(bits)
-        if count == 0:
-            return self._empty_rows(limbs)
-        batch = _primes.default_safe_batch(count, bits) if batch is None else int(batch)
-        if batch < 1:
-            raise ValueError("batch must be at least 1")
-        torch = self.torch
-        found: List[Any] = []
-        have = 0
-        while have < count:
-            halves_t = rng.rows_t(self, batch, bits - 1, limbs)
-            for b in (bits - 2, bits - 3, 0):
-                halves_t[:, b >> 5] |= (1 << (b & 31)) - ((1 << 32) if (b & 31) == 31 else 0)      # the bit as an int32
-            verdict = self.safe_prime_t(halves_t, bits, rounds, rng, _checked=True)
-            kept_t = halves_t[verdict != 0].contiguous()
-            if kept_t.shape[0]:
-                found.append(self.safe_double_t(kept_t, _checked=True))
-                have += int(kept_t.shape[0])
-        return torch.cat(found)[:count].contiguous()
+        bits, rounds = int(bits), int(rounds)
+        return self._search(
+            count, bits, rounds, batch, _primes.default_safe_batch,
+            lambda batch, limbs: self._force_bits(rng.rows_t(self, batch, bits - 1, limbs), (bits - 2, bits - 3, 0)),
+            lambda halves_t: self.safe_double_t(
+                halves_t[self.safe_prime_t(halves_t, bits, rounds, rng, _checked=True) != 0].contiguous(), _checked=True))
 
     # ------------------------------------------------------------------ decryption proofs of a dealt threshold key (threshold.py)
     def _word_rows(self, rows_t, what: str, width: Optional[int] = None) -> Tuple[int, int]:
@@ -2532,27 +2516,47 @@ class Engine:
         return out_t
 
     def dleq_response_t(self, rho_t, e_t, x_t, out_t=None):
-        """(z, status): z[r] = rho[r] + e[r] * x over the integers on the device (mx_dleq_response, csrc/mx_proof.hpp).
+        """(z, status): z[r] = rho[r] + e[r] * x over the integers on the device (mx_dleq_response, csrc/mx_response.hpp).
         ``rho_t`` ``[count, wz]``, ``e_t`` ``[count, ew]``, ``x_t`` ONE row ``[wx]`` or ``[1, wx]`` — the secret exponent,
         which stays on the device —, z ``[count, wz]`` (``out_t``; it may be ``rho_t``), status uint8 ``[count]``: 1 where
         the sum does not fit wz words (z then holds its low words).  The caller sizes wz so that it never happens and
         reads the status when it cannot be sure."""
-        count, wz = self._word_rows(rho_t, "rho rows")
-        _, ew = self._word_rows(e_t, "challenge rows")
-        if e_t.shape[0] != count:
-            raise ValueError("one challenge row per rho row expected")
         if not _is_device_rows(x_t) or x_t.dim() not in (1, 2) or (x_t.dim() == 2 and x_t.shape[0] != 1):
             raise ValueError("ONE exponent row on the device expected")
-        _, wx = self._word_rows(x_t.view(1, -1), "the exponent row")
+        return self._response("mx_dleq_response", rho_t, e_t, x_t.view(1, -1), out_t, shared=True)
+
+    def _response(self, symbol: str, rho_t, e_t, x_t, out_t, shared: bool):
+        """dleq_response_t (`shared`: ONE secret row ``[1, wx]``) and response_rows_t (one per rho row) behind their checks."""
+        count, wz = self._word_rows(rho_t, "rho rows")
+        _, ew = self._word_rows(e_t, "challenge rows")
+        _, wx = self._word_rows(x_t, "the exponent row" if shared else "secret rows")
+        if e_t.shape[0] != count or (not shared and x_t.shape[0] != count):
+            raise ValueError(f"one challenge row{'' if shared else ' and one secret row'} per rho row expected")
         if out_t is None:
             out_t = self.torch.empty_like(rho_t)
         elif self._word_rows(out_t, "z rows", wz)[0] != count:
             raise ValueError("one z row per rho row expected")
         status_t = self.torch.empty(count, dtype=self.torch.uint8, device=self.device)
         if count:
-            self._call("mx_dleq_response", rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(),
-                       wz, ew, wx, count)
+            self._call(symbol, rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(), wz, ew, wx, count)
         return out_t, status_t
+
+    def _multiexp_operands(self, inputs_t, index_t, weights_t, terms: int, weight_bits: int, window: int, checked: bool) -> Tuple[int, int, int]:
+        """(n_inputs, limbs, rows) of the device operands of a multi-exponentiation whose `terms` and `weight_bits` the
+        caller has bounded; ValueError for anything else, the index read for its range last and only when not `checked`."""
+        n_inputs, limbs = self._word_rows(inputs_t, "inputs")
+        if not 0 <= window <= 8:
+            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
+        rows, _ = self._word_rows(index_t, "the index", terms)
+        ww = (weight_bits + 31) // 32
+        if (not _is_device_rows(weights_t) or weights_t.dtype != self.torch.int32 or not weights_t.is_contiguous()
+                or weights_t.device != self.device or weights_t.dim() < 2 or weights_t.shape[0] != rows or weights_t.numel() != rows * terms * ww):
+            raise ValueError(f"contiguous int32 device weights of {terms} x {ww} words per row expected")
+        if n_inputs < 1:
+            raise ValueError("at least one input expected")
+        if rows and not checked and bool(((index_t < 0) | (index_t >= n_inputs)).any()):
+            raise ValueError("index out of range")
+        return n_inputs, limbs, rows
 
     @_int_args
     def multiexp_nsquare_rows_t(self, inputs_t, index_t, weights_t, terms: int, weight_bits: int, n: int, window: int = 0,
@@ -2564,25 +2568,14 @@ class Engine:
         pass: no plan, no sign split, no split-K — the thin entry for weights that are secret or were made on the device
         (``multiexp_nsquare_t`` plans public ones).  Canonical residues ``[rows, limbs2]``."""
         _check_modulus(n)
-        n_inputs, limbs2 = self._word_rows(inputs_t, "inputs")
-        _check_rows_n2(n, limbs2)
         nb = n.bit_length()
         if terms < 1 or weight_bits < 1 or weight_bits > 2 * nb + 64:
             raise ValueError(f"terms >= 1 and weight_bits in 1 .. 2 bits(n) + 64 = {2 * nb + 64} expected")
-        if not 0 <= window <= 8:
-            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
-        rows, _ = self._word_rows(index_t, "the index", terms)
-        ww = (weight_bits + 31) // 32
-        if (not _is_device_rows(weights_t) or weights_t.dtype != self.torch.int32 or not weights_t.is_contiguous()
-                or weights_t.device != self.device or weights_t.dim() < 2 or weights_t.shape[0] != rows or weights_t.numel() != rows * terms * ww):
-            raise ValueError(f"contiguous int32 device weights of {terms} x {ww} words per row expected")
-        if n_inputs < 1:
-            raise ValueError("at least one input expected")
+        n_inputs, limbs2, rows = self._multiexp_operands(inputs_t, index_t, weights_t, terms, weight_bits, window, _checked)
+        _check_rows_n2(n, limbs2)
         out_t = self._empty_rows(limbs2, rows)
         if rows == 0:
             return out_t
-        if not _checked and bool(((index_t < 0) | (index_t >= n_inputs)).any()):
-            raise ValueError("index out of range")
         if window == 0:
             window = self.multiexp_nsquare_shape(n, n_inputs, rows, terms, weight_bits)[0]
         plan = self.nsquare_plan(n, 1)          # the constants of mx_powmod_nsquare_prepare (its exponent is not read)
@@ -2743,30 +2736,19 @@ class Engine:
         longest term first: its table entry is fetched ahead of the squarings).  0^0 = 1.  Shared bases (every row the
         same index) and per-row bases go through the same kernel.  Canonical residues ``[rows, limbs]``."""
         _check_modulus(mod)
-        n_inputs, limbs = self._word_rows(inputs_t, "inputs")
-        if _limbs.limbs_for(mod) > limbs:
-            raise ValueError("rows narrower than the modulus")
         if terms < 1 or not 1 <= weight_bits <= _lib.MX_MULTIEXP_MAX_WEIGHT_BITS:
             raise ValueError(f"terms >= 1 and weight_bits in 1 .. {_lib.MX_MULTIEXP_MAX_WEIGHT_BITS} expected")
-        if not 0 <= window <= 8:
-            raise ValueError("window must lie in 1 .. 8 (0 = automatic)")
-        rows, _ = self._word_rows(index_t, "the index", terms)
-        ww = (weight_bits + 31) // 32
-        if (not _is_device_rows(weights_t) or weights_t.dtype != self.torch.int32 or not weights_t.is_contiguous()
-                or weights_t.device != self.device or weights_t.dim() < 2 or weights_t.shape[0] != rows or weights_t.numel() != rows * terms * ww):
-            raise ValueError(f"contiguous int32 device weights of {terms} x {ww} words per row expected")
-        if n_inputs < 1:
-            raise ValueError("at least one input expected")
         c_term_bits = None
         if term_bits is not None:
             if len(term_bits) != terms or any(not 0 <= int(b) <= weight_bits for b in term_bits):
                 raise ValueError("one length in 0 .. weight_bits per term expected")
             c_term_bits = (_ctypes.c_int32 * terms)(*[int(b) for b in term_bits])
+        n_inputs, limbs, rows = self._multiexp_operands(inputs_t, index_t, weights_t, terms, weight_bits, window, _checked)
+        if _limbs.limbs_for(mod) > limbs:
+            raise ValueError("rows narrower than the modulus")
         out_t = self._empty_rows(limbs, rows)
         if rows == 0:
             return out_t
-        if not _checked and bool(((index_t < 0) | (index_t >= n_inputs)).any()):
-            raise ValueError("index out of range")
         bits = mod.bit_length()
         if window == 0:
             window = self.multiexp_mod_shape(mod, n_inputs, rows, terms, weight_bits)[2]
@@ -2805,20 +2787,7 @@ class Engine:
         csrc/mx_response.hpp) — ``dleq_response_t`` with a secret row PER PROOF: ``rho_t`` ``[count, wz]``, ``e_t``
         ``[count, ew]``, ``x_t`` ``[count, wx]``, z ``[count, wz]`` (``out_t``), status uint8 ``[count]``: 1 where the sum
         does not fit wz words (z then holds its low words)."""
-        count, wz = self._word_rows(rho_t, "rho rows")
-        _, ew = self._word_rows(e_t, "challenge rows")
-        _, wx = self._word_rows(x_t, "secret rows")
-        if e_t.shape[0] != count or x_t.shape[0] != count:
-            raise ValueError("one challenge row and one secret row per rho row expected")
-        if out_t is None:
-            out_t = self.torch.empty_like(rho_t)
-        elif self._word_rows(out_t, "z rows", wz)[0] != count:
-            raise ValueError("one z row per rho row expected")
-        status_t = self.torch.empty(count, dtype=self.torch.uint8, device=self.device)
-        if count:
-            self._call("mx_response_rows", rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), out_t.data_ptr(), status_t.data_ptr(),
-                       wz, ew, wx, count)
-        return out_t, status_t
+        return self._response("mx_response_rows", rho_t, e_t, x_t, out_t, shared=False)
 
     def _widened(self, rows_t, words: int):
         """The rows zero-extended to `words` words (a copy only when they are narrower)."""
@@ -3137,12 +3106,16 @@ class Engine:
         """cts_t int32 [batch, limbs2] (any value of that width) -> int32 [2, batch, limbs_half]: the rows modulo p^2, then
         modulo q^2; ``out[0]`` and ``out[1]`` are the contiguous operands of ``powmod_nsquare_t(.., p, p - 1)`` and
         ``(.., q, q - 1)``."""
-        batch, limbs2 = cts_t.shape
-        plan = self.crt_plan(p, q, limbs2)
+        _, limbs2 = cts_t.shape
+        return self._crt_split(self.crt_plan(p, q, limbs2), "mx_crt_split_run", cts_t)
+
+    def _crt_split(self, plan: _Plan, symbol: str, rows_t):
+        """crt_split_t and crt_prime_split_t: the rows modulo the two moduli of `plan`, int32 [2, batch, limbs_half]."""
+        batch = rows_t.shape[0]
         out_t = self.torch.empty((2, batch, plan.desc.limbs_half), dtype=self.torch.int32, device=self.device)
         if batch:
-            cts_t = cts_t.contiguous()
-            self._small(lambda: self._call("mx_crt_split_run", plan.desc, cts_t.data_ptr(), out_t.data_ptr(), batch, plans=(plan,)))
+            rows_t = rows_t.contiguous()
+            self._small(lambda: self._call(symbol, plan.desc, rows_t.data_ptr(), out_t.data_ptr(), batch, plans=(plan,)))
         return out_t
 
     @_int_args
@@ -3244,13 +3217,8 @@ class Engine:
         modulo q, zero above the prime; ``out[0]`` and ``out[1]`` are the contiguous operands of
         ``powmod_shared_t(.., p, q mod (p-1))`` and ``(.., q, p mod (q-1))``, whose results ``powmod_nsquare_t(.., p, p)``
         and ``(.., q, q)`` take as they are."""
-        batch, limbs_r = rows_t.shape
-        plan = self.crt_enc_plan(p, q, limbs_r)
-        out_t = self.torch.empty((2, batch, plan.desc.limbs_half), dtype=self.torch.int32, device=self.device)
-        if batch:
-            rows_t = rows_t.contiguous()
-            self._small(lambda: self._call("mx_crt_prime_split_run", plan.desc, rows_t.data_ptr(), out_t.data_ptr(), batch, plans=(plan,)))
-        return out_t
+        _, limbs_r = rows_t.shape
+        return self._crt_split(self.crt_enc_plan(p, q, limbs_r), "mx_crt_prime_split_run", rows_t)
 
     @_int_args
     def crt_lift_t(self, rho_p_t, rho_q_t, p: int, q: int, messages_t=None, halves_t=None, packed: bool = False):

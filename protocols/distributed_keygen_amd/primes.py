@@ -21,7 +21,7 @@ digits of d = (n - 1) / 2^s — the class private_key.py documents for the key's
 compaction between the stages show which candidates were dropped where; those are not the key.
 
 Safe primes, p = 2h + 1 with h prime as well (``random_safe_primes`` / ``is_safe_prime_batch``;
-``Engine.safe_prime_t``).  The candidates are the halves h.  One joint sieve (``Engine.safe_sieve_t``, csrc/mx_safe.hpp)
+``Engine.safe_prime_t``).  The candidates are the halves h.  One joint sieve (``Engine.safe_sieve_t``, csrc/mx_sieve.hpp)
 drops every h with h = 0 or h = (l - 1) / 2 modulo a prime l below ``SIEVE_BOUND`` — l divides h or 2h + 1 — from one
 pass over limbs and tables; then the base 2 on h, the base 2 on p, and the `rounds` random bases on h ONLY.  Pocklington:
 with h an odd prime, p = 2h + 1, 3 not dividing p (the sieve saw to it) and 2^(p-1) = 1 mod p, p is prime — the proven

@@ -37,7 +37,7 @@ What this is and is not — read before use:
   * Side channels.  The partial decryption follows the tape of the share like every modexp of this engine
     (``Engine.set_fixed_window``); a = chat^rho and b = v^rho gather table rows by the digits of rho — the same class of
     side channel as the tape on the share.  The response z = rho + e x_i is computed with control
-    flow and addresses that do not depend on x_i, rho or e (csrc/mx_proof.hpp).  Plans and the share's row stay in
+    flow and addresses that do not depend on x_i, rho or e (csrc/mx_response.hpp).  Plans and the share's row stay in
     device memory for as long as their objects live.
 """
 

@@ -1,4 +1,4 @@
-"""The kernels of the decryption proofs (csrc/mx_sha256.hpp, csrc/mx_proof.hpp) and the dealt threshold key over them on
+"""The kernels of the decryption proofs (csrc/mx_sha256.hpp, csrc/mx_response.hpp) and the dealt threshold key over them on
 the GPU — Engine.sha256_rows_t / dleq_response_t / multiexp_nsquare_rows_t / dleq_prove_t / dleq_verify_t and
 threshold.py — bit for bit against hashlib, Python ints and tools/proof_model.py.
 

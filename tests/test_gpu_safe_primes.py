@@ -1,4 +1,4 @@
-"""The safe-prime kernels (csrc/mx_safe.hpp) and the search over them on the GPU — Engine.safe_sieve_t / safe_double_t /
+"""The safe-prime kernels (csrc/mx_sieve.hpp, csrc/mx_safe.hpp) and the search over them on the GPU — Engine.safe_sieve_t / safe_double_t /
 safe_prime_t / safe_prime_search_t, primes.random_safe_primes / is_safe_prime_batch, PaillierPrivateKey.generate(...,
 safe=True) / check_primes(safe=True) — every verdict bit for bit against tools/mr_model.py.
 

@@ -18,7 +18,7 @@ reproducible on the CPU:
     probable_prime(cands, bits, rounds, draw)      sieve, base 2 on the survivors, `rounds` random bases on what is left
     prime_search(count, bits, draw, rounds, batch) draw, force the two top bits and bit 0, test, keep, draw again
 
-Safe primes p = 2h + 1 (csrc/mx_safe.hpp; ``Engine.safe_sieve_t`` / ``safe_prime_t`` / ``safe_prime_search_t``), `bits`
+Safe primes p = 2h + 1 (csrc/mx_sieve.hpp, csrc/mx_safe.hpp; ``Engine.safe_sieve_t`` / ``safe_prime_t`` / ``safe_prime_search_t``), `bits`
 the width of p, the candidates the halves h of bits - 1 bits:
 
     safe_sieve_hit(h)                              some sieve prime divides h or 2h + 1, as one gcd with the primes' product
