@@ -1059,6 +1059,29 @@ int mx_multiexp_run(const uint32_t* h_mod, int limbs, const uint32_t* d_inputs, 
 int mx_response_rows(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, uint32_t* d_z, uint8_t* d_status,
                      int wz, int ew, int wx, int64_t count, void* stream);
 
+/* ---- one-of-k membership proofs: the challenge arithmetic of the OR-composition (ABI 4.4, addition) ------------------
+ * The one step of a Cramer-Damgard-Schoenmakers proof that c encrypts one of k public values which no other entry point
+ * covers (csrc/mx_member.hpp; tools/member_model.py is the model; protocols/distributed_keygen_amd/membership.py composes
+ * it with the modexps, the multi-exponentiation, the hash and the inverse above).  Rows of four little-endian words:
+ * d_e [count][4] the challenges, d_sim and d_out [count][k][4] the per-branch challenges, d_index [count] the REAL branch
+ * of each row (the prover's secret, in [0, k): an index outside it selects no branch), d_status [count].
+ *   mode MX_MEMBER_MASK   d_out[r][j] = (j == d_index[r]) ? 0 : d_sim[r][j]
+ *   mode MX_MEMBER_SPLIT  d_out[r][d_index[r]] = d_e[r] - sum_(j != d_index[r]) d_sim[r][j]  mod 2^128, the other slots copied
+ *   mode MX_MEMBER_SUM    d_status[r] = (sum_j d_sim[r][j] mod 2^128 != d_e[r]); d_index and d_out are not read
+ * One row per lane; control flow and addresses depend on (k, count) only — the real slot is selected by compare-and-mask
+ * arithmetic, every slot of every row is read and written —, carries and borrows are add-with-compare.  d_out may be
+ * d_sim.  A pointer a mode does not use (d_e for the mask; d_status for mask and split; d_index and d_out for the sum)
+ * may be NULL.  One launch on `stream`, no workspace, no synchronisation; a count of 0 returns MX_OK without a launch.
+ * MX_ERR_ARG for a null pointer the mode uses, k outside MX_MEMBER_MIN_K .. MX_MEMBER_MAX_K, a negative count or an
+ * unknown mode; MX_ERR_SIZE for more rows than a launch addresses.  A refused call launches nothing. */
+#define MX_MEMBER_MASK 0
+#define MX_MEMBER_SPLIT 1
+#define MX_MEMBER_SUM 2
+#define MX_MEMBER_MIN_K 2
+#define MX_MEMBER_MAX_K 16
+int mx_member_challenges(const uint32_t* d_e, const uint32_t* d_sim, const int32_t* d_index, uint32_t* d_out,
+                         uint8_t* d_status, int k, int64_t count, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

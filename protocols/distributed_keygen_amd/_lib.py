@@ -62,6 +62,8 @@ MX_GEN_MAX_PARTIES = 16       # include/mxpaillier.h
 MX_SHA256_MAX_SETS = 8        # include/mxpaillier.h
 MX_MULTIEXP_MAX_WEIGHT_BITS = 16384      # include/mxpaillier.h
 MX_FIXEDBASE_POWER, MX_FIXEDBASE_ENCRYPT, MX_FIXEDBASE_RANDOMIZE = 0, 1, 2
+MX_MEMBER_MASK, MX_MEMBER_SPLIT, MX_MEMBER_SUM = 0, 1, 2      # include/mxpaillier.h
+MX_MEMBER_MIN_K, MX_MEMBER_MAX_K = 2, 16
 
 _P4 = [POINTER(c_int)] * 4
 
@@ -189,6 +191,7 @@ SYMBOLS = {
     "mx_multiexp_workspace_bytes": (c_int64, [c_int, c_int, c_int64, c_int, c_int]),
     "mx_multiexp_run": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "mx_response_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "mx_member_challenges": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
 }
 
 

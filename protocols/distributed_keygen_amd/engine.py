@@ -3006,6 +3006,171 @@ class Engine:
         mark("compare")
         return verdict
 
+    # ------------------------------------------------------------------ one-of-k membership proofs (membership.py)
+    def member_challenges_t(self, e_t, sim_t, index_t, mode: int, out_t=None):
+        """The challenge arithmetic of the one-of-k proofs on the device (mx_member_challenges, csrc/mx_member.hpp):
+        ``sim_t`` ``[count, 4 k]`` rows of k challenges of four words, 2 <= k <= 16, ``e_t`` ``[count, 4]``, ``index_t``
+        int32 ``[count]`` in [0, k) — the REAL slot of each row, the prover's secret.  mode 0 (mask): slot index[r] zeroed
+        (``e_t`` may be None); mode 1 (split): slot index[r] = e[r] - the sum of the others mod 2^128; both return
+        ``[count, 4 k]`` rows (``out_t``; it may be ``sim_t``).  mode 2 (sum): uint8 ``[count]``, 1 where the sum of the
+        row mod 2^128 differs from e[r] (``index_t`` may be None: none is read).  Control flow and addresses of the
+        kernel do not depend on the index; it is read here once, for its range."""
+        torch = self.torch
+        mode = int(mode)
+        if mode not in (_lib.MX_MEMBER_MASK, _lib.MX_MEMBER_SPLIT, _lib.MX_MEMBER_SUM):
+            raise ValueError("mode 0 (mask), 1 (split) or 2 (sum) expected")
+        count, words = self._word_rows(sim_t, "challenge slots")
+        k = words // 4
+        if words % 4 or not _lib.MX_MEMBER_MIN_K <= k <= _lib.MX_MEMBER_MAX_K:
+            raise ValueError(f"rows of {_lib.MX_MEMBER_MIN_K} .. {_lib.MX_MEMBER_MAX_K} slots of four words expected")
+        if mode != _lib.MX_MEMBER_MASK and self._word_rows(e_t, "challenge rows", 4)[0] != count:
+            raise ValueError("one challenge row per row of slots expected")
+        if mode == _lib.MX_MEMBER_SUM:
+            status_t = torch.empty(count, dtype=torch.uint8, device=self.device)
+            if count:
+                self._call("mx_member_challenges", e_t.data_ptr(), sim_t.data_ptr(), None, None, status_t.data_ptr(), k, count, mode)
+            return status_t
+        if (not _is_device_rows(index_t) or index_t.dtype != torch.int32 or index_t.dim() != 1 or not index_t.is_contiguous()
+                or index_t.device != self.device or index_t.shape[0] != count):
+            raise ValueError("a contiguous int32 device index [count] expected")
+        if count and bool(((index_t < 0) | (index_t >= k)).any()):
+            raise ValueError("index out of range")
+        if out_t is None:
+            out_t = torch.empty_like(sim_t)
+        elif self._word_rows(out_t, "output slots", words)[0] != count:
+            raise ValueError("one output row per row of slots expected")
+        if count:
+            self._call("mx_member_challenges", None if e_t is None else e_t.data_ptr(), sim_t.data_ptr(), index_t.data_ptr(), out_t.data_ptr(),
+                       None, k, count, mode)
+        return out_t
+
+    @staticmethod
+    def member_shape(n: int, k: int) -> Dict[str, int]:
+        """Bit lengths and row widths of a one-of-k proof (tools/member_model.py: shape).  ValueError unless 2 <= k <= 16."""
+        n, k = int(n), int(k)
+        if not _lib.MX_MEMBER_MIN_K <= k <= _lib.MX_MEMBER_MAX_K:
+            raise ValueError(f"{_lib.MX_MEMBER_MIN_K} <= k <= {_lib.MX_MEMBER_MAX_K} expected")
+        return dict(k=k, draw_bits=n.bit_length() + 64, e_bits=128, e_words=4, limbs_n=_limbs.limbs_for(n), limbs2=_limbs.limbs_for(n * n))
+
+    def _member_values(self, n: int, values: Sequence[int]) -> Tuple[Dict[str, int], List[int]]:
+        values = [int(s) for s in values]
+        sh = self.member_shape(n, len(values))
+        _check_modulus(n)
+        if len(set(values)) != len(values) or any(not 0 <= s < n for s in values):
+            raise ValueError("distinct values in [0, N) expected")
+        return sh, values
+
+    def _member_branches_t(self, rows_t, factors: Sequence[int], n: int):
+        """rows[r] * (1 + factors[j] n) mod n^2 as ``[count k, limbs2]`` rows, row r k + j: the k branch rows of every
+        ciphertext (or of its inverse) — the public factors through mx_fma_mod, the products through mx_mulmod."""
+        k, count = len(factors), rows_t.shape[0]
+        fac_t = self._one_plus_mn_t(self._const_rows(factors, _limbs.limbs_for(n)), n)
+        return self.mulmod_t(rows_t.repeat_interleave(k, dim=0).contiguous(), fac_t.repeat(count, 1).contiguous(), n * n)
+
+    def _member_challenge_t(self, ctx: bytes, cts_t, a_t):
+        """The 128-bit challenge rows: c and the k commitments of a row as ONE row set of k limbs2 words."""
+        return self.sha256_rows_t(ctx, [cts_t, a_t])[:, 4:8].contiguous()
+
+    @_int_args
+    def member_prove_t(self, cts_t, index_t, randomness_t, n: int, values: Sequence[int], ctx: bytes, rng=None, draws=None,
+                       _stages: Optional[List[Any]] = None):
+        """The proofs (a, e, z) that the ciphertexts ``cts_t`` = (1 + n)^(values[index[r]]) r^n hold one of ``values``
+        (membership.py; tools/member_model.py is the model): ``index_t`` int32 ``[count]`` in [0, k) — which value, the
+        secret —, ``randomness_t`` ``[count, limbs(n)]`` rows of r below n.  The two draws — ``[count k, limbs(n^2)]``
+        rows of bits(n) + 64 bits, then ``[count k, 4]`` rows of 128 bits, for EVERY slot — come from ``rng`` (a
+        ``DeviceRng``: two consecutive calls in this order) or are the rows ``draws`` a test passes.  Returns
+        ``(a_t [count, k limbs(n^2)], e_t [count, 4 k], z_t [count, k limbs(n)])``.  Every slot is treated alike: the
+        real one is masked, split and placed by compare-and-select arithmetic (csrc/mx_member.hpp, ``torch.where`` over a
+        slot mask), never by an address or a branch.  Nothing per row leaves the device.  ValueError if a ciphertext
+        is no unit modulo n^2.  `_stages`, a list, receives (name, end event) pairs for tools/member_probe.py."""
+        torch = self.torch
+        sh, values = self._member_values(n, values)
+        k, ln, limbs2 = sh["k"], sh["limbs_n"], sh["limbs2"]
+        count, _ = self._word_rows(cts_t, "ciphertext rows", limbs2)
+        if self._word_rows(randomness_t, "randomness rows", ln)[0] != count:
+            raise ValueError("one randomness row per ciphertext expected")
+        if (rng is None) == (draws is None):
+            raise ValueError("exactly one of rng and draws expected")
+        if draws is None:
+            draws = (rng.rows_t(self, count * k, sh["draw_bits"], limbs2), rng.rows_t(self, count * k, 128))
+        zt_t, et_t = draws
+        if self._word_rows(zt_t, "z draws", limbs2)[0] != count * k or self._word_rows(et_t, "e draws", 4)[0] != count * k:
+            raise ValueError("k draws of each kind per ciphertext expected")
+        n2 = n * n
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        sim_t = self.member_challenges_t(None, et_t.view(count, 4 * k), index_t, _lib.MX_MEMBER_MASK)      # (the range of the index is checked here)
+        if count == 0:
+            return self._empty_rows(k * limbs2, 0), sim_t, self._empty_rows(k * ln, 0)
+        mark("mask")
+        ubar_t = self._member_branches_t(self.modinv_t(cts_t, n2), values, n)
+        mark("branches")
+        a_t = self.powmod_nsquare_t(zt_t, n, n)
+        mark("r_pow_n")
+        own = torch.arange(count * k, device=self.device, dtype=torch.int32).view(-1, 1).contiguous()
+        a_t = self.mulmod_t(a_t, self.multiexp_nsquare_rows_t(ubar_t, own, sim_t.view(count * k, 4), 1, 128, n, _checked=True), n2, out_t=a_t)
+        a_t = a_t.view(count, k * limbs2)
+        mark("multiexp_n2")
+        e_t = self.member_challenges_t(self._member_challenge_t(ctx, cts_t, a_t), sim_t, index_t, _lib.MX_MEMBER_SPLIT, out_t=sim_t)
+        mark("hash_split")
+        real = (torch.arange(k, device=self.device, dtype=torch.int32).view(1, k) == index_t.view(-1, 1)).view(count, k, 1)
+        zero = torch.zeros((), dtype=torch.int32, device=self.device)
+
+        def own_slot(rows_t):          # the real slot of every row, by mask and sum: no address depends on the index
+            return torch.where(real, rows_t, zero).sum(dim=1, dtype=torch.int32).contiguous()
+
+        zs_t = self._reduce_wide_t(zt_t, n).view(count, k, ln)
+        zi_t = self._own_pair_t(own_slot(zs_t), randomness_t, own_slot(e_t.view(count, k, 4)), n)
+        z_t = torch.where(real, zi_t.view(count, 1, ln), zs_t).contiguous().view(count, k * ln)
+        mark("response")
+        return a_t, e_t, z_t
+
+    @_int_args
+    def member_verify_t(self, cts_t, a_t, e_t, z_t, n: int, values: Sequence[int], ctx: bytes, _stages: Optional[List[Any]] = None):
+        """bool ``[count]``: row r is True iff c < n^2, every 0 < a_j < n^2 and 0 < z_j < n, sum_j e_j = e (mod 2^128)
+        with e recomputed from the hash, and z_j^n = a_j u_j^(e_j) (mod n^2) for every j, u_j = c (1 + (n - s_j) n) —
+        the verdicts of the proofs of ``member_prove_t``, one per row; a bad row never raises.  ZERO is refused because
+        a_j = z_j = 0 satisfies the equation for any c (a forgery without a witness); it is the only non-unit that needs
+        a check when every prime factor of n exceeds 2^128 — any other would factor n.  Rows with a value out of range
+        are replaced by 1 (their challenges by 0) before any kernel reads them.  No inverse of anything the prover sent
+        is taken."""
+        torch = self.torch
+        sh, values = self._member_values(n, values)
+        k, ln, limbs2 = sh["k"], sh["limbs_n"], sh["limbs2"]
+        count, _ = self._word_rows(cts_t, "ciphertext rows", limbs2)
+        for r_t, what, words in ((a_t, "a rows", k * limbs2), (e_t, "e rows", 4 * k), (z_t, "z rows", k * ln)):
+            if self._word_rows(r_t, what, words)[0] != count:
+                raise ValueError(f"one of the {what} per ciphertext expected")
+        if count == 0:
+            return torch.ones(0, dtype=torch.bool, device=self.device)
+        n2 = n * n
+        ok = (self._rows_below(cts_t, n2) & self._rows_below(a_t.view(count * k, limbs2), n2).view(count, k).all(dim=1)
+              & self._rows_below(z_t.view(count * k, ln), n).view(count, k).all(dim=1))
+        # zero is refused: a_j = z_j = 0 satisfies 0^n = 0 u_j^(e_j) for ANY c — a forgery without a witness
+        ok = ok & (a_t.view(count, k, limbs2) != 0).any(dim=2).all(dim=1) & (z_t.view(count, k, ln) != 0).any(dim=2).all(dim=1)
+        keep = ok.view(-1, 1, 1)
+
+        def harmless(rows_t, slots: int, value: int):
+            fill = torch.zeros((1, 1, rows_t.shape[1] // slots), dtype=torch.int32, device=self.device)
+            fill[0, 0, 0] = value
+            return torch.where(keep, rows_t.view(count, slots, -1), fill).contiguous().view(count, -1)
+
+        cts_t, a_t, z_t, e_t = harmless(cts_t, 1, 1), harmless(a_t, k, 1), harmless(z_t, k, 1), harmless(e_t, k, 0)
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        split_ok = self.member_challenges_t(self._member_challenge_t(ctx, cts_t, a_t), e_t, None, _lib.MX_MEMBER_SUM) == 0
+        mark("hash_sum")
+        u_t = self._member_branches_t(cts_t, [(n - s) % n for s in values], n)
+        mark("branches")
+        left_t = self.powmod_nsquare_t(self._widened(z_t.view(count * k, ln), limbs2), n, n)
+        mark("r_pow_n")
+        right_t = self.multiexp_nsquare_rows_t(torch.cat([a_t.view(count * k, limbs2), u_t]), self._own_pair_index(count * k),
+                                               self._one_and(e_t.view(count * k, 4)), 2, 128, n, _checked=True)
+        mark("multiexp_n2")
+        verdict = ok & split_ok & (left_t == right_t).view(count, k * limbs2).all(dim=1)
+        mark("compare")
+        return verdict
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):

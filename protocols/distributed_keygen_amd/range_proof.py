@@ -22,7 +22,8 @@ What this is and is not — read before use:
   * WHAT IS PROVEN is |m| < 2^(l + 257) — the usual slack of E + K + 1 = 257 bits — and NOT m < 2^l: an honest prover
     with m = 2^l, or a good deal more, still passes.  Size the slots and bounds of what consumes the ciphertext for
     l + 257 bits.  It is a proof of KNOWLEDGE of m and r.  It bounds the WHOLE plaintext, not each slot of a slot-packed
-    one: a proof per slot is out of scope here.
+    one: a proof per slot is out of scope here — ``membership`` proves that a ciphertext holds one of a few public
+    values EXACTLY (a bit, a one-hot ballot ``slots.one_hot_values``, a small slot value before ``packing.pack``).
   * No sign appears anywhere: m is a non-negative integer.  A caller with signed values v in [-2^(l-1), 2^(l-1)) proves
     m = v + 2^(l-1) (and the receiver subtracts the offset's ciphertext homomorphically, or accounts for it in the sum).
   * Soundness holds under the strong RSA assumption in Nh, in the random-oracle model (SHA-256, a 128-bit challenge),

@@ -151,6 +151,18 @@ def slot_bits_for(value_bits: int, weight_bits: int = 0, terms: int = 1, bias_bi
     return max((-lo - 1).bit_length(), hi.bit_length()) + 1
 
 
+def one_hot_values(n: int, slot_bits: int, k: int) -> List[int]:
+    """[2^(slot_bits j) for j < k]: the plaintexts of a one-hot ballot over k choices in the slot layout — a vote for
+    choice j is 1 in slot j and 0 elsewhere — as the public list of a membership proof (``membership.prove_batch``).
+    A sum of up to 2^slot_bits - 1 such ballots (unsigned slots) decodes slot by slot into the tally.  ValueError
+    unless 1 <= k <= ``packing.slots_per_ciphertext(n, slot_bits)``.  Pure host code."""
+    n, b, k = int(n), int(slot_bits), int(k)
+    cap = slots_per_ciphertext(n, b)
+    if not 1 <= k <= cap:
+        raise ValueError(f"1 .. {cap} slots of {b} bits fit a plaintext modulo a {n.bit_length()}-bit N, got {k}")
+    return [1 << (b * j) for j in range(k)]
+
+
 async def decrypt_sequence_slots(scheme: Any, ciphertexts: Sequence[Any], slot_bits: int, count: int, signed: bool = True,
                                  receivers: Optional[List[str]] = None, engine: Any = None) -> Optional[List[int]]:
     """Threshold-decrypt ciphertexts of slot-packed plaintexts (``encrypt``, or results of ``homomorphic`` operations on
