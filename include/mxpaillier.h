@@ -1082,6 +1082,29 @@ int mx_response_rows(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t*
 int mx_member_challenges(const uint32_t* d_e, const uint32_t* d_sim, const int32_t* d_index, uint32_t* d_out,
                          uint8_t* d_status, int k, int64_t count, int mode, void* stream);
 
+/* ---- multiplication proofs: the response modulo M with its quotient (ABI 4.4, addition) --------------------------------
+ * The one step of a proof of correct multiplication (Damgard-Jurik 2001, section 4) which no other entry point covers
+ * (csrc/mx_response_mod.hpp; tools/mul_model.py is the model; protocols/distributed_keygen_amd/multiplication.py composes
+ * it with the modexps, the multi-exponentiation and the hash above): per row r < count
+ *   s = d_rho[r] + d_e[r] * d_x[r] over the integers,   d_w[r] = s mod M,   d_t[r] = floor(s / M).
+ * Little-endian words: d_rho, d_x and d_w [count][wn], d_e and d_t [count][ew], d_mod ONE modulus of wn words ON THE
+ * DEVICE whose top word is non-zero (any such M, odd or even), d_status [count]: 1 iff the quotient does not fit ew words —
+ * which happens only when d_rho[r] or d_x[r] is not below M —, d_t[r] then holds its low ew words and d_w[r] is the
+ * correct residue all the same.  The two constants are the caller's, from M:
+ *   shift = the number of leading zero bits of M's top word (0 .. 31),
+ *   recip = floor(2^96 / (Md + 1)),  Md = the top 64 bits of M << shift (a one-word M: (M << shift) << 32),
+ * so that 2^32 <= recip < 2^33; with other constants the rows are wrong, nothing else happens.
+ * One row per lane; control flow and addresses depend on (wn, ew, count) only — quotient digits are estimated from the
+ * top words and corrected by two masked subtractions, carries and borrows are add-with-compare —, no private segment, no
+ * LDS.  d_w and d_t serve as the kernel's temporaries: NO OUTPUT MAY OVERLAP AN INPUT OR THE OTHER OUTPUT.  One launch on
+ * `stream`, no workspace, no synchronisation; a count of 0 returns MX_OK without a launch.
+ * MX_ERR_ARG for a null pointer, a width below 1, a negative count, a shift outside 0 .. 31 or a recip outside
+ * [2^32, 2^33); MX_ERR_SIZE for a width above MX_DLEQ_MAX_WORDS or more rows than a launch addresses.  A refused call
+ * launches nothing. */
+int mx_response_mod_rows(const uint32_t* d_rho, const uint32_t* d_e, const uint32_t* d_x, const uint32_t* d_mod,
+                         uint64_t recip, int shift, uint32_t* d_w, uint32_t* d_t, uint8_t* d_status, int wn, int ew,
+                         int64_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

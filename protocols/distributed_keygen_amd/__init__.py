@@ -45,10 +45,11 @@ def configure_hw_queues(queues: int = 16) -> bool:
     return True
 
 
-from . import device_rng, homomorphic, limbs, membership, packing, primes, randomizer, range_proof, slots, threshold  # noqa: F401
+from . import device_rng, homomorphic, limbs, membership, multiplication, packing, primes, randomizer, range_proof, secure_product, slots, threshold  # noqa: F401
 from .device_rng import DeviceRng  # noqa: F401
 from .engine import Engine, default_engine  # noqa: F401
 from .membership import MembershipProofs  # noqa: F401
+from .multiplication import MultiplicationProofs  # noqa: F401
 from .primes import is_probable_prime_batch, random_primes  # noqa: F401
 from .private_key import PaillierPrivateKey  # noqa: F401
 from .randomizer import FastRandomizer, generate_base  # noqa: F401

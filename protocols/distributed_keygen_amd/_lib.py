@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_int, c_int64, c_void_p, POINTER
+from ctypes import c_char_p, c_int, c_int64, c_uint64, c_void_p, POINTER
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libmxpaillier.so"
@@ -192,6 +192,7 @@ SYMBOLS = {
     "mx_multiexp_run": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "mx_response_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
     "mx_member_challenges": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "mx_response_mod_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
 }
 
 

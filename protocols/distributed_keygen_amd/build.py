@@ -18,7 +18,8 @@ SOURCES = [CSRC / "mx_capi.hip", CSRC / "mx_capi_n2.hip", CSRC / "mx_capi_n2w.hi
            CSRC / "mx_capi_n2mm.hip", CSRC / "mx_capi_slots.hip", CSRC / "mx_capi_n2h.hip",
            CSRC / "mx_capi_n2c.hip", CSRC / "mx_capi_share.hip", CSRC / "mx_capi_n2sp.hip",
            CSRC / "mx_capi_gen.hip", CSRC / "mx_capi_crt.hip", CSRC / "mx_capi_crt_enc.hip", CSRC / "mx_capi_mr.hip",
-           CSRC / "mx_capi_safe.hip", CSRC / "mx_capi_proof.hip", CSRC / "mx_capi_range.hip", CSRC / "mx_capi_member.hip"]
+           CSRC / "mx_capi_safe.hip", CSRC / "mx_capi_proof.hip", CSRC / "mx_capi_range.hip", CSRC / "mx_capi_member.hip",
+           CSRC / "mx_capi_mul.hip"]
 HEADERS = sorted(CSRC.glob("*.hpp")) + [PKG.parent.parent / "include" / "mxpaillier.h"]
 BUILD_INPUTS = [Path(__file__).resolve(), PKG / "asm_align.py"]      # the build recipe itself
 

@@ -3171,6 +3171,178 @@ class Engine:
         mark("compare")
         return verdict
 
+    # ------------------------------------------------------------------ multiplication proofs (multiplication.py)
+    @staticmethod
+    def response_mod_constants(mod: int, wn: int) -> Tuple[int, int]:
+        """(recip, shift) of mx_response_mod_rows for a modulus of ``wn`` words whose top word is non-zero: shift = the
+        leading zeros of the top word, recip = floor(2^96 / (Md + 1)) for Md = the top 64 bits of mod << shift
+        (tools/mul_model.py: response_mod_constants)."""
+        mod, wn = int(mod), int(wn)
+        top = mod >> (32 * (wn - 1)) if wn >= 1 else 0
+        if not 0 < top < 1 << 32:
+            raise ValueError("a modulus of wn words whose top word is non-zero expected")
+        shift = 32 - top.bit_length()
+        md = (mod << shift) >> (32 * (wn - 2)) if wn >= 2 else (mod << shift) << 32
+        return (1 << 96) // (md + 1), shift
+
+    @_int_args
+    def response_mod_rows_t(self, rho_t, e_t, x_t, mod: int, out_t=None):
+        """(w, t, status): w[r] = (rho[r] + e[r] x[r]) mod ``mod`` and t[r] = (rho[r] + e[r] x[r]) // ``mod`` on the
+        device (mx_response_mod_rows, csrc/mx_response_mod.hpp) — the response of a Sigma-protocol whose exponent lives
+        modulo N, with the quotient that corrects the second response.  ``rho_t`` and ``x_t`` ``[count, wn]`` (x: a
+        secret row per proof), ``e_t`` ``[count, ew]``, ``mod`` of exactly wn words (``limbs.limbs_for(mod) == wn``), odd
+        or even; w ``[count, wn]`` (``out_t``), canonical; t ``[count, ew]``; status uint8 ``[count]``: 1 where the
+        quotient does not fit ew words — only when rho or x is not below ``mod`` —, t then holds its low words and w is
+        still the residue.  Control flow and addresses of the kernel depend on the shapes only.  The outputs are the
+        kernel's temporaries: ``out_t`` sharing storage with an input is a ValueError."""
+        count, wn = self._word_rows(rho_t, "rho rows")
+        _, ew = self._word_rows(e_t, "challenge rows")
+        if self._word_rows(x_t, "secret rows", wn)[0] != count or e_t.shape[0] != count:
+            raise ValueError("one challenge row and one secret row per rho row expected")
+        if mod < 1 or _limbs.limbs_for(mod) != wn:
+            raise ValueError("a modulus of exactly the width of the rows expected")
+        recip, shift = self.response_mod_constants(mod, wn)
+        if out_t is None:
+            out_t = self.torch.empty_like(rho_t)
+        else:
+            if self._word_rows(out_t, "w rows", wn)[0] != count:
+                raise ValueError("one w row per rho row expected")
+            mine = out_t.untyped_storage().data_ptr()
+            if any(mine == t.untyped_storage().data_ptr() for t in (rho_t, e_t, x_t)):
+                raise ValueError("the output must not alias an input: its rows are the kernel's temporaries")
+        t_t = self.torch.empty((count, ew), dtype=self.torch.int32, device=self.device)
+        status_t = self.torch.empty(count, dtype=self.torch.uint8, device=self.device)
+        if count:
+            mod_t = self._const_rows([mod], wn)
+            self._call("mx_response_mod_rows", rho_t.data_ptr(), e_t.data_ptr(), x_t.data_ptr(), mod_t.data_ptr(), recip, shift,
+                       out_t.data_ptr(), t_t.data_ptr(), status_t.data_ptr(), wn, ew, count)
+        return out_t, t_t, status_t
+
+    @staticmethod
+    def mul_shape(n: int) -> Dict[str, int]:
+        """Bit lengths and row widths of a multiplication proof (tools/mul_model.py: shape)."""
+        n = int(n)
+        return dict(draw_bits=n.bit_length() + 64, e_bits=128, e_words=4, limbs_n=_limbs.limbs_for(n), limbs2=_limbs.limbs_for(n * n))
+
+    def _mul_shape_checked(self, n: int) -> Dict[str, int]:
+        _check_modulus(n)
+        sh = self.mul_shape(n)
+        if sh["draw_bits"] > (n * n).bit_length() - 1 or n.bit_length() < 96:
+            raise ValueError(f"a modulus of {n.bit_length()} bits leaves no room for 64 extra bits of randomness below n^2")
+        return sh
+
+    def _mul_challenge_t(self, ctx: bytes, ca_t, cb_t, d_t, a_t, b_t):
+        """The 128-bit challenge rows over the five rows of the width of n^2."""
+        return self.sha256_rows_t(ctx, [ca_t, cb_t, d_t, a_t, b_t])[:, 4:8].contiguous()
+
+    def _reduce_n2_t(self, rows_t, n: int):
+        """rows below n^2 -> their residues modulo n, ``[count, limbs(n)]``: lo + 2^(32 limbs(n)) hi through the
+        response modulo n — rho = lo, x = hi, e = 2^(32 limbs(n)) mod n — whose residue is right whatever lo and hi are."""
+        ln = _limbs.limbs_for(n)
+        count = rows_t.shape[0]
+        lo_t = rows_t[:, :ln].contiguous()
+        hi_t = self._widened(rows_t[:, ln:].contiguous(), ln) if rows_t.shape[1] > ln else self.torch.zeros_like(lo_t)
+        return self.response_mod_rows_t(lo_t, self._repeated_row((1 << (32 * ln)) % n, ln, count), hi_t, n)[0]
+
+    @_int_args
+    def mul_prove_t(self, ca_t, cb_t, a_t, ra_t, gamma_t, n: int, ctx: bytes, rng=None, draws=None, _stages: Optional[List[Any]] = None):
+        """(d, A, B, w, z, y): d = c_b^a gamma^n mod n^2 and the proof that it holds a b for the a inside
+        c_a = (1 + n)^a r_a^n (multiplication.py; tools/mul_model.py is the model).  ``ca_t`` and ``cb_t``
+        ``[count, limbs(n^2)]``, ``a_t`` (below n), ``ra_t`` and ``gamma_t`` ``[count, limbs(n)]``.  The draws — count rows
+        of bits(n) + 64 bits at the width of n^2 for x, then 2 count such rows for u and v (all u first) — come from
+        ``rng`` (a ``DeviceRng``: two consecutive calls in this order) or are the two row sets ``draws`` a test passes.
+        c_b^a and c_b^x are ONE multi-exponentiation launch over the count inputs c_b (2 count rows, one table per
+        input); u^n, v^n and gamma^n ONE launch of the r^n route on 3 count rows; (w, t) = divmod(x + e a, n) is the
+        response kernel modulo n.  Nothing per row leaves the device.  ValueError for an a that is not below n.
+        `_stages`, a list, receives (name, end event) pairs for tools/mul_probe.py."""
+        torch = self.torch
+        sh = self._mul_shape_checked(n)
+        ln, limbs2 = sh["limbs_n"], sh["limbs2"]
+        count, _ = self._word_rows(ca_t, "c_a rows", limbs2)
+        for r_t, what, words in ((cb_t, "c_b rows", limbs2), (a_t, "a rows", ln), (ra_t, "r_a rows", ln), (gamma_t, "gamma rows", ln)):
+            if self._word_rows(r_t, what, words)[0] != count:
+                raise ValueError(f"one of the {what} per statement expected")
+        if (rng is None) == (draws is None):
+            raise ValueError("exactly one of rng and draws expected")
+        if draws is None:
+            draws = (rng.rows_t(self, count, sh["draw_bits"], limbs2), rng.rows_t(self, 2 * count, sh["draw_bits"], limbs2))
+        xd_t, uv_t = draws
+        if self._word_rows(xd_t, "x draws", limbs2)[0] != count or self._word_rows(uv_t, "u and v draws", limbs2)[0] != 2 * count:
+            raise ValueError("one x draw and two further draws per statement expected")
+        if count == 0:
+            return (self._empty_rows(limbs2),) * 3 + (self._empty_rows(ln),) * 3
+        if not bool(self._rows_below(a_t, n).all()):
+            raise ValueError("a must be below n")
+        n2 = n * n
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        x_t = self._reduce_wide_t(xd_t, n)
+        cbn_t = self._reduce_n2_t(cb_t, n)
+        mark("reduce")
+        rn_t = self.powmod_nsquare_t(torch.cat([uv_t, self._widened(gamma_t, limbs2)]), n, n)          # u^n | v^n | gamma^n
+        mark("r_pow_n")
+        index_t = torch.arange(count, device=self.device, dtype=torch.int32).repeat(2).view(-1, 1).contiguous()
+        pw_t = self.multiexp_nsquare_rows_t(cb_t, index_t, torch.cat([a_t, x_t]), 1, 32 * ln, n, _checked=True)          # c_b^a | c_b^x
+        d_t = self.mulmod_t(pw_t[:count], rn_t[2 * count:], n2)
+        bb_t = self.mulmod_t(pw_t[count:], rn_t[count : 2 * count], n2)
+        aa_t = self.mulmod_t(rn_t[:count], self._one_plus_mn_t(x_t, n), n2)
+        mark("multiexp_n2")
+        e_t = self._mul_challenge_t(ctx, ca_t, cb_t, d_t, aa_t, bb_t)
+        mark("hash")
+        w_t, t_t, _ = self.response_mod_rows_t(x_t, e_t, a_t, n)          # (x, a < n: the quotient fits the four words)
+        mark("response")
+        uvn_t = self._reduce_wide_t(uv_t, n)
+        z_t = self._own_pair_t(uvn_t[:count], ra_t, e_t, n)
+        y_t = self._own_pair_t(self._own_pair_t(uvn_t[count:], cbn_t, t_t, n), gamma_t, e_t, n)
+        mark("multiexp_n")
+        return d_t, aa_t, bb_t, w_t, z_t, y_t
+
+    @_int_args
+    def mul_verify_t(self, ca_t, cb_t, d_t, a_t, b_t, w_t, z_t, y_t, n: int, ctx: bytes, _stages: Optional[List[Any]] = None):
+        """bool ``[count]``: row r is True iff 0 < c_a, c_b, d, A, B < n^2, w < n, 0 < z, y < n,
+        (1 + w n) z^n = A c_a^e and c_b^w y^n = B d^e (mod n^2) with e recomputed from the hash — the verdicts of the
+        proofs of ``mul_prove_t``, one per row; a bad row never raises.  ZERO is refused: A = z = 0 satisfies the first
+        equation and B = y = 0 the second for any statement.  Rows with a value out of range are replaced by 1 (w by 0)
+        before any kernel reads them.  No inverse of anything the prover sent is taken."""
+        torch = self.torch
+        sh = self._mul_shape_checked(n)
+        ln, limbs2 = sh["limbs_n"], sh["limbs2"]
+        count, _ = self._word_rows(ca_t, "c_a rows", limbs2)
+        for r_t, what, words in ((cb_t, "c_b rows", limbs2), (d_t, "d rows", limbs2), (a_t, "A rows", limbs2), (b_t, "B rows", limbs2),
+                                 (w_t, "w rows", ln), (z_t, "z rows", ln), (y_t, "y rows", ln)):
+            if self._word_rows(r_t, what, words)[0] != count:
+                raise ValueError(f"one of the {what} per statement expected")
+        if count == 0:
+            return torch.ones(0, dtype=torch.bool, device=self.device)
+        n2 = n * n
+        ok = self._rows_below(w_t, n)
+        for r_t, bound in ((ca_t, n2), (cb_t, n2), (d_t, n2), (a_t, n2), (b_t, n2), (z_t, n), (y_t, n)):
+            ok = ok & self._rows_below(r_t, bound) & (r_t != 0).any(dim=1)          # zero is refused
+        keep = ok.view(-1, 1)
+
+        def harmless(rows_t, value: int):
+            fill = torch.zeros((1, rows_t.shape[1]), dtype=torch.int32, device=self.device)
+            fill[0, 0] = value
+            return torch.where(keep, rows_t, fill).contiguous()
+
+        ca_t, cb_t, d_t, a_t, b_t, z_t, y_t = (harmless(r_t, 1) for r_t in (ca_t, cb_t, d_t, a_t, b_t, z_t, y_t))
+        w_t = harmless(w_t, 0)
+        mark = (lambda name: None) if _stages is None else (lambda name: _stages.append((name, self._event())))
+        mark("start")
+        e_t = self._mul_challenge_t(ctx, ca_t, cb_t, d_t, a_t, b_t)
+        mark("hash")
+        rn_t = self.powmod_nsquare_t(self._widened(torch.cat([z_t, y_t]), limbs2), n, n)          # z^n | y^n
+        mark("r_pow_n")
+        own = torch.arange(count, device=self.device, dtype=torch.int32).view(-1, 1).contiguous()
+        left1_t = self.mulmod_t(rn_t[:count], self._one_plus_mn_t(w_t, n), n2)
+        left2_t = self.mulmod_t(self.multiexp_nsquare_rows_t(cb_t, own, w_t, 1, 32 * ln, n, _checked=True), rn_t[count:], n2)
+        right_t = self.multiexp_nsquare_rows_t(torch.cat([a_t, b_t, ca_t, d_t]), self._own_pair_index(2 * count),
+                                               self._one_and(torch.cat([e_t, e_t])), 2, 128, n, _checked=True)          # A c_a^e | B d^e
+        mark("multiexp_n2")
+        verdict = ok & (left1_t == right_t[:count]).all(dim=1) & (left2_t == right_t[count:]).all(dim=1)
+        mark("compare")
+        return verdict
+
     # ------------------------------------------------------------------ share recombination
     @_int_args
     def combine_t(self, partials_t, n: int, theta_inv: int, out_t=None, status_t=None, packed: bool = False):
