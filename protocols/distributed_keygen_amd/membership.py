@@ -55,7 +55,7 @@ from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import limbs as _limbs
+from . import limbs as _limbs, proof_flows as _flows
 from .range_proof import E_BITS, _engine_of, _host, _int_bytes, _lp, _rows_of
 
 MIN_BITS = 260                   # every prime factor of N must exceed 2^E_BITS; shorter moduli cannot even claim it
@@ -78,11 +78,7 @@ def _check_values(n: int, values: Sequence[int]) -> List[int]:
 
 def shape(n: int, k: int) -> dict:
     """Bit lengths and row widths of a proof (tools/member_model.py: shape)."""
-    n, k = int(n), int(k)
-    if not MIN_K <= k <= MAX_K:
-        raise ValueError(f"{MIN_K} <= k <= {MAX_K} expected")
-    return dict(k=k, draw_bits=n.bit_length() + 64, e_bits=E_BITS, e_words=E_BITS // 32, limbs_n=_limbs.limbs_for(n),
-                limbs2=_limbs.limbs_for(n * n))
+    return _flows.member_shape(n, k)
 
 
 def context(n: int, values: Sequence[int], label: bytes) -> bytes:

@@ -50,7 +50,7 @@ from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import limbs as _limbs
+from . import limbs as _limbs, proof_flows as _flows
 from .range_proof import E_BITS, _engine_of, _host, _int_bytes, _lp, _rows_of
 
 MIN_BITS = 260                   # every prime factor of N must exceed 2^E_BITS; shorter moduli cannot even claim it
@@ -66,9 +66,7 @@ def _check_modulus(n: int) -> None:
 
 def shape(n: int) -> dict:
     """Bit lengths and row widths of a proof (tools/mul_model.py: shape)."""
-    n = int(n)
-    return dict(draw_bits=n.bit_length() + 64, e_bits=E_BITS, e_words=E_BITS // 32, limbs_n=_limbs.limbs_for(n),
-                limbs2=_limbs.limbs_for(n * n))
+    return _flows.mul_shape(n)
 
 
 def context(n: int, label: bytes) -> bytes:

@@ -53,10 +53,9 @@ from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import limbs as _limbs
+from . import limbs as _limbs, proof_flows as _flows
+from .proof_flows import E_BITS, K_BITS  # noqa: F401  (the challenge width and the statistical hiding margin)
 
-E_BITS = 128                     # challenge width
-K_BITS = 128                     # statistical hiding margin
 ROUNDS = 128                     # rounds of the parameter proof
 TAG = b"mxpaillier/range-proof/v1"
 PTAG = b"mxpaillier/range-parameters/v1"
@@ -92,17 +91,10 @@ def _rows_of(values: Sequence[int], words: int) -> Tuple[np.ndarray, List[bool]]
 def shape(n: int, nh: int, bits: int) -> dict:
     """Bit lengths and row widths of a proof (tools/range_model.py: shape).  ValueError — the refusal every entry point
     makes before any engine call — unless 1 <= bits and bits + E + K + 2 <= bits(N) - 1."""
-    n, nh, bits = int(n), int(nh), int(bits)
+    n = int(n)
     if n < 3 or n % 2 == 0:
         raise ValueError("N must be odd")
-    nb, hb = n.bit_length(), nh.bit_length()
-    if bits < 1 or bits + E_BITS + K_BITS + 2 > nb - 1:
-        raise ValueError(f"a claimed length of 1 .. bits(N) - 259 = {nb - 259} bits expected (l + E + K + 2 <= bits(N) - 1)")
-    out = dict(alpha_bits=bits + E_BITS + K_BITS, mu_bits=hb + K_BITS, gamma_bits=hb + E_BITS + 2 * K_BITS, rho_bits=nb + 64)
-    out.update(z1_bits=out["alpha_bits"] + 1, z3_bits=out["gamma_bits"] + 1)
-    out.update(z1_words=(out["z1_bits"] + 31) // 32, z3_words=(out["z3_bits"] + 31) // 32, limbs_n=_limbs.limbs_for(n),
-               limbs2=_limbs.limbs_for(n * n), limbs_h=_limbs.limbs_for(nh))
-    return out
+    return _flows.range_shape(n, nh, bits)
 
 
 class RangeParameters:

@@ -50,6 +50,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import limbs as _limbs
+from .range_proof import _int_bytes, _lp, _rows_of
 
 E_BITS = 128                     # challenge width
 K_BITS = 128                     # statistical hiding margin
@@ -58,14 +59,6 @@ TAG = b"mxpaillier/threshold-dleq/v1"
 
 _NOT_ONE = ("Combined decryption minus one is not divisible by N. This might be caused by the "
             "fact that the ciphertext that is being decrypted, differs between the parties.")
-
-
-def _lp(data: bytes) -> bytes:
-    return len(data).to_bytes(4, "big") + data
-
-
-def _int_bytes(x: int) -> bytes:
-    return int(x).to_bytes(max(1, (int(x).bit_length() + 7) // 8), "big")
 
 
 def split_shape(n_bits: int, z_bits: int) -> Tuple[int, int]:
@@ -107,13 +100,6 @@ def _cat(parts):
     import torch
 
     return torch.cat(parts)
-
-
-def _rows_of(values: Sequence[int], words: int) -> Tuple[np.ndarray, List[bool]]:
-    """ints -> uint32 rows; a value that is negative or does not fit the row becomes a zero row and False."""
-    vals = [int(v) for v in values]
-    fits = [0 <= v < 1 << (32 * words) for v in vals]
-    return _limbs.pack([v if f else 0 for v, f in zip(vals, fits)], words).reshape(len(vals), words), fits
 
 
 class DecryptionProofs:

@@ -1,34 +1,27 @@
-"""A Python-int double of the engine methods membership.py drives — the new ``member_challenges_t`` / ``member_prove_t`` /
-``member_verify_t`` and the existing entry points they are composed with — on numpy rows.  ``member_prove_t`` and
-``member_verify_t`` are COMPOSED here the way the engine composes them (the draws for every slot, the real slot masked
-and split by the three challenge modes, the branch rows c^-1 (1 + s_j N) from one inverse per ciphertext, N-th powers of
-the count k wide rows joined to ONE multi-exponentiation of 128-bit weights, the k commitments hashed as one row set,
-the real response placed by a slot mask), so widths, layouts and the draw order are exercised; every step is Python
-ints and hashlib.  The three challenge modes are Python ints.  It extends the double of the range proofs.  Lives in
-tests/ only; the product never imports it."""
+"""A Python-int double of the engine PRIMITIVES membership.py drives — ``member_challenges_t`` (its three modes) and
+``modinv_t`` — on CPU ``int32`` tensors; every step is Python ints.  ``member_prove_t`` and ``member_verify_t`` are NOT
+written again here: the double runs the shipped composition it inherits (``ProofFlows``: the draws for every slot, the
+real slot masked and split by the three challenge modes, the branch rows c^-1 (1 + s_j N) from one inverse per
+ciphertext, N-th powers of the count k wide rows joined to ONE multi-exponentiation of 128-bit weights, the k commitments
+hashed as one row set, the real response placed by a slot mask) over these primitives, so widths, layouts, the draw order
+and the screening are the engine's own.  It extends the double of the range proofs.  Lives in tests/ only; the product
+never imports it."""
 
 from __future__ import annotations
 
-import numpy as np
-
-from proof_engine import _rows
-from range_engine import RangeEngine, _wide
-
-from protocols.distributed_keygen_amd import limbs
-from protocols.distributed_keygen_amd.engine import Engine
+from proof_engine import _flags_t, _ints, _rows_t
+from range_engine import RangeEngine
 
 M128 = (1 << 128) - 1
 
 
 class MemberEngine(RangeEngine):
-    member_shape = staticmethod(Engine.member_shape)
-
     # ---- existing entry points, in ints
     def modinv_t(self, x_t, mod):
         self.calls.append(("modinv", len(x_t)))
-        return _rows([pow(v, -1, mod) for v in limbs.unpack(x_t)], x_t.shape[1])          # (ValueError for a non-unit, as the engine)
+        return _rows_t([pow(v, -1, mod) for v in _ints(x_t)], x_t.shape[1])          # (ValueError for a non-unit, as the engine)
 
-    # ---- the new entry points
+    # ---- the primitive of the membership proofs
     def member_challenges_t(self, e_t, sim_t, index_t, mode, out_t=None):
         if mode not in (0, 1, 2):
             raise ValueError("mode 0 (mask), 1 (split) or 2 (sum) expected")
@@ -38,96 +31,33 @@ class MemberEngine(RangeEngine):
             raise ValueError("rows of 2 .. 16 slots of four words expected")
         if mode != 0 and tuple(e_t.shape) != (count, 4):
             raise ValueError("one challenge row per row of slots expected")
-        slots = limbs.unpack(np.ascontiguousarray(sim_t).reshape(count * k, 4))
+        slots = _ints(sim_t.reshape(count * k, 4))
         self.calls.append(("member_challenges", mode, count, k))
         if mode == 2:
-            es = limbs.unpack(e_t)
-            return np.array([int(sum(slots[r * k : (r + 1) * k]) & M128 != es[r]) for r in range(count)], dtype=np.uint8)
+            es = _ints(e_t)
+            return _flags_t(sum(slots[r * k : (r + 1) * k]) & M128 != es[r] for r in range(count))
         if tuple(index_t.shape) != (count,):
             raise ValueError("an index [count] expected")
         index = [int(i) for i in index_t]
         if any(not 0 <= i < k for i in index):
             raise ValueError("index out of range")
+        es = _ints(e_t) if mode == 1 else []
         out = []
         for r in range(count):
             row = [0 if j == index[r] else slots[r * k + j] for j in range(k)]
             if mode == 1:
-                row[index[r]] = (limbs.unpack(e_t[r : r + 1])[0] - sum(row)) & M128
+                row[index[r]] = (es[r] - sum(row)) & M128
             out.extend(row)
-        return _rows(out, 4).reshape(count, 4 * k)
+        return _rows_t(out, 4).reshape(count, 4 * k)
 
-    def _member_values(self, n, values):
-        values = [int(s) for s in values]
-        sh = self.member_shape(n, len(values))
-        if n < 3 or n % 2 == 0 or len(set(values)) != len(values) or any(not 0 <= s < n for s in values):
-            raise ValueError("an odd N and distinct values in [0, N) expected")
-        return sh, values
-
-    def _member_branches_t(self, rows_t, factors, n):
-        k, count = len(factors), rows_t.shape[0]
-        fac_t = self._one_plus_mn_t(_rows(factors, limbs.limbs_for(n)), n)
-        return self.mulmod_t(np.repeat(rows_t, k, axis=0), np.tile(fac_t, (count, 1)), n * n)
-
-    def _member_challenge_t(self, ctx, cts_t, a_t):
-        return np.ascontiguousarray(self.sha256_rows_t(ctx, [cts_t, a_t])[:, 4:8])
-
-    def member_prove_t(self, cts_t, index_t, randomness_t, n, values, ctx, rng=None, draws=None):
-        sh, values = self._member_values(n, values)
-        k, ln, limbs2 = sh["k"], sh["limbs_n"], sh["limbs2"]
-        count = cts_t.shape[0]
-        if cts_t.shape[1] != limbs2 or randomness_t.shape != (count, ln):
-            raise ValueError("rows of the wrong shape")
-        if (rng is None) == (draws is None):
-            raise ValueError("exactly one of rng and draws expected")
-        if draws is None:
-            draws = (rng.rows_t(self, count * k, sh["draw_bits"], limbs2), rng.rows_t(self, count * k, 128))
-        zt_t, et_t = draws
-        if zt_t.shape != (count * k, limbs2) or et_t.shape != (count * k, 4):
-            raise ValueError("k draws of each kind per ciphertext expected")
-        self.calls.append(("member_prove", count, k))
-        n2 = n * n
-        sim_t = self.member_challenges_t(None, et_t.reshape(count, 4 * k), index_t, 0)
-        ubar_t = self._member_branches_t(self.modinv_t(cts_t, n2), values, n)
-        own = np.arange(count * k, dtype=np.int32).reshape(-1, 1)
-        a_t = self.mulmod_t(self.powmod_nsquare_t(zt_t, n, n), self.multiexp_nsquare_rows_t(ubar_t, own, sim_t.reshape(count * k, 4), 1, 128, n), n2)
-        a_t = a_t.reshape(count, k * limbs2)
-        e_t = self.member_challenges_t(self._member_challenge_t(ctx, cts_t, a_t), sim_t, index_t, 1)
-        real = (np.arange(k).reshape(1, k) == index_t.astype(np.int64).reshape(-1, 1)).reshape(count, k, 1)
-
-        def own_slot(rows_t):
-            return np.where(real, rows_t, 0).sum(axis=1).astype(np.uint32)
-
-        zs_t = self._reduce_wide_t(zt_t, n).reshape(count, k, ln)
-        zi_t = self._own_pair_t(own_slot(zs_t), randomness_t, own_slot(e_t.reshape(count, k, 4)), n)
-        z_t = np.where(real, zi_t.reshape(count, 1, ln), zs_t).astype(np.uint32).reshape(count, k * ln)
-        return a_t, e_t, z_t
+    # ---- the shipped compositions, recorded
+    def member_prove_t(self, cts_t, index_t, randomness_t, n, values, *args, **kwargs):
+        return self._proved(("member_prove", cts_t.shape[0], len(values)), super().member_prove_t,
+                            cts_t, index_t, randomness_t, n, values, *args, **kwargs)
 
     def member_verify_t(self, cts_t, a_t, e_t, z_t, n, values, ctx):
-        sh, values = self._member_values(n, values)
-        k, ln, limbs2 = sh["k"], sh["limbs_n"], sh["limbs2"]
-        count = cts_t.shape[0]
-        if any(r_t.shape != (count, w) for r_t, w in ((cts_t, limbs2), (a_t, k * limbs2), (e_t, 4 * k), (z_t, k * ln))):
-            raise ValueError("rows of the wrong shape")
-        self.calls.append(("member_verify", count, k))
-        n2 = n * n
-
-        def below(rows_t, words, bound):
-            return np.array([v < bound for v in limbs.unpack(np.ascontiguousarray(rows_t).reshape(-1, words))], dtype=bool).reshape(count, -1).all(axis=1)
-
-        ok = below(cts_t, limbs2, n2) & below(a_t, limbs2, n2) & below(z_t, ln, n)
-        ok &= (a_t.reshape(count, k, limbs2) != 0).any(axis=2).all(axis=1) & (z_t.reshape(count, k, ln) != 0).any(axis=2).all(axis=1)
-
-        def harmless(rows_t, slots, value):
-            fill = _rows([value], rows_t.shape[1] // slots).reshape(1, 1, -1)
-            return np.where(ok.reshape(-1, 1, 1), rows_t.reshape(count, slots, -1), fill).astype(np.uint32).reshape(count, -1)
-
-        cts_t, a_t, z_t, e_t = harmless(cts_t, 1, 1), harmless(a_t, k, 1), harmless(z_t, k, 1), harmless(e_t, k, 0)
-        split_ok = self.member_challenges_t(self._member_challenge_t(ctx, cts_t, a_t), e_t, None, 2) == 0
-        u_t = self._member_branches_t(cts_t, [(n - s) % n for s in values], n)
-        left_t = self.powmod_nsquare_t(_wide(z_t.reshape(count * k, ln), limbs2), n, n)
-        right_t = self.multiexp_nsquare_rows_t(np.concatenate([a_t.reshape(count * k, limbs2), u_t]), self._own_pair_index(count * k),
-                                               self._one_and(e_t.reshape(count * k, 4)), 2, 128, n)
-        return ok & split_ok & (left_t == right_t).reshape(count, k * limbs2).all(axis=1)
+        self.calls.append(("member_verify", cts_t.shape[0], len(values)))
+        return super().member_verify_t(cts_t, a_t, e_t, z_t, n, values, ctx)
 
 
 def forgeries(n, values, label, c, seed=3):

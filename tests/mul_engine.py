@@ -1,28 +1,24 @@
-"""A Python-int double of the engine methods multiplication.py and secure_product.py drive — the new
-``response_mod_rows_t`` / ``mul_prove_t`` / ``mul_verify_t`` and the existing entry points they are composed with — on
-numpy rows.  ``mul_prove_t`` and ``mul_verify_t`` are COMPOSED here the way the engine composes them (the wide draws cut
-and reduced, c_b^a and c_b^x as ONE multi-exponentiation over the count inputs c_b, u^N, v^N and gamma^N as ONE launch
-on 3 count rows, five row sets hashed, the response modulo N with its quotient, the quotient as the exponent of
-c_b mod N), so widths, layouts and the draw order are exercised; every step is Python ints and hashlib.  The response
-modulo N runs the model's STEP-WISE form (tools/mul_model.py: response_mod_steps — the kernel word for word) and checks
-it against divmod on every row.  It extends the double of the membership proofs.  Lives in tests/ only; the product never
-imports it."""
+"""A Python-int double of the engine PRIMITIVE multiplication.py and secure_product.py add — ``response_mod_rows_t`` — on
+CPU ``int32`` tensors.  ``mul_prove_t`` and ``mul_verify_t`` are NOT written again here: the double runs the shipped
+composition it inherits (``ProofFlows``: the wide draws cut and reduced, c_b^a and c_b^x as ONE multi-exponentiation over
+the count inputs c_b, u^N, v^N and gamma^N as ONE launch on 3 count rows, five row sets hashed, the response modulo N
+with its quotient, the quotient as the exponent of c_b mod N) over the primitives, so widths, layouts, the draw order and
+the screening are the engine's own.  The response modulo N runs the model's STEP-WISE form (tools/mul_model.py:
+response_mod_steps — the kernel word for word) and checks it against divmod on every row; its refusals and constants are
+the engine's (``Engine.response_mod_constants``).  It extends the double of the membership proofs.  Lives in tests/ only;
+the product never imports it."""
 
 from __future__ import annotations
 
-import numpy as np
-
 import mul_model as mulm
 from member_engine import MemberEngine
-from proof_engine import _rows
-from range_engine import _wide
+from proof_engine import _flags_t, _ints, _rows_t
 
 from protocols.distributed_keygen_amd import limbs
 from protocols.distributed_keygen_amd.engine import Engine
 
 
 class MulEngine(MemberEngine):
-    mul_shape = staticmethod(Engine.mul_shape)
     response_mod_constants = staticmethod(Engine.response_mod_constants)
 
     def response_mod_rows_t(self, rho_t, e_t, x_t, mod, out_t=None):
@@ -37,84 +33,21 @@ class MulEngine(MemberEngine):
         assert self.response_mod_constants(mod, wn) == mulm.response_mod_constants(mod, wn)
         self.calls.append(("response_mod", count, wn, ew))
         ws, ts, status = [], [], []
-        for rho, e, x in zip(limbs.unpack(rho_t), limbs.unpack(np.ascontiguousarray(e_t)), limbs.unpack(x_t)):
+        for rho, e, x in zip(_ints(rho_t), _ints(e_t), _ints(x_t)):
             w, t, st = mulm.response_mod_steps(rho, e, x, mod, wn, ew)
             q, r = divmod(rho + e * x, mod)
             assert (w, t, st) == (r, q & ((1 << (32 * ew)) - 1), int(q >> (32 * ew) != 0))
             ws.append(w), ts.append(t), status.append(st)
-        return _rows(ws, wn), _rows(ts, ew), np.array(status, dtype=np.uint8)
+        self.statuses.append(_flags_t(status))
+        return _rows_t(ws, wn), _rows_t(ts, ew), self.statuses[-1]
 
-    def _mul_challenge_t(self, ctx, ca_t, cb_t, d_t, a_t, b_t):
-        return np.ascontiguousarray(self.sha256_rows_t(ctx, [ca_t, cb_t, d_t, a_t, b_t])[:, 4:8])
+    # ---- the shipped compositions, recorded
+    def mul_prove_t(self, ca_t, *args, **kwargs):
+        return self._proved(("mul_prove", ca_t.shape[0]), super().mul_prove_t, ca_t, *args, **kwargs)
 
-    def _reduce_n2_t(self, rows_t, n):
-        ln = limbs.limbs_for(n)
-        count = rows_t.shape[0]
-        lo_t = np.ascontiguousarray(rows_t[:, :ln])
-        hi_t = _wide(rows_t[:, ln:], ln)
-        return self.response_mod_rows_t(lo_t, np.tile(_rows([(1 << (32 * ln)) % n], ln), (count, 1)), hi_t, n)[0]
-
-    def mul_prove_t(self, ca_t, cb_t, a_t, ra_t, gamma_t, n, ctx, rng=None, draws=None):
-        sh = self.mul_shape(n)
-        ln, limbs2 = sh["limbs_n"], sh["limbs2"]
-        count = ca_t.shape[0]
-        if n < 3 or n % 2 == 0 or sh["draw_bits"] > (n * n).bit_length() - 1:
-            raise ValueError("an odd N with room for the wide draws expected")
-        if any(t.shape != (count, w) for t, w in ((ca_t, limbs2), (cb_t, limbs2), (a_t, ln), (ra_t, ln), (gamma_t, ln))):
-            raise ValueError("rows of the wrong shape")
-        if (rng is None) == (draws is None):
-            raise ValueError("exactly one of rng and draws expected")
-        if draws is None:
-            draws = (rng.rows_t(self, count, sh["draw_bits"], limbs2), rng.rows_t(self, 2 * count, sh["draw_bits"], limbs2))
-        xd_t, uv_t = draws
-        if xd_t.shape != (count, limbs2) or uv_t.shape != (2 * count, limbs2):
-            raise ValueError("one x draw and two further draws per statement expected")
-        if any(a >= n for a in limbs.unpack(a_t)):
-            raise ValueError("a must be below n")
-        self.calls.append(("mul_prove", count))
-        n2 = n * n
-        x_t = self._reduce_wide_t(xd_t, n)
-        cbn_t = self._reduce_n2_t(cb_t, n)
-        rn_t = self.powmod_nsquare_t(np.concatenate([uv_t, _wide(gamma_t, limbs2)]), n, n)
-        index_t = np.tile(np.arange(count, dtype=np.int32), 2).reshape(-1, 1)
-        pw_t = self.multiexp_nsquare_rows_t(cb_t, index_t, np.concatenate([a_t, x_t]), 1, 32 * ln, n)
-        d_t = self.mulmod_t(pw_t[:count], rn_t[2 * count:], n2)
-        bb_t = self.mulmod_t(pw_t[count:], rn_t[count : 2 * count], n2)
-        aa_t = self.mulmod_t(rn_t[:count], self._one_plus_mn_t(x_t, n), n2)
-        e_t = self._mul_challenge_t(ctx, ca_t, cb_t, d_t, aa_t, bb_t)
-        w_t, t_t, status = self.response_mod_rows_t(x_t, e_t, a_t, n)
-        assert not status.any()
-        uvn_t = self._reduce_wide_t(uv_t, n)
-        z_t = self._own_pair_t(uvn_t[:count], ra_t, e_t, n)
-        y_t = self._own_pair_t(self._own_pair_t(uvn_t[count:], cbn_t, t_t, n), gamma_t, e_t, n)
-        return d_t, aa_t, bb_t, w_t, z_t, y_t
-
-    def mul_verify_t(self, ca_t, cb_t, d_t, a_t, b_t, w_t, z_t, y_t, n, ctx):
-        sh = self.mul_shape(n)
-        ln, limbs2 = sh["limbs_n"], sh["limbs2"]
-        count = ca_t.shape[0]
-        wide, narrow = (ca_t, cb_t, d_t, a_t, b_t), (w_t, z_t, y_t)
-        if any(t.shape != (count, limbs2) for t in wide) or any(t.shape != (count, ln) for t in narrow):
-            raise ValueError("rows of the wrong shape")
-        self.calls.append(("mul_verify", count))
-        n2 = n * n
-        ok = np.array([w < n for w in limbs.unpack(w_t)], dtype=bool)
-        for r_t, bound in [(t, n2) for t in wide] + [(z_t, n), (y_t, n)]:
-            ok &= np.array([0 < v < bound for v in limbs.unpack(r_t)], dtype=bool)
-
-        def harmless(rows_t, value):
-            return np.where(ok[:, None], rows_t, _rows([value], rows_t.shape[1])).astype(np.uint32)
-
-        ca_t, cb_t, d_t, a_t, b_t, z_t, y_t = (harmless(t, 1) for t in (ca_t, cb_t, d_t, a_t, b_t, z_t, y_t))
-        w_t = harmless(w_t, 0)
-        e_t = self._mul_challenge_t(ctx, ca_t, cb_t, d_t, a_t, b_t)
-        rn_t = self.powmod_nsquare_t(_wide(np.concatenate([z_t, y_t]), limbs2), n, n)
-        own = np.arange(count, dtype=np.int32).reshape(-1, 1)
-        left1_t = self.mulmod_t(rn_t[:count], self._one_plus_mn_t(w_t, n), n2)
-        left2_t = self.mulmod_t(self.multiexp_nsquare_rows_t(cb_t, own, w_t, 1, 32 * ln, n), rn_t[count:], n2)
-        right_t = self.multiexp_nsquare_rows_t(np.concatenate([a_t, b_t, ca_t, d_t]), self._own_pair_index(2 * count),
-                                               self._one_and(np.concatenate([e_t, e_t])), 2, 128, n)
-        return ok & (left1_t == right_t[:count]).all(axis=1) & (left2_t == right_t[count:]).all(axis=1)
+    def mul_verify_t(self, ca_t, *args, **kwargs):
+        self.calls.append(("mul_verify", ca_t.shape[0]))
+        return super().mul_verify_t(ca_t, *args, **kwargs)
 
 
 def equations_hold(n, label, ca, cb, d, proof):

@@ -69,7 +69,7 @@ def test_proofs_equal_the_model_bit_for_bit_and_verify(key_length, name, count):
     assert membership.shape(n, len(values)) == mm.shape(n, len(values)) == eng.member_shape(n, len(values))
     assert membership.verify_batch(n, values, cts, proofs, mc.LABEL, engine=eng) == [True] * count
     again = membership.MembershipProofs.from_ints(*proofs.to_ints(), n, len(values))
-    assert again.unfit == [False] * count and all((x == y).all() for x, y in zip(again.rows(), proofs.rows()))
+    assert again.unfit == [False] * count and all((x == eng.to_host(y)).all() for x, y in zip(again.rows(), proofs.rows()))
     assert membership.verify_batch(n, values, cts, again, mc.LABEL, engine=eng) == [True] * count
     # the composition: two draws, ONE inverse per ciphertext, count k wide N-th powers, one multi-exponentiation per side
     k = len(values)
@@ -89,7 +89,7 @@ def test_the_double_takes_the_smallest_key_and_equals_the_model():
         sh = eng.member_shape(N128, k)
         index, msgs, rands, cts = mc.statements(N128, values, count)
         ctx = mm.context(N128, values, mc.LABEL)
-        rows = eng.member_prove_t(eng.to_device(limbs.pack(cts, sh["limbs2"]).reshape(count, -1)), np.array(index, dtype=np.uint32),
+        rows = eng.member_prove_t(eng.to_device(limbs.pack(cts, sh["limbs2"]).reshape(count, -1)), eng.to_device(np.array(index, dtype=np.uint32)),
                                   eng.to_device(limbs.pack(rands, sh["limbs_n"]).reshape(count, -1)), N128, values, ctx,
                                   rng=DeviceRng(key=mc.KEY, first_call=7))
         assert membership.MembershipProofs(*rows, k).to_ints() == mc.model_proofs(N128, values, mc.LABEL, index, rands, 7)
@@ -137,10 +137,10 @@ def test_the_challenge_modes(k):
     count = len(e)
     e_t = eng.to_device(limbs.pack(e, 4).reshape(count, 4))
     sim_t = eng.to_device(limbs.pack([v for row in sims for v in row], 4).reshape(count, 4 * k))
-    index_t = np.array(index, dtype=np.uint32)
+    index_t = eng.to_device(np.array(index, dtype=np.uint32))
 
     def slots_of(rows_t):
-        flat = limbs.unpack(np.ascontiguousarray(rows_t).reshape(count * k, 4))
+        flat = limbs.unpack(eng.to_host(rows_t).reshape(count * k, 4))
         return [flat[r * k : (r + 1) * k] for r in range(count)]
 
     masked = slots_of(eng.member_challenges_t(None, sim_t, index_t, 0))
@@ -155,9 +155,9 @@ def test_the_challenge_modes(k):
     split_t = eng.member_challenges_t(e_t, sim_t, index_t, 1)
     assert list(eng.member_challenges_t(e_t, split_t, None, 2)) == [0] * count == mm.challenges(2, e, split, index)
     for word in range(4):
-        spoiled = np.array(split_t, copy=True)
+        spoiled = eng.to_host(split_t).copy()
         spoiled[3, 4 * (k - 1) + word] ^= 1 << 31
-        assert list(eng.member_challenges_t(e_t, spoiled, None, 2)) == [0, 0, 0, 1] + [0] * (count - 4)
+        assert list(eng.member_challenges_t(e_t, eng.to_device(spoiled), None, 2)) == [0, 0, 0, 1] + [0] * (count - 4)
     for bad in (lambda: eng.member_challenges_t(e_t, sim_t, index_t, 3), lambda: eng.member_challenges_t(e_t, sim_t[:, :4], index_t, 1),
                 lambda: eng.member_challenges_t(e_t, sim_t, index_t + k, 1), lambda: eng.member_challenges_t(e_t[:1], sim_t, index_t, 2)):
         with pytest.raises(ValueError):

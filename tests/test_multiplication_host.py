@@ -87,7 +87,7 @@ def test_the_quotient_of_in_range_rows_fits_the_challenge_width():
 
 def test_the_engines_double_refuses_what_the_engine_refuses():
     eng = MulEngine()
-    rows = np.zeros((2, 4), dtype=np.uint32)
+    rows = eng.to_device(np.zeros((2, 4), dtype=np.uint32))
     for bad in (lambda: eng.response_mod_rows_t(rows, rows, rows[:, :3], N128), lambda: eng.response_mod_rows_t(rows, rows[:1], rows, N128),
                 lambda: eng.response_mod_rows_t(rows, rows, rows, N128 >> 40), lambda: eng.response_mod_rows_t(rows, rows, rows, N128 << 8),
                 lambda: eng.response_mod_rows_t(rows, rows, rows, N128, out_t=rows), lambda: eng.response_mod_constants(1 << 128, 4),
@@ -135,7 +135,7 @@ def test_proofs_equal_the_model_bit_for_bit_and_verify(key_length, count):
     assert multiplication.shape(n) == mulm.shape(n) == eng.mul_shape(n)
     assert multiplication.verify_batch(n, ca, cb, d, proofs, mc.LABEL, engine=eng) == [True] * count
     again = MultiplicationProofs.from_ints(*proofs.to_ints(), n)
-    assert again.unfit == [False] * count and all((x == y).all() for x, y in zip(again.rows(), proofs.rows()))
+    assert again.unfit == [False] * count and all((x == eng.to_host(y)).all() for x, y in zip(again.rows(), proofs.rows()))
     assert multiplication.verify_batch(n, ca, cb, d, again, mc.LABEL, engine=eng) == [True] * count
     # the composition: c_b^a and c_b^x are ONE multi-exponentiation over the count inputs; u^N, v^N, gamma^N ONE launch on
     # 3 count rows; the prover's response modulo N twice (the reduction of c_b, then (w, t))
@@ -164,7 +164,7 @@ def test_the_double_takes_the_smallest_key_and_equals_the_model():
     rows = eng.mul_prove_t(up(ca, sh["limbs2"]), up(cb, sh["limbs2"]), up(a, sh["limbs_n"]), up(ra, sh["limbs_n"]), up(gamma, sh["limbs_n"]),
                            N128, ctx, rng=DeviceRng(key=mc.KEY, first_call=7))
     want_d, want = mc.model_proofs(N128, mc.LABEL, a, ra, gamma, ca, cb, 7)
-    assert limbs.unpack(rows[0]) == want_d and MultiplicationProofs(*rows[1:]).to_ints() == want
+    assert limbs.unpack(eng.to_host(rows[0])) == want_d and MultiplicationProofs(*rows[1:]).to_ints() == want
     assert [mc.decrypt(128, d) for d in want_d] == [x * y % N128 for x, y in zip(a, b)]
     assert list(eng.mul_verify_t(up(ca, sh["limbs2"]), up(cb, sh["limbs2"]), *rows, N128, ctx)) == [True] * count
 

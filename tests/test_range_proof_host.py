@@ -121,7 +121,7 @@ def test_the_bounds_of_z1_and_z3_are_exact():
             spoiled = range_proof.RangeProofs.from_ints(*cols, N1K, params, BITS)
             assert spoiled.unfit == [False, False]
             c_t = eng.to_device(limbs.pack(cts, sh["limbs2"]))
-            assert list(eng.range_bounds_t(c_t, *spoiled.rows(), N1K, params.nh, BITS)) == [True, expect]
+            assert list(eng.range_bounds_t(c_t, *(eng.to_device(r) for r in spoiled.rows()), N1K, params.nh, BITS)) == [True, expect]
             assert rm.in_range(N1K, mpar, BITS, cts[1], [col[1] for col in cols]) is expect
             assert range_proof.verify_batch(N1K, params, BITS, cts, spoiled, rc.LABEL, engine=eng) == [True, False]
 
@@ -146,8 +146,14 @@ def test_the_slack_and_what_lies_beyond_it():
     c = rm.encrypt(N1K, m, r)
     proof = rm.prove(N1K, mpar, BITS, rc.LABEL, m, r, alpha, mu, gamma, rho)
     assert proof[3] >= 1 << sh["z1_bits"] and not rm.verify(N1K, mpar, BITS, rc.LABEL, c, proof)
-    got = range_proof.prove_batch(N1K, params, BITS, [m], [r], rc.LABEL, rng=DeviceRng(key=rc.KEY, first_call=3), engine=eng)
-    assert range_proof.verify_batch(N1K, params, BITS, [c], got, rc.LABEL, engine=eng) == [False]
+    # this z1 does not even fit its row: the response kernel says so in its status, and the double lets no prover pass with one set
+    assert proof[3] >> (32 * sh["z1_words"])
+    with pytest.raises(AssertionError, match="overflowed"):
+        range_proof.prove_batch(N1K, params, BITS, [m], [r], rc.LABEL, rng=DeviceRng(key=rc.KEY, first_call=3), engine=eng)
+    # what the engine returns then — the low words of z1 beside the rest of the proof — is refused like any other
+    cut = proof[:3] + (proof[3] & ((1 << (32 * sh["z1_words"])) - 1),) + proof[4:]
+    got = range_proof.RangeProofs.from_ints(*([v] for v in cut), N1K, params, BITS)
+    assert got.unfit == [False] and range_proof.verify_batch(N1K, params, BITS, [c], got, rc.LABEL, engine=eng) == [False]
 
 
 def test_the_extreme_messages_prove():
