@@ -1,7 +1,9 @@
-"""Argument coercion and the operand checks that the engine (engine.py) and the proof compositions (proof_flows.py) share.
-Imports neither torch nor the native library."""
+"""Argument coercion and the operand checks that the engine (engine.py), the proof compositions (proof_flows.py) and the
+private-key compositions (key_flows.py) share.  Imports neither torch nor the native library."""
 
 from __future__ import annotations
+
+from typing import Optional, Tuple
 
 from . import limbs as _limbs
 
@@ -50,3 +52,25 @@ def _check_rows_n2(n: int, limbs2: int) -> None:
 def _is_device_rows(x) -> bool:
     """Rows that are already a device tensor (not a numpy array, not a sequence of ints)."""
     return hasattr(x, "data_ptr") and hasattr(x, "device")
+
+
+def _nsquare(n: int) -> Tuple[int, int]:
+    """(N^2, limbs of its rows) for a valid Paillier modulus N."""
+    _check_modulus(n)
+    n2 = n * n
+    return n2, _limbs.limbs_for(n2)
+
+
+class RowChecks:
+    """The row check both mix-ins (proof_flows.ProofFlows, key_flows.PrivateKeyFlows) and the engine inherit; it reads
+    ``self.torch`` and ``self.device``."""
+
+    def _word_rows(self, rows_t, what: str, width: Optional[int] = None) -> Tuple[int, int]:
+        if not _is_device_rows(rows_t) or rows_t.dim() != 2 or rows_t.dtype != self.torch.int32 or not rows_t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous int32 device rows [count, words]")
+        if rows_t.device != self.device:
+            raise ValueError(f"{what} live on {rows_t.device}, the operation runs on {self.device}")
+        rows, words = rows_t.shape
+        if words < 1 or (width is not None and words != width):
+            raise ValueError(f"{what} must have {'at least one word' if width is None else f'{width} words'}")
+        return rows, words

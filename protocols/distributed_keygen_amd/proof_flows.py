@@ -14,7 +14,7 @@ from __future__ import annotations
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 from . import _lib, limbs as _limbs
-from ._checks import _check_modulus, _check_rows_n2, _int_args, _is_device_rows
+from ._checks import RowChecks, _check_modulus, _check_rows_n2, _int_args
 
 E_BITS = 128                     # challenge width
 K_BITS = 128                     # statistical hiding margin
@@ -50,7 +50,7 @@ def mul_shape(n: int) -> Dict[str, int]:
                 limbs2=_limbs.limbs_for(n * n))
 
 
-class ProofFlows:
+class ProofFlows(RowChecks):
     """The prove and verify compositions of the four proofs and their helpers; see the module docstring for what a
     class that inherits them has to provide."""
 
@@ -59,16 +59,6 @@ class ProofFlows:
     mul_shape = staticmethod(mul_shape)
 
     # ------------------------------------------------------------------ what the four proofs share
-    def _word_rows(self, rows_t, what: str, width: Optional[int] = None) -> Tuple[int, int]:
-        if not _is_device_rows(rows_t) or rows_t.dim() != 2 or rows_t.dtype != self.torch.int32 or not rows_t.is_contiguous():
-            raise ValueError(f"{what} must be contiguous int32 device rows [count, words]")
-        if rows_t.device != self.device:
-            raise ValueError(f"{what} live on {rows_t.device}, the operation runs on {self.device}")
-        rows, words = rows_t.shape
-        if words < 1 or (width is not None and words != width):
-            raise ValueError(f"{what} must have {'at least one word' if width is None else f'{width} words'}")
-        return rows, words
-
     def _expect_rows(self, expected, count: int, per: str = "ciphertext") -> None:
         """ValueError unless every (rows, what, words) of `expected` holds `count` rows of `words` words."""
         for rows_t, what, words in expected:

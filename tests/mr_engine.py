@@ -1,83 +1,95 @@
-"""A Python-int double of the engine methods primes.py and the key generation of private_key.py drive — ``mr_split_t`` /
-``miller_rabin_t`` / ``miller_rabin_base2_t`` / ``probable_prime_t`` / ``prime_search_t`` on numpy rows — computed by the
-model of the kernels (tools/mr_model.py) with the random rows of a ``FakeRng`` (or anything else with ``rows_t``).  It
-extends the encryption's double, so a key generated over it encrypts and decrypts.  Lives in tests/ only; the product
-never imports it."""
+"""A Python-int double of the engine PRIMITIVES primes.py and the key generation of private_key.py drive —
+``chacha20_rows_t`` / ``sieve_t`` / ``mr_split_t`` / ``miller_rabin_t`` / ``miller_rabin_base2_t`` / ``generator_shares_t``
+— on CPU ``int32`` tensors, each from the model of its kernel (tools/mr_model.py, tools/chacha_model.py), with the random
+rows of a ``FakeRng`` or of a real ``DeviceRng``.  ``probable_prime_t`` and ``prime_search_t`` are NOT written again
+here: they are the shipped compositions of ``PrivateKeyFlows`` — range check, compaction, the one draw per batch, the loop
+of the search — recorded; tools/mr_model.py's pipeline is the oracle the tests compare them with.  It extends the
+encryption's double, so a key generated over it encrypts and decrypts.  Lives in tests/ only; the product never imports
+it."""
 
 from __future__ import annotations
 
+import math
 import sys
 from pathlib import Path
 
 import numpy as np
+import torch
 
-from crt_enc_engine import CrtEncEngine, FakeRng  # noqa: F401
+from crt_enc_engine import CrtEncEngine, FakeRng, _is_pair  # noqa: F401
+from crt_engine import _flags_t, _ints, _rows_t
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
 import chacha_model  # noqa: E402
 import mr_model  # noqa: E402
 
-from protocols.distributed_keygen_amd import limbs, primes  # noqa: E402
+from protocols.distributed_keygen_amd import primes  # noqa: E402
+
+_PRODUCTS = {}
+
+
+def _product(prime_list):
+    key = tuple(prime_list)
+    if key not in _PRODUCTS:
+        _PRODUCTS[key] = math.prod(key)
+    return _PRODUCTS[key]
+
+
+def _drawn_batch(default_batch, count, bits, batch):
+    """The rows per draw of an accepted search, for its record (a search for nothing draws nothing)."""
+    return int(batch) if batch is not None else default_batch(count, bits) if count else 0
 
 
 class MrEngine(CrtEncEngine):
-    @staticmethod
-    def to_device(rows):
-        return np.ascontiguousarray(rows, dtype=np.uint32)
-
-    @staticmethod
-    def to_host(rows_t):
-        return rows_t
-
     def chacha20_rows_t(self, key, nonce, counter0, count, bits, row_words=None):
         """What a real ``DeviceRng`` asks of its engine, from the model of the kernel."""
         words = row_words or (bits + 31) // 32
-        return np.array(chacha_model.rows_words(list(key), list(nonce), counter0, count, bits, words), dtype=np.uint32).reshape(count, words)
+        rows = np.array(chacha_model.rows_words(list(key), list(nonce), counter0, count, bits, words), dtype=np.uint32)
+        return self.to_device(rows.reshape(count, words))
 
-    def _draw(self, rng):
-        return lambda count, bits, row_words: limbs.unpack(rng.rows_t(self, count, bits, row_words))
+    # ---- the primitives of the prime search, in ints
+    def sieve_t(self, cands_t, prime_list, out_t=None):
+        self.calls.append(("sieve", len(cands_t)))
+        product = _product(prime_list)
+        return _flags_t(math.gcd(n, product) != 1 for n in _ints(cands_t))
 
-    def _candidates(self, cands_t, bits, above=3):
-        if cands_t.ndim != 2:
-            raise ValueError("candidates must be rows [S, limbs]")
-        bits = 32 * cands_t.shape[1] if bits is None else int(bits)
-        vals = limbs.unpack(cands_t)
-        if any(n % 2 == 0 or n < above or n.bit_length() > bits for n in vals):
-            raise ValueError(f"candidates must be odd, at least {above} and of at most `bits` bits")
-        return vals, bits
+    def mr_split_t(self, cands_t, bits=None, _checked=False):
+        rows, words, _ = self._mr_candidates(cands_t, bits, checked=_checked)
+        self.calls.append(("mr_split", rows))
+        parts = [mr_model.split(n) for n in _ints(cands_t)]
+        return _rows_t([d for d, _ in parts], words), torch.tensor([s for _, s in parts], dtype=torch.int32)
 
-    def mr_split_t(self, cands_t, bits=None):
-        vals, _ = self._candidates(cands_t, bits)
-        self.calls.append(("mr_split", len(vals)))
-        parts = [mr_model.split(n) for n in vals]
-        return limbs.pack([d for d, _ in parts], cands_t.shape[1]), np.array([s for _, s in parts], dtype=np.int32)
-
-    def miller_rabin_t(self, cands_t, bases_t, group_size, out_t=None, bits=None):
+    def miller_rabin_t(self, cands_t, bases_t, group_size, out_t=None, bits=None, _checked=False):
         if int(group_size) < 1:
             raise ValueError("group_size must be at least 1")
-        vals, _ = self._candidates(cands_t, bits)
-        if tuple(bases_t.shape) != (len(vals) * group_size, cands_t.shape[1]):
+        rows, words, _ = self._mr_candidates(cands_t, bits, checked=_checked)
+        if tuple(bases_t.shape) != (rows * group_size, words):
             raise ValueError("bases_t must hold group_size rows per candidate")
-        self.calls.append(("miller_rabin", len(vals), group_size))
-        bases = limbs.unpack(bases_t)
-        return np.array([mr_model.round_passes(vals[k // group_size], b) for k, b in enumerate(bases)], dtype=np.uint8)
+        self.calls.append(("miller_rabin", rows, group_size))
+        vals = _ints(cands_t)
+        return _flags_t(mr_model.round_passes(vals[k // group_size], b) for k, b in enumerate(_ints(bases_t)))
 
-    def miller_rabin_base2_t(self, cands_t, bits=None, out_t=None):
-        vals, bits = self._candidates(cands_t, bits)
-        self.calls.append(("base2", len(vals)))
-        return np.array([mr_model.base2(n, bits) for n in vals], dtype=np.uint8)
+    def miller_rabin_base2_t(self, cands_t, bits=None, out_t=None, _checked=False):
+        rows, _, bits = self._mr_candidates(cands_t, bits, checked=_checked)
+        self.calls.append(("base2", rows))
+        return _flags_t(mr_model.base2(n, bits) for n in _ints(cands_t))
 
-    def probable_prime_t(self, cands_t, bits, rounds, rng):
-        if int(rounds) < 1:
-            raise ValueError("rounds must be at least 1")
-        vals, bits = self._candidates(cands_t, bits, above=primes.SIEVE_BOUND)
-        self.calls.append(("probable_prime", len(vals), rounds))
-        return np.array(mr_model.probable_prime(vals, bits, int(rounds), self._draw(rng)), dtype=np.uint8)
+    def generator_shares_t(self, mods, group_size, rng=None, draws_t=None, out_t=None):
+        """Device ``(rows, bits)`` moduli only: ONE draw of S * G rows of bits + 64 bits, row c * G + k modulo candidate c."""
+        if not _is_pair(mods) or int(group_size) < 1 or (rng is None) == (draws_t is None):
+            raise ValueError("a device (rows, bits) pair, group_size >= 1 and exactly one of rng and draws_t expected")
+        mods_t, bits = mods
+        total = len(mods_t) * group_size
+        self.calls.append(("generator_shares", len(mods_t), group_size))
+        if total and draws_t is None:
+            draws_t = rng.rows_t(self, total, bits + 64, (bits + 64 + 31) // 32)
+        ms = _ints(mods_t)
+        return _rows_t([d % ms[k // group_size] for k, d in enumerate(_ints(draws_t) if total else [])], mods_t.shape[1])
+
+    # ---- the shipped compositions, recorded
+    def probable_prime_t(self, cands_t, bits, rounds, rng, **kwargs):
+        return self._recorded(("probable_prime", len(cands_t), rounds), super().probable_prime_t, cands_t, bits, rounds, rng, **kwargs)
 
     def prime_search_t(self, count, bits, rng, rounds=64, batch=None):
-        if count < 0 or bits < 16 or rounds < 1:
-            raise ValueError("count >= 0, bits >= 16 and rounds >= 1 expected")
-        batch = primes.default_batch(count, bits) if batch is None else int(batch)
-        self.calls.append(("prime_search", count, bits, batch))
-        found, _ = mr_model.prime_search(count, bits, self._draw(rng), rounds, batch)
-        return limbs.pack(found, limbs.limbs_for_bits(bits))
+        return self._recorded(lambda: ("prime_search", count, bits, _drawn_batch(primes.default_batch, count, bits, batch)),
+                              super().prime_search_t, count, bits, rng, rounds=rounds, batch=batch)

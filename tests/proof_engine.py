@@ -3,8 +3,8 @@
 ``multiexp_nsquare_t`` / ``combine_t`` — on CPU ``int32`` tensors; every step is Python ints and hashlib.  ``dleq_prove_t``
 and ``dleq_verify_t`` are NOT written again here: the double inherits ``ProofFlows`` and runs the shipped composition
 (piece bases by squarings, one multi-exponentiation whose weight block is the exponent rows, fixed-base products piece by
-piece) over these primitives, recording what it is asked.  It extends the safe-prime double, whose numpy entry points take
-the tensors where a proof test reaches them, so ``deal(check=True)`` runs over it.  Lives in tests/ only; the product
+piece) over these primitives, recording what it is asked.  It extends the safe-prime double, which works on
+the same CPU tensors and runs the shipped private-key compositions, so ``deal(check=True)`` runs over it.  Lives in tests/ only; the product
 never imports it."""
 
 from __future__ import annotations
@@ -12,61 +12,18 @@ from __future__ import annotations
 import hashlib
 
 import numpy as np
-import torch
 
+from crt_engine import _flags_t, _host, _ints, _rows, _rows_t  # noqa: F401
 from safe_engine import FakeRng, SafeEngine  # noqa: F401
 
 from protocols.distributed_keygen_amd import limbs
 from protocols.distributed_keygen_amd.proof_flows import ProofFlows
 
 
-def _rows(values, words):
-    return limbs.pack(list(values), words).reshape(len(values), words) if len(values) else np.zeros((0, words), dtype=np.uint32)
-
-
-def _host(rows_t):
-    """Rows, a CPU tensor or numpy already, as contiguous uint32 numpy rows."""
-    return np.ascontiguousarray(np.asarray(rows_t)).view(np.uint32)
-
-
-def _ints(rows_t):
-    return limbs.unpack(_host(rows_t)) if len(rows_t) else []
-
-
-def _rows_t(values, words):
-    return torch.from_numpy(_rows(values, words).view(np.int32))
-
-
-def _flags_t(flags):
-    return torch.tensor([1 if f else 0 for f in flags], dtype=torch.uint8)
-
-
 class ProofEngine(ProofFlows, SafeEngine):
-    torch = torch
-    device = torch.device("cpu")
-
     def __init__(self):
         super().__init__()
         self.statuses = []          # what every response primitive returned, for _proved
-
-    # ---- rows in and out, and the inherited numpy entry points the proof tests reach with tensors
-    @staticmethod
-    def to_device(rows):
-        return torch.from_numpy(np.ascontiguousarray(rows, dtype=np.uint32).view(np.int32))
-
-    to_host = staticmethod(_host)
-
-    def _empty_rows(self, limbs_, rows=0):
-        return torch.empty((rows, limbs_), dtype=torch.int32)
-
-    def chacha20_rows_t(self, *args, **kwargs):
-        return self.to_device(super().chacha20_rows_t(*args, **kwargs))
-
-    def _draw(self, rng):
-        return lambda count, bits, row_words: _ints(rng.rows_t(self, count, bits, row_words))
-
-    def _candidates(self, cands_t, bits, above=3):
-        return super()._candidates(_host(cands_t), bits, above)
 
     def _proved(self, marker, prove, *args, **kwargs):
         """Record `marker`, run the shipped prover and check that no response it computed overflowed its rows."""
@@ -82,12 +39,6 @@ class ProofEngine(ProofFlows, SafeEngine):
         return _rows_t([f & ((1 << (32 * wz)) - 1) for f in full], wz), self.statuses[-1]
 
     # ---- existing entry points, in ints
-    def powmod_nsquare_t(self, bases_t, n, exp, out_t=None):
-        if exp < 0:
-            raise ValueError("negative exponent: invert the base first (paillier_shared_key.py:89-91)")
-        self.calls.append(("powmod_nsquare", len(bases_t)))
-        return _rows_t([pow(b, exp, n * n) for b in _ints(bases_t)], bases_t.shape[1])
-
     def mulmod_t(self, a_t, b_t, mod, out_t=None):
         return _rows_t([x * y % mod for x, y in zip(_ints(a_t), _ints(b_t))], a_t.shape[1])
 

@@ -8,17 +8,9 @@ the double of the decryption proofs.  Lives in tests/ only; the product never im
 
 from __future__ import annotations
 
-import numpy as np
-
 from proof_engine import ProofEngine, _ints, _rows_t
 
 from protocols.distributed_keygen_amd import limbs
-
-
-def _wide(rows_t, words):
-    out = np.zeros((rows_t.shape[0], words), dtype=np.uint32)
-    out[:, : rows_t.shape[1]] = rows_t
-    return out
 
 
 class RangeEngine(ProofEngine):
@@ -67,16 +59,6 @@ class RangeEngine(ProofEngine):
     def response_rows_t(self, rho_t, e_t, x_t, out_t=None):
         self.calls.append(("response_rows", len(rho_t), rho_t.shape[1], e_t.shape[1], x_t.shape[1]))
         return self._response_t([r + e * x for r, e, x in zip(_ints(rho_t), _ints(e_t), _ints(x_t))], rho_t.shape[1])
-
-    def powmod_multi_t(self, bases_t, mods, exps, group_size, out_t=None):
-        """Device pairs only: (modulus rows, bits) and (exponent rows, bits), one group per `group_size` rows."""
-        (mods_t, mod_bits), (exps_t, exp_bits) = mods, exps
-        ms, es = _ints(mods_t), _ints(exps_t)
-        if len(ms) != len(es) or len(bases_t) != len(ms) * group_size:
-            raise ValueError("one modulus and one exponent per group expected")
-        assert all(m.bit_length() <= mod_bits for m in ms) and all(e.bit_length() <= exp_bits for e in es)          # the caller's bounds
-        self.calls.append(("powmod_multi", len(ms), group_size, exp_bits))
-        return _rows_t([pow(b, es[k // group_size], ms[k // group_size]) for k, b in enumerate(_ints(bases_t))], bases_t.shape[1])
 
     # ---- the shipped compositions, recorded, and what the mirror asserted of their operands
     def _one_plus_mn_t(self, m_t, n):

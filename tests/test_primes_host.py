@@ -16,9 +16,10 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 sys.path.insert(0, str(ROOT / "tests"))
 import mr_model as mm  # noqa: E402
+from crt_engine import MARKERS, _ints  # noqa: E402
 from mr_engine import FakeRng, MrEngine  # noqa: E402
 
-from protocols.distributed_keygen_amd import PaillierPrivateKey, primes, synthetic  # noqa: E402
+from protocols.distributed_keygen_amd import DeviceRng, PaillierPrivateKey, limbs, primes, synthetic  # noqa: E402
 
 KNOWN_PRIMES = (3, 5, 7, 65537, 2**61 - 1, 2**64 - 2**32 + 1)
 PSP = 3215031751          # the smallest strong pseudoprime to the bases 2, 3, 5 and 7 at once
@@ -108,7 +109,83 @@ def test_device_decisions_over_the_model_engine():
     vals = [7, 8] + big + [16381 * 16369]
     out = primes.is_probable_prime_batch(vals, rounds=16, rng=FakeRng(3), engine=eng)
     assert out == [True, False, True, True, False, True, False, synthetic.is_probable_prime(big[5], random.Random(2)), False, False]
-    assert eng.calls == [("probable_prime", len(big), 16)]
+    sieved = [n for n in big if not mm.sieve_hit(n)]                      # the stages of the model: each drops something
+    left = [n for n in sieved if mm.base2(n)]
+    assert len(big) > len(sieved) > len(left) >= 3
+    assert eng.calls == [("probable_prime", len(big), 16), ("sieve", len(big)), ("base2", len(sieved)),
+                         ("generator_shares", len(left), 16), ("miller_rabin", len(left), 16)]
+
+
+def counted_draws(key, first_call):
+    """(draw, asked): the model's draws of DeviceRng(key, first_call) and the list of what was asked of them."""
+    draw, asked = mm.chacha_draws(key, first_call), []
+
+    def counted(count, bits, row_words=0):
+        asked.append((count, bits))
+        return draw(count, bits, row_words)
+
+    return counted, asked
+
+
+def test_shipped_search_equals_the_model():
+    """The comparison the end-to-end run makes on the device: the shipped search over the kernels' models, draw for draw —
+    ONE draw of bases per batch with survivors, none otherwise."""
+    key = bytes(range(32))
+    eng = MrEngine()
+    rng = DeviceRng(key, first_call=7)
+    draw, asked = counted_draws(key, 7)
+    want, verdicts = mm.prime_search(3, 64, draw, 8, 256)
+    assert _ints(eng.prime_search_t(3, 64, rng, rounds=8, batch=256)) == want and rng.next_call == 7 + len(asked)
+    assert eng.calls[0] == ("prime_search", 3, 64, 256) and [c[0] for c in eng.calls if c[0] in MARKERS] == ["prime_search"]
+    assert [c for c in eng.calls if c[0] == "sieve"] == [("sieve", 256)] * len(verdicts)
+    assert [c for c in eng.calls if c[0] == "generator_shares"] == [("generator_shares", count // 8, 8) for count, bits in asked if bits == 128]
+    assert eng.prime_search_t(0, 64, rng).shape == (0, 2) and rng.next_call == 7 + len(asked)      # a search for nothing draws nothing
+
+
+@pytest.mark.parametrize("words,bits", [(2, 33), (2, 63), (2, 64), (2, 32), (3, 33), (3, 63), (1, 32)])
+def test_candidate_range_check(words, bits):
+    """_mr_candidates: odd, at least `above`, at most `bits` bits — at widths that end inside a word, at a word boundary
+    below the rows' width and at the rows' full width, where the top bit is the int32's sign."""
+    eng = MrEngine()
+    rows_t = lambda *values: eng.to_device(limbs.pack(list(values), words))
+    top = (1 << bits) - 1
+    for legal in (top, (1 << (bits - 1)) + 1, 0x80000001, 3):
+        assert eng._mr_candidates(rows_t(legal, top), bits) == (2, words, bits)
+    refused = [top - 1, 0x80000000, 1]                                   # even rows, a row below 3
+    if bits < 32 * words:
+        refused += [(1 << bits) | 1, (1 << (32 * words - 1)) | 1]       # one bit above `bits`; the rows' top bit, a sign
+    if (bits + 31) // 32 < words:
+        refused.append((1 << (32 * ((bits + 31) // 32))) | 1)            # a set word above the top word of `bits`
+    for bad in refused:
+        for rows in (rows_t(bad), rows_t(top, bad), rows_t(bad, top)):
+            with pytest.raises(ValueError, match="odd, at least 3 and of at most"):
+                eng._mr_candidates(rows, bits)
+        assert eng._mr_candidates(rows_t(top, bad), bits, checked=True) == (2, words, bits)      # the caller made the rows
+    above = primes.SIEVE_BOUND
+    assert eng._mr_candidates(rows_t(above + 1), bits, above=above) == (1, words, bits)
+    with pytest.raises(ValueError, match=f"at least {above}"):
+        eng._mr_candidates(rows_t(top, above - 1), bits, above=above)
+    for bad_bits in (1, 32 * words + 1):
+        with pytest.raises(ValueError, match="bits must lie"):
+            eng._mr_candidates(rows_t(top), bad_bits)
+    assert eng._mr_candidates(rows_t(top), None) == (1, words, 32 * words)
+    assert eng.calls == []
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+def test_forced_bits_where_the_sign_of_the_word_lies(bits):
+    """_force_bits sets bit 31 of a word as the int32 it is: positions 31 and 63, next to 30, 62 and 0, on rows that have
+    the bits clear, set, and at random.  The rows read as unsigned are the model's."""
+    rnd = random.Random(bits)
+    eng = MrEngine()
+    whole = [0, (1 << bits) - 1, 1 << (bits - 1), 1 << (bits - 2)] + [rnd.getrandbits(bits) for _ in range(12)]
+    rows = eng._force_bits(eng.to_device(limbs.pack(whole, bits // 32)), (bits - 1, bits - 2, 0))
+    assert rows.dtype == eng.torch.int32 and _ints(rows) == [mm.force_bits(r, bits) for r in whole]
+    rows = eng._force_bits(eng.to_device(limbs.pack(whole, bits // 32)), (bits - 1, bits - 2, 0))      # the halves of bits + 1
+    assert _ints(rows) == [mm.force_half_bits(r, bits + 1) for r in whole]
+    for position in (0, 30, 31, bits - 1):
+        rows = eng._force_bits(eng.to_device(limbs.pack(whole, bits // 32)), (position,))
+        assert _ints(rows) == [r | (1 << position) for r in whole]
 
 
 def test_generate_argument_checks():
@@ -144,7 +221,7 @@ def test_generate_over_the_model_engine(key_length):
 def test_generate_batch_takes_one_search():
     eng = MrEngine()
     keys = PaillierPrivateKey.generate_batch(3, 128, rng=FakeRng(2), rounds=4, engine=eng)
-    assert [c[0] for c in eng.calls] == ["prime_search"] and eng.calls[0][1] == 6
+    assert [c[0] for c in eng.calls if c[0] in MARKERS] == ["prime_search"] and eng.calls[0][1] == 6
     found = [x for k in keys for x in (k.p, k.q)]
     assert len(set(found)) == 6 and all(x.bit_length() == 64 for x in found)
 
@@ -164,8 +241,8 @@ def test_check_primes_refuses_composites():
     assert key.check_primes(rounds=8, rng=FakeRng(1)) is False
     assert PaillierPrivateKey(561 * (2**61 - 1), p2, engine=eng).check_primes(rounds=8, rng=FakeRng(1)) is False
     small_bad = PaillierPrivateKey(2**61 - 1, 43 * 47, engine=eng)          # decided on the host
-    calls = len(eng.calls)
-    assert small_bad.check_primes() is False and len(eng.calls) == calls + 1      # only p went to the engine
+    calls = len([c for c in eng.calls if c[0] in MARKERS])
+    assert small_bad.check_primes() is False and len([c for c in eng.calls if c[0] in MARKERS]) == calls + 1      # only p went to the engine
 
 
 @pytest.mark.parametrize("bits", [512, 1024, 2048])

@@ -12,12 +12,14 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 import crt_model as cm  # noqa: E402
 
 from crt_enc_engine import CrtEncEngine, FakeRng  # noqa: E402
+from crt_engine import _ints  # noqa: E402
 from protocols.distributed_keygen_amd import limbs, synthetic  # noqa: E402
 from protocols.distributed_keygen_amd.private_key import PaillierPrivateKey  # noqa: E402
 
@@ -184,8 +186,8 @@ def test_fresh_mode_empty_batches_and_return_randomness():
     cts, ok, rs = eng.private_encrypt_batch(msgs, p, q, randomness=[3, 4, 5, 6], return_randomness=True)
     assert rs == [3, 4, 5, 6] and cts == [(1 + (m % n) * n) * pow(r, n, n2) % n2 for m, r in zip(msgs, rs)]
     assert eng.private_encrypt_batch([], p, q, rng=rng, return_randomness=True) == ([], [], [])
-    m_t = limbs.pack([1, 2], limbs.limbs_for(n))
-    d_t = limbs.pack([11, 12], limbs.limbs_for(n2))
+    m_t = eng.to_device(limbs.pack([1, 2], limbs.limbs_for(n)))
+    d_t = eng.to_device(limbs.pack([11, 12], limbs.limbs_for(n2)))
     for kwargs in ({}, dict(rng=rng, draws_t=d_t), dict(randomness_t=m_t, draws_t=d_t), dict(randomness_t=m_t, rng=rng, draws_t=d_t)):
         with pytest.raises(ValueError, match="exactly one"):
             eng.private_encrypt_t(m_t, p, q, **kwargs)
@@ -202,14 +204,15 @@ def test_tensor_level_formats_of_the_key_object():
     eng = CrtEncEngine()
     key = PaillierPrivateKey(p, q, engine=eng)
     msgs, rs = [3, n - 1, p, 9], [2, 3, 5 * q, 0]
-    rows, status = key.encrypt_t(limbs.pack(msgs, limbs.limbs_for(n)), randomness_t=limbs.pack(rs, limbs.limbs_for(n)))
-    assert rows.shape == (4, limbs.limbs_for(n2)) and rows.dtype == np.uint32 and status.tolist() == [0, 0, 2, 3]
-    assert limbs.unpack(rows) == [(1 + msgs[0] * n) * pow(2, n, n2) % n2, (1 + msgs[1] * n) * pow(3, n, n2) % n2, 0, 0]
-    again, status = key.randomize_t(rows[:2], randomness_t=limbs.pack([7, 8], limbs.limbs_for(n) + 2))
-    assert limbs.unpack(again) == [c * pow(r, n, n2) % n2 for c, r in zip(limbs.unpack(rows[:2]), (7, 8))] and not status.any()
-    noise, status = key.noise_t(2, randomness_t=limbs.pack([7, 8], limbs.limbs_for(n)))
-    assert limbs.unpack(noise) == [pow(7, n, n2), pow(8, n, n2)] and not status.any()
-    packed = eng.private_noise_t(2, p, q, draws_t=limbs.pack([p * p * 3, 5], limbs.limbs_for(n2)), packed=True)
+    rows_t = lambda values, words: eng.to_device(limbs.pack(values, words))
+    rows, status = key.encrypt_t(rows_t(msgs, limbs.limbs_for(n)), randomness_t=rows_t(rs, limbs.limbs_for(n)))
+    assert rows.shape == (4, limbs.limbs_for(n2)) and rows.dtype == torch.int32 and status.tolist() == [0, 0, 2, 3]
+    assert _ints(rows) == [(1 + msgs[0] * n) * pow(2, n, n2) % n2, (1 + msgs[1] * n) * pow(3, n, n2) % n2, 0, 0]
+    again, status = key.randomize_t(rows[:2], randomness_t=rows_t([7, 8], limbs.limbs_for(n) + 2))
+    assert _ints(again) == [c * pow(r, n, n2) % n2 for c, r in zip(_ints(rows[:2]), (7, 8))] and not status.any()
+    noise, status = key.noise_t(2, randomness_t=rows_t([7, 8], limbs.limbs_for(n)))
+    assert _ints(noise) == [pow(7, n, n2), pow(8, n, n2)] and not status.any()
+    packed = eng.private_noise_t(2, p, q, draws_t=rows_t([p * p * 3, 5], limbs.limbs_for(n2)), packed=True)
     assert packed.shape == (2, limbs.limbs_for(n2) + 1) and packed[:, -1].tolist() == [1, 0] and not packed[0, :-1].any()
     assert [name for name, *_ in eng.calls].count("lift") == 4
 
@@ -241,19 +244,42 @@ def test_fixed_window_moves_the_prime_modexps_off_the_shared_exponent_schedule()
     assert stub.calls == [("shared", 101, 13), ("multi", [101], [13], 7)]
 
 
+@pytest.mark.parametrize("idx", range(len(SHORT)))
+def test_fixed_window_route_inside_an_encryption(idx):
+    """With the fixed window the two modexps modulo the primes of a real encryption go through powmod_multi_t with one
+    group — nothing else changes, and the ciphertexts are the same bit for bit."""
+    p, q = SHORT[idx]
+    n = p * q
+    rnd = random.Random(400 + idx)
+    msgs, rs = [0, n - 1, rnd.randrange(n)], [1, n - 1, rnd.randrange(1, n)]
+    runs = []
+    for fixed in (False, True):
+        eng = CrtEncEngine()
+        eng._fixed_window = fixed
+        rows, status = eng.private_encrypt_t(eng.to_device(limbs.pack(msgs, limbs.limbs_for(n))), p, q,
+                                             randomness_t=eng.to_device(limbs.pack(rs, limbs.limbs_for(n))))
+        assert not status.any()
+        runs.append((rows, eng.calls))
+    assert torch.equal(runs[0][0], runs[1][0]) and _ints(runs[0][0]) == [(1 + m * n) * pow(r, n, n * n) % (n * n) for m, r in zip(msgs, rs)]
+    assert runs[0][1] == [("prime_split", 3), ("powmod_shared", 3), ("powmod_nsquare", 3), ("powmod_shared", 3), ("powmod_nsquare", 3),
+                          ("lift", 3, "message")]
+    assert runs[1][1] == [("prime_split", 3), ("powmod_multi", 1, 3, (q % (p - 1)).bit_length()), ("powmod_nsquare", 3),
+                          ("powmod_multi", 1, 3, (p % (q - 1)).bit_length()), ("powmod_nsquare", 3), ("lift", 3, "message")]
+
+
 def test_key_object_forwards_the_engine_keywords():
     p, q = SHORT[0]
     n = p * q
     eng = CrtEncEngine()
     key = PaillierPrivateKey(p, q, engine=eng)
-    m_t = limbs.pack([4, 5], limbs.limbs_for(n))
-    d_t = limbs.pack([11, 12], limbs.limbs_for(n * n))
+    m_t = eng.to_device(limbs.pack([4, 5], limbs.limbs_for(n)))
+    d_t = eng.to_device(limbs.pack([11, 12], limbs.limbs_for(n * n)))
     packed = key.encrypt_t(m_t, draws_t=d_t, side_by_side=False, packed=True)
     assert packed.shape == (2, limbs.limbs_for(n * n) + 1) and not packed[:, -1].any()
     rows, status = eng.private_encrypt_t(m_t, p, q, draws_t=d_t)
     assert (packed[:, :-1] == rows).all()
     rows2, _, kept = key.randomize_t(rows, draws_t=d_t, return_randomness=True)
-    assert limbs.unpack(kept) == [11, 12] and limbs.unpack(rows2) != limbs.unpack(rows)
+    assert _ints(kept) == [11, 12] and _ints(rows2) != _ints(rows)
     assert key.noise_t(2, draws_t=d_t, packed=True).shape == packed.shape
 
 

@@ -10,8 +10,8 @@ import random
 import sys
 from pathlib import Path
 
-import numpy as np
 import pytest
+import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
@@ -137,12 +137,14 @@ def test_decrypt_t_returns_rows_in_the_format_of_combine_t():
     p, q = KEYS[4]
     n = p * q
     rng = random.Random(2)
-    key = PaillierPrivateKey(p, q, engine=CrtEngine())
+    eng = CrtEngine()
+    key = PaillierPrivateKey(p, q, engine=eng)
     msgs = [3, n - 1, p]
-    rows = limbs.pack([encrypt(p, q, m, rng) for m in msgs] + [0], limbs.limbs_for(n * n))
+    rows = eng.to_device(limbs.pack([encrypt(p, q, m, rng) for m in msgs] + [0], limbs.limbs_for(n * n)))
     out, status = key.decrypt_t(rows)
-    assert out.shape == (4, limbs.limbs_for(n)) and out.dtype == np.uint32
-    assert limbs.unpack(out) == msgs + [0] and status.tolist() == [0, 0, 0, 3]
+    assert out.shape == (4, limbs.limbs_for(n)) and out.dtype == torch.int32
+    assert limbs.unpack(eng.to_host(out)) == msgs + [0] and status.tolist() == [0, 0, 0, 3]
+    assert eng.calls == [("split", 4), ("powmod_nsquare", 4), ("powmod_nsquare", 4), ("recombine", 4, False)]
 
 
 # ------------------------------------------------------------------ the C ABI, without a launch

@@ -16,9 +16,11 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 sys.path.insert(0, str(ROOT / "tests"))
 import mr_model as mm  # noqa: E402
+from crt_engine import MARKERS, _ints  # noqa: E402
 from safe_engine import FakeRng, SafeEngine  # noqa: E402
+from test_primes_host import counted_draws  # noqa: E402
 
-from protocols.distributed_keygen_amd import PaillierPrivateKey, limbs, primes, synthetic  # noqa: E402
+from protocols.distributed_keygen_amd import DeviceRng, PaillierPrivateKey, limbs, primes, synthetic  # noqa: E402
 
 
 def host_prime(n):
@@ -144,7 +146,57 @@ def test_device_decisions_over_the_model_engine():
     full_only = next(p for p in range(2**40 + 3, 2**41, 4) if host_prime(p) and not host_prime((p - 1) // 2))
     vals = [found[0], 23, half_only, full_only, found[1], found[0] + 4, 2 * mm.pseudoprime_half() + 1]
     assert primes.is_safe_prime_batch(vals, rounds=6, rng=FakeRng(2), engine=eng) == [True, True, False, False, True, False, False]
-    assert eng.calls == [("safe_prime", 6, 6)]
+    device = [p for p in vals if p != 23]                                 # 23 is decided on the host
+    left = [len(stage) for stage in mm.safe_prime_stages([(p - 1) // 2 for p in device], limbs.max_bits(device), 6, mm.chacha_draws(bytes(32)))]
+    assert 6 > left[0] >= left[1] >= left[2] >= 3                         # the pseudoprime half reaches the random rounds
+    assert eng.calls == [("safe_prime", 6, 6), ("safe_sieve", 6), ("base2", left[0]), ("safe_double", left[1]), ("base2", left[1]),
+                         ("generator_shares", left[2], 6), ("miller_rabin", left[2], 6)]
+
+
+def test_shipped_search_equals_the_model():
+    """The comparison the end-to-end run makes on the device: the shipped safe-prime search over the kernels' models."""
+    key = bytes(range(32))
+    eng = SafeEngine()
+    rng = DeviceRng(key, first_call=3)
+    draw, asked = counted_draws(key, 3)
+    want, verdicts = mm.safe_prime_search(2, 64, draw, 4, 2048)
+    assert _ints(eng.safe_prime_search_t(2, 64, rng, rounds=4, batch=2048)) == want and rng.next_call == 3 + len(asked)
+    assert all(host_safe(p) for p in want)
+    assert eng.calls[0] == ("safe_prime_search", 2, 64, 2048) and [c[0] for c in eng.calls if c[0] in MARKERS] == ["safe_prime_search"]
+    assert [c for c in eng.calls if c[0] == "safe_sieve"] == [("safe_sieve", 2048)] * len(verdicts)
+    assert [c for c in eng.calls if c[0] == "generator_shares"] == [("generator_shares", count // 4, 4) for count, bits in asked if bits == 63 + 64]
+    assert [c for c in eng.calls if c[0] == "safe_double"][-1] == ("safe_double", sum(verdicts[-1]))      # 2h + 1 of what the last batch kept
+
+
+def test_shipped_stages_equal_the_model():
+    """safe_prime_t stage by stage on halves of every kind that passes the joint sieve, a composite that passes both rounds
+    to the base 2, and random halves, most of which the sieve drops: every stage leaves something and drops something."""
+    bits, rounds, key = 64, 3, bytes([64]) * 32
+    kinds = mm.safe_cases(bits)
+    rnd = random.Random(bits)
+    psp = mm.pseudoprime_half()
+    assert mm.base2(psp) and mm.base2(2 * psp + 1) and not host_prime(psp) and not mm.safe_sieve_hit(psp)
+    halves = [h for kind in mm.SAFE_KINDS for h in kinds[kind]] + [psp] + [mm.force_half_bits(rnd.getrandbits(bits - 1), bits) for _ in range(8)]
+    rnd.shuffle(halves)
+    draw, asked = counted_draws(key, 5)
+    want = mm.safe_prime_stages(halves, bits, rounds, draw)
+    left = [len(stage) for stage in want]
+    assert len(halves) > left[0] > left[1] > left[2] > left[3] >= 1 and asked == [(left[2] * rounds, bits - 1 + 64)]
+    eng, rng, stages = SafeEngine(), DeviceRng(key, first_call=5), []
+    got = eng.safe_prime_t(eng.to_device(limbs.pack(halves, 2)), bits, rounds, rng, _stages=stages)
+    assert [stage.tolist() for stage in stages] == want
+    assert got.tolist() == [int(i in want[3]) for i in range(len(halves))] and rng.next_call == 6
+    assert eng.calls == [("safe_prime", len(halves), rounds), ("safe_sieve", len(halves)), ("base2", left[0]), ("safe_double", left[1]),
+                         ("base2", left[1]), ("generator_shares", left[2], rounds), ("miller_rabin", left[2], rounds)]
+    # nothing past the base 2 on h: no draw, no call number taken
+    del eng.calls[:]
+    composite = kinds["full"] + kinds["neither"]
+    assert eng.safe_prime_t(eng.to_device(limbs.pack(composite, 2)), bits, rounds, rng).tolist() == [0] * len(composite)
+    assert eng.calls == [("safe_prime", len(composite), rounds), ("safe_sieve", len(composite)), ("base2", len(composite))] and rng.next_call == 6
+    # nothing past the base 2 on p
+    del eng.calls[:]
+    assert eng.safe_prime_t(eng.to_device(limbs.pack(kinds["half"], 2)), bits, rounds, rng).tolist() == [0] * len(kinds["half"])
+    assert [c[0] for c in eng.calls] == ["safe_prime", "safe_sieve", "base2", "safe_double", "base2"] and rng.next_call == 6
 
 
 def test_argument_checks_reach_no_engine():
@@ -164,10 +216,11 @@ def test_argument_checks_reach_no_engine():
         primes.safe_prime_density(2)
     assert eng.calls == []
     rng = FakeRng(1)
+    rows_t = lambda values: eng.to_device(limbs.pack(values, 2))
     for call in (lambda: eng.safe_prime_search_t(1, 8, rng), lambda: eng.safe_prime_search_t(1, 64, rng, rounds=0),
-                 lambda: eng.safe_prime_t(limbs.pack([2**61 - 1], 2), 64, 0, rng), lambda: eng.safe_prime_t(limbs.pack([2**61 - 1], 2), 65, 4, rng),
-                 lambda: eng.safe_prime_t(limbs.pack([2**61], 2), 64, 4, rng), lambda: eng.safe_prime_t(limbs.pack([8191], 2), 64, 4, rng),
-                 lambda: eng.safe_double_t(limbs.pack([2**63], 2)), lambda: eng.safe_sieve_t(limbs.pack([5], 2), [3, 9, 4])):
+                 lambda: eng.safe_prime_t(rows_t([2**61 - 1]), 64, 0, rng), lambda: eng.safe_prime_t(rows_t([2**61 - 1]), 65, 4, rng),
+                 lambda: eng.safe_prime_t(rows_t([2**61]), 64, 4, rng), lambda: eng.safe_prime_t(rows_t([8191]), 64, 4, rng),
+                 lambda: eng.safe_double_t(rows_t([2**63])), lambda: eng.safe_sieve_t(rows_t([5]), [3, 9, 4])):
         with pytest.raises(ValueError):
             call()
     assert eng.calls == [] and rng.calls == []
@@ -176,8 +229,8 @@ def test_argument_checks_reach_no_engine():
 def test_double_of_the_kernels():
     eng = SafeEngine()
     vals = [0, 1, 2**63 - 1, 2**31, 0x8000000080000000 >> 1]
-    assert limbs.unpack(eng.safe_double_t(limbs.pack(vals, 2))) == [2 * h + 1 for h in vals]
-    assert list(eng.safe_sieve_t(limbs.pack([15, 7, 17, 8], 2), [3, 5])) == [1, 1, 1, 0]          # 7 = (15 - 1) / 2, 17 = 2 mod 5 = (5 - 1) / 2
+    assert _ints(eng.safe_double_t(eng.to_device(limbs.pack(vals, 2)))) == [2 * h + 1 for h in vals]
+    assert eng.safe_sieve_t(eng.to_device(limbs.pack([15, 7, 17, 8], 2)), [3, 5]).tolist() == [1, 1, 1, 0]          # 7 = (15 - 1) / 2, 17 = 2 mod 5 = (5 - 1) / 2
 
 
 @pytest.mark.parametrize("key_length", [128, 192])
@@ -196,7 +249,7 @@ def test_generate_safe_over_the_model_engine(key_length):
 def test_generate_batch_safe_takes_one_search_and_the_default_stays():
     eng = SafeEngine()
     keys = PaillierPrivateKey.generate_batch(2, 128, rng=FakeRng(2), rounds=4, engine=eng, safe=True)
-    assert [c[0] for c in eng.calls] == ["safe_prime_search"] and eng.calls[0][1] == 4
+    assert [c[0] for c in eng.calls if c[0] in MARKERS] == ["safe_prime_search"] and eng.calls[0][1] == 4
     found = [x for k in keys for x in (k.p, k.q)]
     assert len(set(found)) == 4 and all(host_safe(x) and x.bit_length() == 64 for x in found)
     # without the flag: the ordinary search, the same primes as an engine without the safe-prime methods finds

@@ -17,6 +17,7 @@ sys.path.insert(0, str(ROOT / "tools"))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import proof_model as pm  # noqa: E402
+from crt_engine import MARKERS  # noqa: E402
 from proof_engine import ProofEngine, tamperings  # noqa: E402
 
 from protocols.distributed_keygen_amd import limbs, threshold  # noqa: E402
@@ -173,7 +174,7 @@ def test_every_refusal_comes_before_an_engine_call():
         threshold.deal(PaillierPrivateKey(65267, 65239, engine=eng), 3, 1, rng=random.Random(1), engine=eng)
     assert eng.calls == []
     pub, shares = threshold.deal(key, 5, 2, rng=random.Random(1), engine=eng)            # the golden primes pass the check
-    assert [c[0] for c in eng.calls] == ["safe_prime"]
+    assert [c[0] for c in eng.calls if c[0] in MARKERS] == ["safe_prime"]
     del eng.calls[:]
     _, cts = ciphertexts(pub.n, 2)
     with pytest.raises(KeyError):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Python-int model of the strong-pseudoprime test of csrc/mx_mr.hpp and of the prime search around it
 (``Engine.mr_split_t`` / ``miller_rabin_t`` / ``miller_rabin_base2_t`` / ``probable_prime_t`` / ``prime_search_t``) —
-developer tool and test vehicle.
+developer tool and the ORACLE of the tests: the GPU tests compare the kernels and the shipped compositions with it, and
+so do the host tests, whose doubles (tests/mr_engine.py, tests/safe_engine.py) take only the primitives from here
+(split, round_passes, base2) and run the shipped pipeline of key_flows.PrivateKeyFlows over them.
 
     split(n)              (d, s) with n - 1 = 2^s d, d odd
     tail(n, x0, b, s)     the verdict of one round from x0 = b^d mod n: b = 0 modulo n (vacuous), x0 = 1, x0 = n - 1, or
